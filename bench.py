@@ -2,10 +2,15 @@
 """bench.py -- event-image pairs/s (extract + match, 346x260, 1024 keypoints) on N MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config sp_mnn|silk_mnn|sp_lg] [--batch B]
+                    [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (EIM.forward: event extractor + image extractor + matcher) over
 one batch of synthetic pairs already resident in HBM.  Default workload = BASELINE.json configs[1]:
 batch 32, 5-bin event voxel + gray image, SuperPoint-shaped extractors + MNN matcher.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs
+of the last timed step if --dump-outputs is given (see dump_outputs), print the result line.  Every
+other measurement or check listed below runs only with --full (the --no-* switches then trim it).
 
 One process per GPU.  Under a launcher (torchrun sets RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*) this
 process is a rank; started plainly with `--gpus N` (N > 1) it is the LAUNCHER: it never touches
@@ -14,7 +19,7 @@ init_process_group(env://) under a launcher, train_extractor.py:82-91) and exits
 Pairs are independent, so ranks shard them with NO data-path collective; the only RCCL traffic is
 the all-reduce of the metric accumulators (weak scaling: the per-GPU batch is fixed).
 
-Rank 0 prints ONE JSON line with the driver contract plus
+Rank 0 prints ONE JSON line with the driver contract plus, with --full,
   roofline         dominant kernel (conv1b), mean of >= 20 launches timed with HIP events
   roofline_stages  conv stage, descriptor-correlation GEMM, LightGlue GEMM / attention kernels
   cpu_baseline     the oracle (a port) on the host cores, bounded sample; `verified_pairs` = pairs of
@@ -23,7 +28,10 @@ Rank 0 prints ONE JSON line with the driver contract plus
                    (whole-job pairs/s over the slowest rank, per-rank min/max, RCCL world)
   extra_configs    legs for BASELINE configs[2], configs[3], the reference-complete dict, B=1 latency and the round-1 weights
   cpu_baseline_torch  plain PyTorch on the host cores (oracle/torch_cpu.py), bounded to a few seconds
-  rccl             world size seen by the process group + latency of the metric all-reduce (N > 1 or --spawn)
+  streams          overlap ratios of the streams a forward uses
+  rccl.allreduce_us  latency of the metric all-reduce (N > 1 or --spawn)
+and, with or without --full,
+  rccl             world size and backend of the process group (N > 1 or --spawn)
 """
 import argparse
 import importlib
@@ -81,7 +89,16 @@ def parse(argv=None):
     ap.add_argument("--spawn", action="store_true", help="go through the rank launcher even for --gpus 1 (one-rank RCCL group)")
     ap.add_argument("--dry-run-gloo", action="store_true",
                     help="launcher / collective rehearsal on CPU: ranks form a gloo group, all-reduce the metric accumulators, run no kernels")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: rooflines, stream overlap, CPU baselines + verification, scale legs, "
+                         "extra configs, the all-reduce latency (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: larger outputs as a fixed, seeded sample)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs is not None and (args.steps < 1 or args.kernel_only or args.layer_table):
+        ap.error("--dump-outputs writes the last timed step: it needs --steps >= 1 and neither --kernel-only nor --layer-table")
+    return args
 
 
 # ------------------------------------------------------------------------------------ launcher
@@ -161,8 +178,8 @@ SCALE_LEG_STEPS = 10
 
 def scale_leg_plan(args):
     """Workloads every rank runs after the headline, at every N (so that the N = 1, 2, 4, 8 lines of a scaling run each carry
-    them): BASELINE configs[4] = SP + LightGlue, 64 pairs per GPU (512 over 8 GPUs), rank-sharded like the headline."""
-    if args.no_scale_legs or args.kernel_only or args.layer_table or args.config == "sp_lg":
+    them): BASELINE configs[4] = SP + LightGlue, 64 pairs per GPU (512 over 8 GPUs), rank-sharded like the headline.  --full only."""
+    if not args.full or args.no_scale_legs or args.kernel_only or args.layer_table or args.config == "sp_lg":
         return []
     return [("sp_lg", WORKLOADS["sp_lg"][1], SCALE_LEG_STEPS)]
 
@@ -450,6 +467,83 @@ def timed_stream(wl, steps, depth=2):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     return el / steps, nm / (steps * wl.B)
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def output_arrays(outputs):
+    """The three dicts EIM.forward returns, as (name, [tensor, ...]) in dict order: `events.<key>`, `image.<key>`,
+    `matches.<key>`.  A tensor is a list of one; a per-image list is kept as its items.  Entries that hold no tensor (None,
+    dense entries not computed yet) are left out: reading them here would compute what the timed step did not."""
+    import torch
+    out = []
+    for side, d in zip(("events", "image", "matches"), outputs):
+        if d is None:
+            continue
+        for k in dict.keys(d):
+            v = dict.__getitem__(d, k)
+            if torch.is_tensor(v):
+                out.append((f"{side}.{k}", [v]))
+            elif isinstance(v, (list, tuple)) and v and all(torch.is_tensor(t) for t in v):
+                out.append((f"{side}.{k}", list(v)))
+    return out
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: what the last timed step returned, one DIR/<name>.npy per entry of output_arrays.
+    Floating tensors are written as float32 (float64 stays float64), integer and boolean ones as float64 (exact).  A per-image
+    list whose items share one shape is written stacked ([B, ...]); otherwise its items are flattened and concatenated, and
+    DIR/<name>.numel.npy holds their element counts.  When the files would exceed DUMP_BUDGET_BYTES, every entry larger than
+    a common cap (the largest power-of-two fraction of the biggest entry that fits) is replaced by a sample of `cap`
+    elements of its flattened array: sorted positions drawn without replacement by numpy's default_rng seeded with the
+    crc32 of the name, so that two runs with the same arguments write the same positions.  Returns a summary for the line."""
+    import zlib
+    import numpy as np
+    import torch
+    specs = []
+    for name, items in output_arrays(outputs):
+        n = sum(int(t.numel()) for t in items)
+        f64 = items[0].dtype == torch.float64 or not items[0].is_floating_point()
+        stacked = all(t.shape == items[0].shape for t in items)
+        specs.append((name, items, n, 8 if f64 else 4, stacked))
+        if not stacked:
+            specs.append((name + ".numel", [torch.tensor([float(t.numel()) for t in items], dtype=torch.float64)], len(items), 8, True))
+
+    def total(cap):
+        return sum(min(n, cap) * size for _, _, n, size, _ in specs)
+
+    cap = max([n for _, _, n, _, _ in specs] + [1])
+    while cap > 1 and total(cap) > DUMP_BUDGET_BYTES:
+        cap = (cap + 1) // 2
+    os.makedirs(out_dir, exist_ok=True)
+    sampled, written = [], 0
+    for name, items, n, size, stacked in specs:
+        dt, tdt = (np.float64, torch.float64) if size == 8 else (np.float32, torch.float32)
+        if n <= cap:
+            parts = [t.detach().to("cpu", tdt) for t in items]
+            if len(parts) == 1:
+                arr = parts[0].numpy()
+            elif stacked:
+                arr = torch.stack(parts).numpy()
+            else:
+                arr = torch.cat([p.reshape(-1) for p in parts]).numpy()
+        else:
+            pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, size=cap, replace=False))
+            chunks, o = [], 0
+            for t in items:  # the positions index the flattened concatenation of the items (= the stacked array when stacked)
+                k = int(t.numel())
+                lo, hi = np.searchsorted(pos, [o, o + k])
+                if hi > lo:
+                    idx = torch.from_numpy(pos[lo:hi] - o).to(t.device)
+                    chunks.append(t.detach().reshape(-1)[idx].to("cpu", tdt))
+                o += k
+            arr = torch.cat(chunks).numpy()
+            sampled.append(name)
+        arr = np.ascontiguousarray(arr, dtype=dt)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written += arr.nbytes
+    return {"dir": out_dir, "arrays": len(specs), "bytes": written, "sampled": sampled, "sample_elements": cap if sampled else None}
 
 
 def hip_time(torch, fn, reps, warm=2):
@@ -965,12 +1059,13 @@ def run_rank(args):
         dist.all_reduce(probe)  # communicator set-up happens here, not in the timed region
         torch.cuda.synchronize()
         assert int(probe[0].item()) == world, "RCCL all-reduce did not see every rank"
-        t0 = time.perf_counter()
-        for _ in range(20):
-            dist.all_reduce(probe)
-        torch.cuda.synchronize()
-        rccl = {"backend": dist.get_backend(), "world": world, "allreduce_us": round((time.perf_counter() - t0) / 20 * 1e6, 1),
-                "allreduce_payload_bytes": 64}
+        rccl = {"backend": dist.get_backend(), "world": world}
+        if args.full:
+            t0 = time.perf_counter()
+            for _ in range(20):
+                dist.all_reduce(probe)
+            torch.cuda.synchronize()
+            rccl.update(allreduce_us=round((time.perf_counter() - t0) / 20 * 1e6, 1), allreduce_payload_bytes=64)
     placements = gather_placements(placement, dist, world) if distributed else None
     if world != args.gpus and rank == 0:
         print(f"[bench] note: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE", file=sys.stderr)
@@ -1043,8 +1138,9 @@ def run_rank(args):
     stats = acc.as_dict()
     pairs_total = max(stats["pairs"], 1.0)
     value = stats["pairs"] / elapsed if elapsed > 0 else 0.0
+    dumped = dump_outputs(args.dump_outputs, last) if (rank == 0 and args.dump_outputs) else None
 
-    streams = stream_overlap_report(pkg, dev) if rank == 0 else None
+    streams = stream_overlap_report(pkg, dev) if (rank == 0 and args.full) else None
 
     # ---- all-rank legs (every N): BASELINE configs[4], SP + LightGlue at 64 pairs per GPU, sharded like the headline ----
     scale_legs, leg_wls = [], {}
@@ -1062,16 +1158,17 @@ def run_rank(args):
 
     roofline = stages = cpu_baseline = cpu_torch = None
     extras = []
-    do_extras = rank == 0 and not args.no_extras and (world == 1 or args.extras)
-    if rank == 0:
+    do_extras = rank == 0 and args.full and not args.no_extras and (world == 1 or args.extras)
+    if rank == 0 and (args.full or args.kernel_only):
         roofline = dominant_kernel_roofline(wl, value / max(world, 1), kernel_only=args.kernel_only)
 
     # ---- CPU baseline (the oracle: a port, not the reference files) + verification, N=1 only ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    do_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
+    if do_cpu:
         if last is None:
             last = step()
         cpu_baseline = cpu_baseline_and_verify(wl, args, last)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_cpu_torch and args.config == "sp_mnn":
+    if do_cpu and not args.no_cpu_torch and args.config == "sp_mnn":
         cpu_torch = cpu_torch_protocol(wl, torch)
 
     # ---- short extra legs: the other BASELINE configs, B=1 latency, the round-1 (un-calibrated) weights ----
@@ -1198,6 +1295,9 @@ def run_rank(args):
             out["placement"] = placements  # per rank: GPU, its NUMA node, the cores the rank is pinned to, thread-pool size
         if cpu_torch is not None:
             out["cpu_baseline_torch"] = cpu_torch
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        out["full"] = bool(args.full)
         print(json.dumps(out))
         sys.stdout.flush()
     if distributed:

@@ -76,10 +76,35 @@ def load_synth_weights(module, seed):
     return {k: list(v.shape) for k, v in sorted(new.items())}
 
 
+MAX_FIXTURE_BYTES = 1000 * 1024  # no committed file reaches 1 MiB
+
+
 def save(name, **arrays):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {name}: {os.path.getsize(path) / 1024:.1f} KiB")
+    """name.npz; a fixture that would reach MAX_FIXTURE_BYTES is split by keys, in order, into name.npz (with `meta`),
+    name.1.npz, ... of about equal raw size (tests/helpers.py::Golden reads the parts as one)."""
+    import glob
+    base = os.path.join(HERE, name[:-4])
+    for old in glob.glob(base + ".[0-9]*.npz"):
+        os.remove(old)
+    keys = sorted(arrays, key=lambda k: k != "meta")  # `meta` goes to name.npz (helpers.lg_noise reads it there)
+    n = 1
+    while True:
+        target = sum(np.asarray(v).nbytes for v in arrays.values()) / n
+        groups, acc = [[]], 0.0
+        for k in keys:
+            if groups[-1] and acc + np.asarray(arrays[k]).nbytes > target and len(groups) < n:
+                groups.append([])
+                acc = 0.0
+            groups[-1].append(k)
+            acc += np.asarray(arrays[k]).nbytes
+        paths = [base + (".npz" if i == 0 else f".{i}.npz") for i in range(len(groups))]
+        for path, g in zip(paths, groups):
+            np.savez_compressed(path, **{k: arrays[k] for k in g})
+        if all(os.path.getsize(p) < MAX_FIXTURE_BYTES for p in paths) or n >= len(keys):
+            break
+        n += 1
+    for p in paths:
+        print(f"wrote {os.path.basename(p)}: {os.path.getsize(p) / 1024:.1f} KiB")
 
 
 # =========================================================================================

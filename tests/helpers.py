@@ -30,20 +30,26 @@ synth = load_synth()
 
 
 class Golden:
+    """One fixture: tests/golden/<name>.npz (holds `meta`) plus <name>.1.npz, <name>.2.npz, ... when the generator had to split
+    it to keep every file under 1 MiB (gen_golden.py::save); the parts are read as one archive."""
+
     def __init__(self, name):
-        self.z = np.load(os.path.join(GOLDEN, name + ".npz"))
-        self.meta = json.loads(bytes(self.z["meta"]).decode())
+        parts = [np.load(os.path.join(GOLDEN, name + ".npz"))]
+        while os.path.exists(os.path.join(GOLDEN, f"{name}.{len(parts)}.npz")):
+            parts.append(np.load(os.path.join(GOLDEN, f"{name}.{len(parts)}.npz")))
+        self._part = {k: z for z in parts for k in z.files}
+        self.meta = json.loads(bytes(self["meta"]).decode())
         self.cases = {c["name"]: c for c in self.meta["cases"]}
 
     def __getitem__(self, k):
-        return self.z[k]
+        return self._part[k][k]
 
     def __contains__(self, k):
-        return k in self.z.files
+        return k in self._part
 
     def overrides(self, case):
         pre = f"{case}.override."
-        return {k[len(pre):]: self.z[k] for k in self.z.files if k.startswith(pre)}
+        return {k[len(pre):]: self[k] for k in self._part if k.startswith(pre)}
 
 
 def state_dict_for(case_meta, golden=None, seed_key="wseed"):

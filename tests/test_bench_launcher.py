@@ -19,7 +19,7 @@ def _run(*args, env_drop=("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MA
 
 
 def test_launcher_spawns_two_gloo_ranks():
-    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "4")
+    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "4", "--full")
     assert r.returncode == 0, r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout  # only rank 0 prints
@@ -42,13 +42,13 @@ def test_launcher_spawns_two_gloo_ranks():
 
 
 def test_scale_legs_can_be_switched_off_and_are_not_doubled_for_sp_lg():
-    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "1", "--no-scale-legs")
+    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "1", "--full", "--no-scale-legs")
     assert r.returncode == 0, r.stderr
     assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])["scale_legs"] == []
 
 
 def test_launcher_passes_config_and_batch():
-    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "1", "--config", "sp_lg", "--batch", "64")
+    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "1", "--full", "--config", "sp_lg", "--batch", "64")
     assert r.returncode == 0, r.stderr
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert d["config"]["pairs_per_gpu_per_step"] == 64 and d["config"]["global_batch"] == 128
@@ -86,7 +86,7 @@ def test_launcher_world_8_on_gloo_shards_512_pairs():
     assert d["pairs"] == 8 * 2 * 64
     assert d["matches"] == 2 * 10 * sum(range(1, 9))
     assert d["shard_ranges"] == [[64 * k, 64 * (k + 1)] for k in range(8)]  # contiguous, disjoint, covering 0..512
-    r = _run("--gpus", "8", "--dry-run-gloo", "--steps", "1")
+    r = _run("--gpus", "8", "--dry-run-gloo", "--steps", "1", "--full")
     assert r.returncode == 0, r.stderr
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     leg = d["scale_legs"][0]
@@ -213,3 +213,79 @@ def test_placement_divides_by_the_ranks_on_this_host(monkeypatch):
     assert plc.local_world() == 16 and plc.local_world(4) == 4
     monkeypatch.delenv("WORLD_SIZE")
     assert plc.local_world() == 1
+
+
+def test_plain_run_leaves_the_scale_legs_to_full():
+    """Without --full the line carries the headline only: the all-rank scale legs run with --full alone."""
+    r = _run("--gpus", "2", "--dry-run-gloo", "--steps", "3")
+    assert r.returncode == 0, r.stderr
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["pairs"] == 2 * 3 * 32 and d["scale_legs"] == []
+
+
+def test_dump_outputs_needs_a_timed_step():
+    for extra in (("--steps", "0"), ("--kernel-only",), ("--layer-table",)):
+        r = _run("--gpus", "1", "--dump-outputs", "unused", *extra)
+        assert r.returncode == 2 and "--dump-outputs" in r.stderr, (extra, r.stderr[-500:])
+
+
+def _bench_module():
+    """bench.py loaded in this process; the GPU_MAX_HW_QUEUES default it sets on import is undone (later tests share the process)."""
+    import importlib.util
+    keep = os.environ.get("GPU_MAX_HW_QUEUES")
+    spec = importlib.util.spec_from_file_location("einx_bench", BENCH)
+    mod = importlib.util.module_from_spec(spec)
+    try:
+        spec.loader.exec_module(mod)
+    finally:
+        if keep is None:
+            os.environ.pop("GPU_MAX_HW_QUEUES", None)
+        else:
+            os.environ["GPU_MAX_HW_QUEUES"] = keep
+    return mod
+
+
+def _fake_outputs():
+    g = torch.Generator().manual_seed(3)
+    ef = {"sparse_positions": [torch.rand(5, 3, generator=g), torch.rand(7, 3, generator=g)],
+          "score": torch.rand(2, 1, 40, 50, generator=g), "nms": torch.ones(2, 1, 4, 4, dtype=torch.uint8), "coarse_descriptors": None}
+    imf = {"sparse_positions": [torch.rand(6, 3, generator=g), torch.rand(6, 3, generator=g)], "image_size": [torch.tensor([260, 346])] * 2}
+    m = {"matches0": [torch.tensor([[0, -1, 2]]), torch.tensor([[1, 1, -1]])], "matching_scores0": torch.rand(2, 3, dtype=torch.float64, generator=g)}
+    return ef, imf, m
+
+
+def test_dump_outputs_writes_each_entry_as_float_npy(tmp_path):
+    import numpy as np
+    b = _bench_module()
+    ef, imf, m = _fake_outputs()
+    info = b.dump_outputs(str(tmp_path), (ef, imf, m))
+    arrs = {p.name[:-4]: np.load(p) for p in tmp_path.iterdir()}
+    assert set(arrs) == {"events.sparse_positions", "events.sparse_positions.numel", "events.score", "events.nms", "image.sparse_positions",
+                         "image.image_size", "matches.matches0", "matches.matching_scores0"}
+    assert info["arrays"] == len(arrs) and info["sampled"] == [] and info["bytes"] == sum(a.nbytes for a in arrs.values())
+    # ragged list: flattened items + their element counts; equal shapes: stacked
+    assert np.array_equal(arrs["events.sparse_positions"], torch.cat([t.reshape(-1) for t in ef["sparse_positions"]]).numpy())
+    assert arrs["events.sparse_positions.numel"].tolist() == [15.0, 21.0]
+    assert np.array_equal(arrs["image.sparse_positions"], torch.stack(imf["sparse_positions"]).numpy())
+    assert np.array_equal(arrs["events.score"], ef["score"].numpy()) and arrs["events.score"].dtype == np.float32
+    # integer / boolean entries as exact float64, float64 stays float64
+    assert arrs["matches.matches0"].dtype == np.float64 and arrs["matches.matches0"].tolist() == [[[0, -1, 2]], [[1, 1, -1]]]
+    assert arrs["events.nms"].dtype == np.float64 and arrs["image.image_size"].tolist() == [[260, 346]] * 2
+    assert np.array_equal(arrs["matches.matching_scores0"], m["matching_scores0"].numpy())
+
+
+def test_dump_outputs_samples_the_largest_entries_to_the_budget_and_repeats_itself(tmp_path, monkeypatch):
+    import numpy as np
+    b = _bench_module()
+    monkeypatch.setattr(b, "DUMP_BUDGET_BYTES", 8000)
+    ef, imf, m = _fake_outputs()
+    runs = []
+    for d in ("a", "b"):
+        info = b.dump_outputs(str(tmp_path / d), (ef, imf, m))
+        runs.append({p.name: np.load(p) for p in (tmp_path / d).iterdir()})
+        assert info["sampled"] == ["events.score"] and info["bytes"] <= 8000
+    assert runs[0].keys() == runs[1].keys() and all(np.array_equal(runs[0][k], runs[1][k]) for k in runs[0])
+    s = runs[0]["events.score.npy"]
+    assert s.ndim == 1 and s.size == info["sample_elements"] < ef["score"].numel()
+    assert np.isin(s, ef["score"].numpy().reshape(-1)).all() and np.unique(s).size == s.size  # distinct positions of the real map
+    assert np.array_equal(runs[0]["events.sparse_positions.npy"], torch.cat([t.reshape(-1) for t in ef["sparse_positions"]]).numpy())

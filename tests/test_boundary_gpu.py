@@ -149,13 +149,38 @@ def test_bench_one_rank_through_the_launcher_uses_rccl():
     from helpers import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--steps", "2", "--warmup", "0",
-                        "--no-cpu-baseline", "--no-extras", "--batch", "4"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--no-cpu-baseline", "--no-extras", "--batch", "4"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["rccl"]["world"] == 1 and d["rccl"]["backend"] == "nccl"
     assert d["value"] > 0 and d["config"]["pairs_per_gpu_per_step"] == 4 and d["roofline"]["frac"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the headline only (no roofline, CPU
+    baseline, scale legs or extra legs), K timed steps, and the last step's outputs as float32 / float64 .npy files."""
+    from helpers import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"scale_legs", "roofline_stages", "extra_configs", "cpu_baseline_torch", "streams"} & set(d)
+    files = sorted(p.name for p in out.iterdir())
+    assert len(files) == d["dumped_outputs"]["arrays"] and all(f.endswith(".npy") for f in files)
+    arrs = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert arrs["events.sparse_positions"].shape[0] == 4 or "events.sparse_positions.numel" in arrs
+    m0 = arrs["matches.matches0"]
+    assert m0.dtype == np.float64 and np.array_equal(m0, np.round(m0)) and m0.min() >= -1
 
 
 def test_torch_free_c_abi_host():
