@@ -89,6 +89,7 @@ SIGNATURES = {
     "einx_fork_stream_prepare": (c_int, [c_void_p]),
     "einx_fork_stream_release": (c_int, [c_void_p]),
     "einx_fork_stream_count": (c_int, []),
+    "einx_side_stream": (c_void_p, [c_void_p, c_int, ctypes.POINTER(c_void_p), c_int]),
     "einx_extract_shapes": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(ExtractShapes)]),
     "einx_extract_ws_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
     "einx_extract": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(ExtractOut), c_void_p]),

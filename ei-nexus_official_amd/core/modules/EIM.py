@@ -52,10 +52,10 @@ class EIM(nn.Module):
     _SIDE_STREAMS_MAX = 16
 
     def _side_stream(self, device):
-        """The stream the event extractor runs on beside the caller's.  HIP maps streams onto a small pool of hardware queues: a
-        side stream per model instance means that the third or fourth model of a process gets one that shares a queue with the
-        main stream, and its two extractors serialise (measured in bench.py's extra legs: B=1 1.23 ms instead of 0.92).  So all
-        instances share one per (device, caller stream), chosen by probing (round 6)."""
+        """The stream the event extractor runs on beside the caller's: lane 1 of the caller's stream in the library's side-stream
+        table (einx.h::einx_side_stream), a pool stream that a probe found running beside it and that lives as long as the
+        process.  On its first use the native fork streams of both callers are chosen as well, each beside its caller and clear
+        of the other streams of a forward."""
         cur = torch.cuda.current_stream(device)
         key = (device.type, device.index if device.index is not None else torch.cuda.current_device(), cur.cuda_stream)
         st = EIM._side_streams.get(key)
@@ -63,36 +63,14 @@ class EIM(nn.Module):
             from ..._lib import check
             from ... import _native as N
             lib = N.lib()
-            if torch.cuda.is_current_stream_capturing():  # no probe (it synchronises) and no stream creation inside a capture
+            if torch.cuda.is_current_stream_capturing():  # no probe (it synchronises) inside a capture
                 raise RuntimeError("einx: run one forward on this stream before capturing it (the side streams are chosen then)")
-            # a stream that runs BESIDE the caller's: which hardware queue a stream lands on depends on what the process created
-            # before it (a process group, a loader), so candidates from torch's pool are probed (einx_stream_overlap_us:
-            # elapsed / spin is ~1.1 side by side, ~1.3 on one compute pipe, ~2.1 on one queue) and the first clean one is kept
-            best, best_ratio = None, None
             with torch.cuda.device(device):
-                for _ in range(8):
-                    cand = torch.cuda.Stream(device=device)
-                    if cand.cuda_stream == cur.cuda_stream:
-                        continue
-                    if os.environ.get("EINX_NO_STREAM_PROBE"):  # (diagnostics: first stream of torch's pool, no probe)
-                        best = cand
-                        break
-                    us = ctypes.c_float()
-                    if lib.einx_stream_overlap_us(ctypes.c_void_p(cur.cuda_stream), ctypes.c_void_p(cand.cuda_stream), 100, ctypes.byref(us)) != 0:
-                        best = best or cand  # (no verdict from the probe: first candidate)
-                        break
-                    ratio = us.value / 100.0
-                    if best is None or ratio < best_ratio - 0.1:
-                        best, best_ratio = cand, ratio
-                    if ratio < 1.25:
-                        break
-                if best is None:
-                    best = torch.cuda.Stream(device=device)
-                while len(EIM._side_streams) >= EIM._SIDE_STREAMS_MAX:  # (oldest first; torch's pool owns the streams)
-                    EIM._side_streams.pop(next(iter(EIM._side_streams)))
-                st = EIM._side_streams[key] = best
-                # the native fork streams of both callers, each beside its caller and clear of the other three streams of a forward
-                # (einx.h::einx_fork_stream_prepare_beside)
+                h = lib.einx_side_stream(ctypes.c_void_p(cur.cuda_stream), 1, None, 0)
+                check(0 if h else -1, "einx_side_stream")
+                while len(EIM._side_streams) >= EIM._SIDE_STREAMS_MAX:  # (oldest first)
+                    EIM._side_streams.pop(next(iter(EIM._side_streams)), None)
+                st = EIM._side_streams[key] = torch.cuda.ExternalStream(h, device=device)
                 arr = (ctypes.c_void_p * 2)(st.cuda_stream, None)
                 check(lib.einx_fork_stream_prepare_beside(ctypes.c_void_p(cur.cuda_stream), arr, 1), "einx_fork_stream_prepare_beside")
                 arr = (ctypes.c_void_p * 2)(cur.cuda_stream, lib.einx_fork_stream_of(ctypes.c_void_p(cur.cuda_stream)))

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "../../include/einx.h"
 #include "../../include/einx_math.h"
 
@@ -46,6 +48,14 @@ class EinxProfScope {
 
 #define EINX_PROF(name, stream) EinxProfScope einx_prof_scope_(name, (hipStream_t)(stream))
 bool einx_profile_active();  // the per-launch scopes are recording: kernels are meant to be timed alone (no concurrent branches)
+
+// streams.hip: the side of `caller` (a pool stream beside it, fork / join events) for ONE fork .. join section, locked in *lock
+// until the section has been enqueued; NULL when none can be had: the caller then enqueues both branches in line.
+struct EinxSide {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+const EinxSide* einx_side_acquire(hipStream_t caller, std::unique_lock<std::mutex>* lock);
 
 // Workgroups are dealt round-robin over the 8 XCDs in linear dispatch order (observed placement: speed only, never
 // correctness), each XCD with its own L2.  xcd_contiguous() turns the linear workgroup id into a work-item id such that every

@@ -17,50 +17,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <map>
-#include <memory>
 #include <mutex>
 #include <new>
 #include <vector>
 
 #include "einx_common.h"
-
-// One side (a library-owned stream + fork / join events) per (device, caller stream), shared by EVERY extractor handle of the
-// process (round 5; rounds 3-4 kept one per handle): HIP maps streams onto its few hardware queues, so the streams of the fifth or
-// sixth handle of a process landed on the queue of a caller's stream and the fork serialised -- bench.py's single-pair leg ran
-// 1.06 instead of 0.77 ms per forward once two more streams had been created before its model
-// (tools/experiments/r5_eager_after_run2.py).  Round 6: BOUNDED, and no stream is ever destroyed.  The streams come from a POOL of
-// EINX_FORK_STREAM_POOL streams per device, created together at the first use on that device and kept for the life of the process;
-// a side BORROWS the pool stream that a probe finds running beside its caller (pick_side_stream), and owns only its two events.
-// At most EINX_FORK_STREAMS_MAX sides exist; a call on a further stream evicts the least recently used side that no call holds
-// (shared_ptr: a side in use outlives its map entry), einx_fork_stream_release drops one explicitly.  (An earlier form of this
-// round created up to eight candidate streams per side and destroyed the rejected ones, and destroyed a side's stream at
-// eviction: with hipGraphs in the same process, hipGraphLaunch of ROCm 7.2 then crashed in hip::Graph::UpdateStreams after
-// some tens of captures -- tools/experiments/r6_modes_crash.py, profiles/r06_notes.md 7.)  hipEventDestroy on events with
-// enqueued work is deferred by the runtime until that work has drained.
-// `mu` is held while a call enqueues its fork .. join section, so two host threads that enqueue on one stream cannot interleave
-// on the events; re-recording an event does not disturb waits that were enqueued on its earlier record.  Two sides may borrow
-// the same pool stream (more callers than pool streams): their sections then run one after the other, each between its own events.
-struct EinxSide {
-  hipStream_t stream = nullptr;  // borrowed from the device's pool: never destroyed
-  hipEvent_t fork = nullptr, join = nullptr;
-  int dev = 0;
-  unsigned long long last_use = 0;
-  std::mutex mu;
-  EinxSide() = default;
-  EinxSide(const EinxSide&) = delete;
-  EinxSide& operator=(const EinxSide&) = delete;
-  ~EinxSide() {
-    int cur = 0;
-    const bool sw = (fork || join) && hipGetDevice(&cur) == hipSuccess && cur != dev;
-    if (sw) (void)hipSetDevice(dev);
-    if (fork) (void)hipEventDestroy(fork);
-    if (join) (void)hipEventDestroy(join);
-    if (sw) (void)hipSetDevice(cur);
-  }
-};
 
 struct einx_extractor {
   einx_extractor_desc d;
@@ -91,155 +52,6 @@ struct Plan {
 // alternating libraries).  The full-resolution networks (SiLK family) measured the same either way at B = 32 and keep the limit.
 constexpr long kForkMaxCells = 8192;  // B x head pixels up to which the two head branches of a full-resolution network run concurrently
 bool fork_heads(const einx_extractor* e, const Plan& pl, int B) { return e->d.cell == 8 || (long)B * pl.hc * pl.wc <= kForkMaxCells; }
-
-// the sides of the process: (device, caller stream) -> side, with a use stamp for the LRU bound
-typedef std::map<std::pair<int, hipStream_t>, std::shared_ptr<EinxSide>> SideMap;
-std::mutex g_sides_mu;
-unsigned long long g_side_clock = 0;
-SideMap& side_map() {
-  static SideMap* m = new SideMap();  // (never destructed: no HIP calls at process exit)
-  return *m;
-}
-
-// The pool stream for `caller`'s side: one that runs BESIDE it.  HIP deals streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4
-// by default) on a handful of compute pipes; which queue a stream got depends on everything the process created before it (torch's
-// stream pool, a process group's streams, a loader's copy streams), and a side stream on its caller's queue serialises the fork
-// (bench.py under torchrun with 4 queues: einx_stream_overlap_us(caller, fork stream) = 2.1).  So the choice is probed (round 6):
-// the pool's streams are tried, least borrowed first, until one overlaps with the caller and, if possible, with the streams the
-// host names (einx_fork_stream_prepare_beside) and the side streams of the two most recently used other sides of the device; the
-// best one is borrowed.  Skipped (least borrowed stream taken) while the caller is capturing.  A few hundred microseconds per
-// stream tried, once per (device, caller stream).  Called with g_sides_mu held and `dev` current.
-constexpr int kProbeSpinUs = 100;
-struct StreamPool {
-  std::vector<hipStream_t> streams;
-};
-StreamPool* pool_for(int dev) {
-  static std::map<int, StreamPool>* pools = new std::map<int, StreamPool>();  // (never destructed: no HIP calls at process exit)
-  StreamPool& p = (*pools)[dev];
-  if (p.streams.empty()) {
-    for (int i = 0; i < EINX_FORK_STREAM_POOL; ++i) {
-      hipStream_t st = nullptr;
-      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) break;
-      p.streams.push_back(st);
-    }
-    if (p.streams.empty()) (void)hipGetLastError();
-  }
-  return p.streams.empty() ? nullptr : &p;
-}
-
-hipStream_t pick_side_stream(const SideMap& sides, int dev, hipStream_t caller, void* const* beside, int n_beside) {
-  static const bool debug = getenv("EINX_DEBUG_STREAMS") != nullptr;
-  static const bool no_probe = getenv("EINX_NO_STREAM_PROBE") != nullptr;  // (diagnostics: no probe, least borrowed stream)
-  StreamPool* pool = pool_for(dev);
-  if (!pool) return nullptr;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool probe = !no_probe && hipStreamIsCapturing(caller, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
-  if (!probe) (void)hipGetLastError();
-  // peers: (stream, weight) -- the caller first
-  std::vector<std::pair<hipStream_t, int>> peers;
-  peers.push_back({caller, 8});
-  for (int i = 0; probe && i < n_beside; ++i)
-    if ((hipStream_t)beside[i] != caller) peers.push_back({(hipStream_t)beside[i], 2});
-  if (probe) {
-    std::vector<const EinxSide*> recent;
-    for (int k = 0; k < 2; ++k) {
-      SideMap::const_iterator best = sides.end();
-      for (SideMap::const_iterator it = sides.begin(); it != sides.end(); ++it) {
-        if (!it->second || it->first.first != dev || it->first.second == caller || !it->second->stream) continue;
-        bool taken = false;
-        for (const EinxSide* r : recent) taken = taken || r == it->second.get();
-        if (!taken && (best == sides.end() || it->second->last_use > best->second->last_use)) best = it;
-      }
-      if (best == sides.end()) break;
-      recent.push_back(best->second.get());
-      // (only the side's OWN stream: its caller's handle may belong to a stream the host has destroyed since)
-      bool have = false;
-      for (const std::pair<hipStream_t, int>& pr : peers) have = have || pr.first == best->second->stream;
-      if (!have) peers.push_back({best->second->stream, 2});
-    }
-  }
-  // pool streams, least borrowed first (ties: pool order)
-  const int np = (int)pool->streams.size();
-  std::vector<int> borrowed(np, 0), order(np);
-  for (SideMap::const_iterator it = sides.begin(); it != sides.end(); ++it)
-    for (int i = 0; i < np; ++i)
-      if (it->second && it->first.first == dev && it->second->stream == pool->streams[i]) ++borrowed[i];
-  for (int i = 0; i < np; ++i) order[i] = i;
-  for (int i = 1; i < np; ++i)
-    for (int j = i; j > 0 && borrowed[order[j]] < borrowed[order[j - 1]]; --j) {
-      const int t = order[j];
-      order[j] = order[j - 1];
-      order[j - 1] = t;
-    }
-  int best_i = -1, best_cost = 1 << 30;
-  for (int c = 0; c < np; ++c) {
-    hipStream_t st = pool->streams[order[c]];
-    if (st == caller) continue;
-    int cost = 0;
-    if (probe) {
-      for (const std::pair<hipStream_t, int>& pr : peers) {
-        if (pr.first == st) {  // a stream the side has to stay clear of IS this pool stream
-          cost += 4 * pr.second;
-          continue;
-        }
-        float us = 0.f;
-        if (einx_stream_overlap_us((void*)pr.first, (void*)st, kProbeSpinUs, &us) != EINX_OK) continue;  // (no verdict: no cost)
-        const float ratio = us / kProbeSpinUs;
-        cost += ratio > 1.6f ? 4 * pr.second : ratio > 1.25f ? pr.second : 0;  // one queue / (probably) one pipe
-        if (debug) fprintf(stderr, "[einx streams] caller %p pool stream %d (%p) vs %p: %.2f\n", (void*)caller, order[c], (void*)st, (void*)pr.first, ratio);
-      }
-    }
-    if (debug) fprintf(stderr, "[einx streams] caller %p pool stream %d cost %d (borrowed by %d)\n", (void*)caller, order[c], cost, borrowed[order[c]]);
-    if (cost < best_cost) {
-      best_cost = cost;
-      best_i = order[c];
-    }
-    if (cost == 0) break;
-  }
-  return best_i >= 0 ? pool->streams[best_i] : nullptr;
-}
-
-// the side of `caller` (keyed on the stream's OWN device, not on the current one); the returned reference keeps it alive
-std::shared_ptr<EinxSide> side_for(hipStream_t caller, void* const* beside = nullptr, int n_beside = 0) {
-  int dev = 0;
-  if (caller) {
-    if (hipStreamGetDevice(caller, &dev) != hipSuccess) return nullptr;
-  } else if (hipGetDevice(&dev) != hipSuccess) {
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> lk(g_sides_mu);
-  SideMap& sides = side_map();
-  std::shared_ptr<EinxSide>& slot = sides[{dev, caller}];
-  if (!slot) {
-    std::shared_ptr<EinxSide> sd = std::make_shared<EinxSide>();
-    sd->dev = dev;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != dev;
-    if (sw) (void)hipSetDevice(dev);
-    sd->stream = pick_side_stream(sides, dev, caller, beside, n_beside);
-    const bool ok = sd->stream != nullptr && hipEventCreateWithFlags(&sd->fork, hipEventDisableTiming) == hipSuccess &&
-                    hipEventCreateWithFlags(&sd->join, hipEventDisableTiming) == hipSuccess;
-    if (sw) (void)hipSetDevice(cur);
-    if (!ok) {
-      sides.erase({dev, caller});
-      return nullptr;  // (~EinxSide releases what was created)
-    }
-    slot = sd;
-    // bound: evict least recently used sides nobody holds (use_count 1 = only the map)
-    while ((int)sides.size() > EINX_FORK_STREAMS_MAX) {
-      SideMap::iterator victim = sides.end();
-      for (SideMap::iterator it = sides.begin(); it != sides.end(); ++it)
-        if (it->second != sd && it->second.use_count() == 1 && (victim == sides.end() || it->second->last_use < victim->second->last_use)) victim = it;
-      if (victim == sides.end()) break;  // every other side is in use right now: over the bound until they return
-      sides.erase(victim);
-    }
-    std::shared_ptr<EinxSide> out = sd;
-    out->last_use = ++g_side_clock;
-    return out;
-  }
-  slot->last_use = ++g_side_clock;
-  return slot;
-}
 
 // Padder.__init__ arithmetic (core/modules/utils/util.py:6-15)
 void padder(int h, int w, int p, int* w0, int* w1, int* h0, int* h1) {
@@ -364,54 +176,6 @@ EINX_EXPORT einx_extractor* einx_extractor_create(const einx_extractor_desc* d) 
 }
 
 EINX_EXPORT void einx_extractor_destroy(einx_extractor* e) { delete e; }
-
-EINX_EXPORT int einx_fork_stream_prepare(void* stream) {
-  if (!side_for((hipStream_t)stream)) {
-    einx_set_error("einx_fork_stream_prepare: could not create the side stream / events");
-    return EINX_ERR_LAUNCH;
-  }
-  return EINX_OK;
-}
-
-EINX_EXPORT int einx_fork_stream_prepare_beside(void* stream, void* const* beside, int n_beside) {
-  EINX_CHECK_ARG(n_beside >= 0 && n_beside <= 8 && (beside || n_beside == 0), "0..8 streams to stay clear of");
-  if (!side_for((hipStream_t)stream, beside, n_beside)) {
-    einx_set_error("einx_fork_stream_prepare_beside: could not create the side stream / events");
-    return EINX_ERR_LAUNCH;
-  }
-  return EINX_OK;
-}
-
-EINX_EXPORT int einx_fork_stream_release(void* stream) {
-  std::vector<std::shared_ptr<EinxSide>> dropped;  // destroyed after the map lock is released
-  {
-    std::lock_guard<std::mutex> lk(g_sides_mu);
-    SideMap& sides = side_map();
-    for (SideMap::iterator it = sides.begin(); it != sides.end();) {
-      if (it->first.second == (hipStream_t)stream) {
-        dropped.push_back(it->second);
-        it = sides.erase(it);
-      } else {
-        ++it;
-      }
-    }
-  }
-  return EINX_OK;
-}
-
-EINX_EXPORT void* einx_fork_stream_of(void* stream) {
-  int dev = 0;
-  if (stream ? hipStreamGetDevice((hipStream_t)stream, &dev) != hipSuccess : hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(g_sides_mu);
-  SideMap& sides = side_map();
-  SideMap::iterator it = sides.find({dev, (hipStream_t)stream});
-  return it == sides.end() ? nullptr : (void*)it->second->stream;
-}
-
-EINX_EXPORT int einx_fork_stream_count(void) {
-  std::lock_guard<std::mutex> lk(g_sides_mu);
-  return (int)side_map().size();
-}
 
 EINX_EXPORT int einx_extract_shapes(const einx_extractor* e, int H, int W, einx_extract_shapes_t* s) {
   EINX_CHECK_ARG(e && s, "null pointer");
@@ -545,9 +309,8 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
     if (e->d.cell == 8) r = einx_normalize_map(o->raw, B, D, h * w, e->d.desc_scale, o->coarse, o->raw_cl, st);
     return r;
   };
-  const std::shared_ptr<EinxSide> sd = fork ? side_for((hipStream_t)stream) : nullptr;  // (held until the call returns)
-  std::unique_lock<std::mutex> side_lock;
-  if (sd) side_lock = std::unique_lock<std::mutex>(sd->mu);
+  std::unique_lock<std::mutex> side_lock;  // (held until the call returns)
+  const EinxSide* sd = fork ? einx_side_acquire((hipStream_t)stream, &side_lock) : nullptr;
   if (sd) {  // fork: the descriptor branch runs beside the detector branch
     if (hipEventRecord(sd->fork, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(sd->stream, sd->fork, 0) != hipSuccess) {
       einx_set_error("einx_extract: fork failed");

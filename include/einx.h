@@ -11,10 +11,9 @@
  *   - the caller makes the device of `stream` and of the buffers the current HIP device (hipSetDevice) before a call;
  *   - return 0 on success, negative on error (einx_last_error() gives the text);
  *   - no device-memory allocation inside: callers pass workspaces sized by the *_ws_bytes helpers.  Two documented pieces of
- *     library-owned state: (a) a pool of EINX_FORK_STREAM_POOL streams per device, created at the first einx_extract that
- *     forks on that device and never destroyed, and two events per (device, caller stream) that forks (see einx_extract),
- *     shared by every handle of the process; at most EINX_FORK_STREAMS_MAX such pairs exist at a time (least recently used
- *     first out; einx_fork_stream_release drops one explicitly); (b) einx_voxel_grid /
+ *     library-owned state: (a) per device, two pools of EINX_FORK_STREAM_POOL side streams and EINX_FORK_STREAMS_MAX slots of two
+ *     events each, created at the first use on that device and never destroyed; a slot lends a (caller stream, lane) the pool
+ *     stream that runs beside it (see einx_fork_stream_prepare), shared by every handle of the process; (b) einx_voxel_grid /
  *     einx_events_mask keep a few hundred bytes of pinned staging per host thread for the host offsets array;
  *   - einx_build_flags() tells a shipped library from a timing-only experiment build (see below).
  * No torch types cross this boundary.  INTEGRATION.md shows the ctypes binding.
@@ -70,8 +69,8 @@ int einx_math_eval(int fn, const float* x, long long n, float* y, void* stream);
  * streams onto a few hardware queues; two that share one serialise, and which share depends on everything the process created
  * before (a process group's streams, a loader's copy streams).  Holds one wave spinning for spin_us (1..5000) on each stream
  * between a common start and end and returns the elapsed time in *elapsed_us: about spin_us when they overlap, about twice that
- * when they do not (or when a == b).  Synchronises with both streams; not capturable.  The Python package uses it to choose the
- * event extractor's side stream, einx_fork_stream_prepare to choose the fork streams. */
+ * when they do not (or when a == b).  Synchronises with both streams; not capturable.  The library uses it to choose its side
+ * streams (einx_fork_stream_prepare). */
 int einx_stream_overlap_us(void* stream_a, void* stream_b, int spin_us, float* elapsed_us);
 
 /* Measurement aid (no reference counterpart; the reference's scripts time with wall clocks around
@@ -443,30 +442,28 @@ typedef struct einx_weight_watch {
 
 einx_extractor* einx_extractor_create(const einx_extractor_desc* d); /* NULL on error (einx_last_error) */
 void einx_extractor_destroy(einx_extractor* e);
-/* Optional: choose the library's side stream and create the fork / join events of `stream` NOW instead of at the first
- * einx_extract that forks on it.  HIP deals streams onto a few hardware queues on the GPU's compute pipes (GPU_MAX_HW_QUEUES, 4
- * by default), and which one a stream got depends on everything the process created before it: a side stream on its caller's
- * queue serialises the fork (single pair: 0.77 -> 1.06 ms).  Since round 6 the choice is PROBED (einx_stream_overlap_us): the
- * library keeps EINX_FORK_STREAM_POOL streams per device (created together at the first use, never destroyed) and lends
- * `stream` the one that runs beside it and beside the side streams of the two most recently used other sides of the device.
- * The probe synchronises with `stream` (a few hundred microseconds per pool stream tried, once per (device, stream)); it is
- * skipped while `stream` is capturing.  A host that wants that cost at start-up calls this once per caller stream; the Python
- * package does so when a model is first used on a device. */
-int einx_fork_stream_prepare(void* stream);
-/* The same with up to 8 further streams the new side stream should stay clear of (a host that runs two extractors on two streams
- * names the other extractor's stream and its side stream, einx_fork_stream_of).  No effect when `stream` has a side already. */
-int einx_fork_stream_prepare_beside(void* stream, void* const* beside, int n_beside);
-/* The library keeps at most EINX_FORK_STREAMS_MAX (device, caller stream) sides; a call on a further stream evicts the least
- * recently used one that no call is using at that moment (its events are destroyed once their enqueued work has drained; its
- * stream goes back to the pool), so a server that creates a stream per request does not grow HIP streams / events without
- * bound: EINX_FORK_STREAM_POOL streams per device for the life of the process, whatever the host does.
- * einx_fork_stream_release drops the side of `stream` now (a host that destroys a stream it has made calls on; optional).
- * einx_fork_stream_count: sides alive at the moment (tests, diagnostics). */
+/* Side streams (no reference counterpart).  einx_extract forks onto a side stream of its caller's stream; a host that runs two
+ * extractors on two streams wants the second beside the first.  HIP deals streams onto a few hardware queues, and a side stream
+ * on its caller's queue serialises the fork (single pair: 0.77 -> 1.06 ms).  So, per device, the library keeps EINX_FORK_STREAMS_MAX
+ * slots of two events and, per lane, EINX_FORK_STREAM_POOL streams (created at the first use, never destroyed).  A slot is keyed
+ * on (caller stream, lane) -- lane 0: einx_extract's fork, lane 1: einx_side_stream -- and lent the stream of its lane's pool that
+ * a probe (einx_stream_overlap_us) finds beside the caller, the `beside` streams and the streams of the two most recently used
+ * other slots of the device.  A new key takes a free slot or the least recently used one that no call holds (with none left,
+ * einx_extract runs its branches in line, the same bits, and the calls below fail).  The probe synchronises with the caller's
+ * stream (a few hundred microseconds per pool stream tried, once per key; skipped while it is capturing); probes of one device
+ * take turns, nothing else waits for them.
+ * einx_fork_stream_prepare[_beside]: choose the lane-0 side of `stream` NOW instead of at the first einx_extract that forks on it,
+ * staying clear of up to 8 `beside` streams (the other extractor's stream and its side stream); no effect when it has one.
+ * einx_side_stream: the side stream of `stream` in `lane` (0 or 1), lent for the life of the process; NULL on error.
+ * einx_fork_stream_release un-keys the slots of `stream` (a host that destroys a stream it has made calls on; optional).
+ * einx_fork_stream_count: keyed slots, all devices; einx_fork_stream_of: the lane-0 side stream, NULL when none (diagnostics). */
 #define EINX_FORK_STREAMS_MAX 16
 #define EINX_FORK_STREAM_POOL 8
+int einx_fork_stream_prepare(void* stream);
+int einx_fork_stream_prepare_beside(void* stream, void* const* beside, int n_beside);
+void* einx_side_stream(void* stream, int lane, void* const* beside, int n_beside);
 int einx_fork_stream_release(void* stream);
 int einx_fork_stream_count(void);
-/* the side stream (a hipStream_t) the library forks `stream` onto, NULL when none exists yet (diagnostics: einx_stream_overlap_us) */
 void* einx_fork_stream_of(void* stream);
 int einx_extract_shapes(const einx_extractor* e, int H, int W, einx_extract_shapes_t* shapes);
 /* nms_iters: NMS pass budget per call (see einx_detect); <= 0 selects the default (8) in BOTH functions below.  The
@@ -476,11 +473,11 @@ size_t einx_extract_ws_bytes(const einx_extractor* e, int B, int H, int W, int c
  * ws: device scratch, ws_bytes >= einx_extract_ws_bytes(e, B, H, W, out->cap, nms_iters) (checked).
  * Networks with 1/8-resolution heads (cell == 8; full-resolution networks while B x head pixels <= 8192) enqueue the descriptor
  * branch on a library-owned side stream between a fork and a join event of `stream`; every return path has `stream` wait for the
- * join.  The side stream and its two events are created on the FIRST such call for a (device, stream) pair (or by
- * einx_fork_stream_prepare), shared by every handle of the process and bounded in number (einx_fork_stream_release) -- so make one un-captured call (or the prepare call) per
- * stream before capturing einx_extract into a hipGraph (stream / event creation is not capturable).  While `stream` is being
- * captured the branches are enqueued in line (no fork: a fork nested in a caller's own fork / join makes hipStreamEndCapture of
- * ROCm 7.2 crash).  Calls that fork from one stream are serialised on a mutex. */
+ * join.  The side stream is chosen on the FIRST such call for a (device, stream) pair (or by einx_fork_stream_prepare), shared by
+ * every handle of the process -- so make one un-captured call (or the prepare call) per stream before capturing einx_extract into
+ * a hipGraph (the probe is not capturable).  While `stream` is being captured the branches are enqueued in line (no fork: a fork
+ * nested in a caller's own fork / join makes hipStreamEndCapture of ROCm 7.2 crash).  Calls that fork from one stream are
+ * serialised on a mutex. */
 int einx_extract(const einx_extractor* e, float* in, const uint8_t* mask, int B, int H, int W, int nms_iters, void* ws,
                  size_t ws_bytes, const einx_extract_out* out, void* stream);
 /* the same call with the weight watch riding on it (watch == NULL or watch->n == 0: exactly einx_extract) */

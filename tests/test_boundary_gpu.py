@@ -683,9 +683,9 @@ def test_superpoint_wrong_channel_count_raises_like_conv1a():
 # ------------------------------------------------------------------ library-owned side streams are bounded
 def test_fork_streams_stay_bounded_over_many_caller_streams():
     """einx_extract forks its descriptor branch onto a library-owned side stream per (device, caller stream).  Round 5 kept every
-    side for the life of the process: a server that creates a stream per request grew HIP streams + events without bound.  Now at
-    most EINX_FORK_STREAMS_MAX sides exist (least recently used first out, never one that a call is using), their streams are
-    lent from a pool of 8 per device, and einx_fork_stream_release drops one explicitly.  64 short-lived caller streams: the count stays bounded, every result equals
+    side for the life of the process: a server that creates a stream per request grew HIP streams + events without bound.  Now a
+    device has EINX_FORK_STREAMS_MAX slots (least recently used first re-keyed, never one that a call is using), their streams are
+    lent from a pool of 8 per device, and einx_fork_stream_release un-keys one explicitly.  64 short-lived caller streams: the count stays bounded, every result equals
     the first one bit for bit."""
     import ctypes
     L = pkg.native.lib()
@@ -766,6 +766,61 @@ def test_side_streams_are_chosen_to_run_beside_their_callers():
     side2 = EIM._side_streams[("cuda", torch.cuda.current_device(), s2.cuda_stream)].cuda_stream
     assert side2 != s2.cuda_stream and ratio(s2.cuda_stream, side2) < 1.6
     assert len(EIM._side_streams) <= EIM._SIDE_STREAMS_MAX
+
+
+def test_concurrent_first_forwards_on_fresh_streams():
+    """Four host threads start their first forward on a stream of their own at the same moment: the side streams of all four are
+    chosen by probes (einx_side_stream, einx_fork_stream_prepare_beside) that no longer run under one process-wide lock.  Every
+    thread finishes (no deadlock), gets side streams other than its caller, and the results equal a single-thread run bit for bit."""
+    import ctypes
+    import threading
+    L = pkg.native.lib()
+    EIM = import_module(pkg.__name__ + ".core.modules.EIM").EIM
+    n = 4
+    models = [_eim_model("SP_MNN", 55)[1] for _ in range(n)]
+    ev, mask = synth.synth_events(66, 1, 5)
+    img = synth.synth_image(66, 1)
+    ref = models[0](_t(ev), _t(img.copy()), _t(mask))
+    for m in models[1:]:  # (the models' own first forward, on the default stream)
+        m(_t(ev), _t(img.copy()), _t(mask))
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(DEV) for _ in range(n)]
+    for s in streams:  # fresh for the library and for the package, whatever earlier tests ran on these handles
+        assert L.einx_fork_stream_release(ctypes.c_void_p(s.cuda_stream)) == 0
+        EIM._side_streams.pop(("cuda", torch.cuda.current_device(), s.cuda_stream), None)
+    inputs = [(_t(ev), _t(img.copy()), _t(mask)) for _ in range(n)]
+    torch.cuda.synchronize()
+    start = threading.Barrier(n)
+    got, errors = [None] * n, []
+
+    def run(i):
+        try:
+            s = streams[i]
+            start.wait(timeout=60)
+            with torch.cuda.stream(s):
+                out = models[i](*inputs[i])
+            s.synchronize()
+            side = EIM._side_streams[("cuda", torch.cuda.current_device(), s.cuda_stream)].cuda_stream
+            got[i] = (out, side, L.einx_fork_stream_of(ctypes.c_void_p(s.cuda_stream)))
+        except BaseException as exc:  # noqa: BLE001 (re-raised on the main thread)
+            errors.append(exc)
+
+    threads = [threading.Thread(target=run, args=(i,), daemon=True) for i in range(n)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=180)
+    assert not any(t.is_alive() for t in threads), "a first forward did not finish (deadlock?)"
+    assert not errors, errors
+    for i, (out, side, fork) in enumerate(got):
+        caller = streams[i].cuda_stream
+        assert side and side != caller and fork and fork != caller, (i, caller, side, fork)
+        for k in (0, 1):
+            assert torch.equal(out[k]["sparse_positions"][0], ref[k]["sparse_positions"][0]), i
+            assert torch.equal(out[k]["sparse_descriptors"][0], ref[k]["sparse_descriptors"][0]), i
+        assert torch.equal(out[2]["matches0"][0], ref[2]["matches0"][0]), i
+        assert torch.equal(out[2]["matching_scores0"][0], ref[2]["matching_scores0"][0]), i
+    assert L.einx_fork_stream_count() <= 16  # EINX_FORK_STREAMS_MAX (include/einx.h), one device
 
 
 def test_silk_family_runs_on_one_stream_beyond_a_single_image():
