@@ -114,6 +114,20 @@ def la_bound(tag):
     return max(1e-4, factor * max(n["la_perm"], n["la_threads"]) + LA_ULPS * float(np.spacing(np.float32(n["la_absmax"]))))
 
 
+LA_F64_FACTOR = 2.0
+
+
+def la_bound_f64(peer_errors, absmax, tag=None):
+    """Bound against the EXACT (float64, tests/lg_f64.py) answer on the SAME inputs = LA_F64_FACTOR x the largest error of the
+    independent fp32 implementations measured there -- `peer_errors`: max |x - x_f64| of lg_f64's float32 run and of the oracle
+    where it ran -- + LA_ULPS units in the last place of `absmax` (the largest |x| compared).  A correct fp32 kernel rounds about as
+    much as its peers; one that sits twice as far from the exact value as the worse of them has more than rounding in it.  With a
+    fixture `tag` it is never looser than la_bound(tag).  The same rule bounds the descriptors after each layer (each layer
+    against its own peers)."""
+    b = LA_F64_FACTOR * max(float(e) for e in peer_errors) + LA_ULPS * float(np.spacing(np.float32(absmax)))
+    return min(b, la_bound(tag)) if tag is not None else b
+
+
 def la_bound_e2e(tag, upstream=None):
     """End-to-end comparisons against the reference: its extractors' floats differ from ours upstream (conv accumulation
     order), and log_assignment is ill-conditioned in its inputs -- the REFERENCE moves by `la_cond` (0.7e-3 .. 2.8e-3) when its
@@ -425,3 +439,21 @@ def row_checksums(raw):
 
 def recorded_flips():
     return _FLIPS
+
+
+# ---- LightGlue against its float64 forward (tests/lg_f64.py; test_lightglue_f64_cpu.py / _gpu.py) ----------------------------
+# single pairs of the shipped model (d 256, 4 x 64, 9 layers): partial / whole 32-key blocks, count 1, both latency kernels
+# (lg_attn16_kernel, lg_gemm_small_kernel), stacked (n == m) and unstacked sides
+LGF64_PAIRS = [(1, 1), (1, 300), (2, 3), (31, 33), (32, 32), (33, 31), (64, 64), (65, 127), (128, 128), (129, 300), (513, 511),
+               (1023, 1024), (1024, 1024)]
+
+
+def lgf64_shipped_state_dict(seed):
+    """name-synthesised weights of the shipped LightGlue (the lg.npz fixture's parameter tree: input 256, d 256, 4 heads, 9 layers)"""
+    G = Golden("lg")
+    return state_dict_for({"state_keys": json.loads(bytes(G["d256.state_keys"]).decode()), "wseed": seed})
+
+
+def lgf64_pair(seed, n, m, din=256):
+    """one pair as helpers.lg_inputs makes it: half of the smaller side shared (mixed) across the two sides"""
+    return lg_inputs(dict(seed=seed, n=n, m=m, input_dim=din, shared=min(n, m) // 2))

@@ -14,6 +14,7 @@ from importlib import import_module
 
 from helpers import (check_matches_vs_reference, close_and_record, la_bound, la_bound_e2e, lg_noise, record_flips, record_only,
                      split, state_dict_for, sub_dict, synth, twin_inputs, twin_state_dict_for, upstream_deviation)
+from test_lightglue_f64_gpu import SHIPPED, _check_pair
 from gpu_support import (CONV, DEV, E2E, FTOL, LGCAL, MNN, PAD0, _Z, _assert_feats_equal_oracle, _bench_like_model, _build,
                          _calibrate, _calibrate_lightglue, _inputs, _np, _oracle_feats, _oracle_pair, _t, pkg)
 
@@ -264,6 +265,21 @@ def test_small_helper_functions(oracle):
     assert tuple(dd.get_dense_descriptors(nd).shape) == (2, 20, 16)
 
 
+def _every_pair_equals_its_own_forward(model, ev_t, img_t, mask_t, ef, imf, m):
+    """pair b of the batched forward, for EVERY b, is bit-identical to the forward of pair b alone (keypoints, descriptors,
+    matches, matched keypoints, matching scores, log_assignment): the XCD remap, the persistent tile walk and the stacked 2B layout
+    may not depend on a pair's place in the batch"""
+    for b in range(ev_t.shape[0]):
+        ef1, imf1, m1 = model(ev_t[b:b + 1], img_t[b:b + 1].clone(), mask_t[b:b + 1])
+        for got, one in ((ef, ef1), (imf, imf1)):
+            assert torch.equal(got["sparse_positions"][b], one["sparse_positions"][0]), f"pair {b}: keypoints"
+            assert torch.equal(got["sparse_descriptors"][b], one["sparse_descriptors"][0]), f"pair {b}: descriptors"
+        for k in ("matches0", "matches1", "matched_kpts0", "matched_kpts1", "matching_scores0", "matching_scores1", "log_assignment"):
+            a, o = m[k][b], m1[k][0]
+            assert (a is None) == (o is None), f"pair {b}: {k}"
+            assert a is None or torch.equal(a, o), f"pair {b}: {k}"
+
+
 @pytest.mark.parametrize("cfg_name,B", [("SP_MNN", 32), ("SiLK_MNN", 32)])
 def test_baseline_batch_sampled_pairs_vs_oracle_mnn(oracle, cfg_name, B):
     """configs[1] / configs[2] at their real batch size: pairs 0, B/2, B-1 bit-equal to per-pair oracle runs
@@ -287,6 +303,7 @@ def test_baseline_batch_sampled_pairs_vs_oracle_mnn(oracle, cfg_name, B):
         assert np.array_equal(_np(m["matched_kpts0"][b]), mk0) and np.array_equal(_np(m["matched_kpts1"][b]), mk1)
         nmatch.append(int((r["matches0"] > -1).sum()))
     assert min(nmatch) >= 5, f"calibrated descriptors should give real matches, got {nmatch}"
+    _every_pair_equals_its_own_forward(model, ev_t, img_t, mask_t, ef, imf, m)
 
 
 @pytest.mark.parametrize("cfg_name", ["SP_MNN", "SP_LG"])
@@ -361,6 +378,7 @@ def test_shipped_16_bin_config_at_bench_batch_vs_per_pair_oracle(oracle):
         r = oracle.mnn(oe["sparse_descriptors"][0], oi["sparse_descriptors"][0], want_la=False)
         assert np.array_equal(_np(m["matches0"][b])[0], r["matches0"]), f"pair {b}: matches0"
         assert np.array_equal(_np(m["matches1"][b])[0], r["matches1"]), f"pair {b}: matches1"
+    _every_pair_equals_its_own_forward(model, ev_t, img_t, mask_t, ef, imf, m)
 
 
 @pytest.mark.parametrize("cfg_name,bins", [("SP_MNN", 5), ("SP_LG", 16), ("SiLK_MNN", 5)])
@@ -440,6 +458,13 @@ def test_baseline_batch_sampled_pairs_vs_oracle_lightglue(oracle):
         es = np.asarray(r["matching_scores0"]).reshape(-1)
         assert es.max() > 0.9 and ((es > 0.1) & (es < 0.9)).sum() >= 100
         close_and_record("B64 sp_lg (same scene) matching_scores0 vs oracle", _np(m["matching_scores0"][b])[0], es, atol=1e-4)
+        # the float64 forward on the GPU's own features (equal to the oracle's): GPU vs exact and oracle vs exact side by side
+        pair = (oe["sparse_positions"][0], oe["sparse_descriptors"][0], oi["sparse_positions"][0], oi["sparse_descriptors"][0],
+                (260, 346), (260, 346))
+        got = {"la": gla, "layers": None, "m0": g0, "m1": _np(m["matches1"][b])[0], "s0": _np(m["matching_scores0"][b])[0],
+               "s1": _np(m["matching_scores1"][b])[0]}
+        _check_pair("lgf64.b64_sp_lg", sub_dict(sd, "matcher.matcher."), SHIPPED, pair, got, orc=r, fixture="sp_lg_twin.0")
+    _every_pair_equals_its_own_forward(model, ev_t, img_t, mask_t, ef, imf, m)
 
 
 @pytest.mark.parametrize("name", list(PAD0))
