@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import MetricParams, check
+from ..._lib import MetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -82,3 +82,56 @@ def single_pair(points1, points2, desc1, desc2, matched1, matched2, size0, size1
     out = pair_metrics(k0, d0, cnt(points1.shape[0]), k1, d1, cnt(points2.shape[0]), mk0, mk1, cnt(M), size0, size1, hom, mma_thr, vdd_thr,
                        ordering, rep_nan_if_empty=rep_nan_if_empty)
     return dict(zip(metric_names(mma_thr, vdd_thr), out[0].tolist()))
+
+
+POSE_SEED = 0x5EED0F5E
+POSE_STATUS = {-1: "few", -2: "noE", -3: "cheir"}  # einx.h: >= 0 pose found, negative: why not
+
+
+@on_input_device
+def relative_pose(mk0, mk1, nmatch, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx", max_iters=1000, seed=POSE_SEED):
+    """RANSAC essential matrix + recoverPose + update_one's errors for a batch (csrc/pose.hip), no host sync.
+    mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the device, K0 / K1 [B,3,3] float32 or float64 (numpy's dtype rules
+    follow K's), T_0to1 [B,4,4] or None.  Returns device tensors (R [B,3,3] f64, t [B,3] f64, mask [B,cap] bool,
+    status [B] int32, rows [B,4] f64 = R_err, t_err, pose_err, inlier ratio)."""
+    B, cap, cols = mk0.shape
+    dev = mk0.device
+    k_f64 = K0.dtype == torch.float64 or K1.dtype == torch.float64
+    kdt = torch.float64 if k_f64 else torch.float32
+    K0 = K0.to(dev, kdt).reshape(B, 9).contiguous()
+    K1 = K1.to(dev, kdt).reshape(B, 9).contiguous()
+    T = None if T_0to1 is None else T_0to1.to(dev, torch.float64).reshape(B, 16).contiguous()
+    p = PoseParams()
+    p.struct_size = ctypes.sizeof(PoseParams)
+    p.B, p.cap, p.cols, p.kp_yx, p.k_f64, p.max_iters = B, cap, cols, int(ordering == "yx"), int(k_f64), int(max_iters)
+    p.thresh, p.conf, p.seed = float(thresh), float(conf), int(seed)
+    L = N.lib()
+    N._dev_check(mk0, mk1)
+    N._dev_check(nmatch, dt=torch.int32)
+    ws = torch.empty(L.einx_relative_pose_ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    R = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
+    t = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    rows = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    check(L.einx_relative_pose(ctypes.byref(p), N._ptr(mk0), N._ptr(mk1), N._ptr(nmatch), N._ptr(K0), N._ptr(K1), N._ptr(T), N._ptr(ws),
+                               N._ptr(R), N._ptr(t), N._ptr(mask), N._ptr(status), N._ptr(rows), N._stream(mk0)), "einx_relative_pose")
+    return R, t, mask.bool(), status, rows
+
+
+@on_input_device
+def batch_relative_pose(mr, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx"):
+    """relative_pose of an EIM match result (MatchResult: mk0 / mk1 / nmatch), no host sync"""
+    return relative_pose(mr.mk0, mr.mk1, mr.nmatch, K0, K1, T_0to1, thresh, conf, ordering)
+
+
+@on_input_device
+def essential_5pt(x1, x2):
+    """the minimal solver alone (test aid): x1 / x2 [n,5,2] float64 -> (E [n,10,3,3], n_solutions [n] int32)"""
+    n = x1.shape[0]
+    x1 = x1.to(torch.float64).contiguous()
+    x2 = x2.to(torch.float64).contiguous()
+    E = torch.zeros((n, 10, 3, 3), dtype=torch.float64, device=x1.device)
+    ns = torch.empty((n,), dtype=torch.int32, device=x1.device)
+    check(N.lib().einx_essential_5pt(N._ptr(x1), N._ptr(x2), n, N._ptr(E), N._ptr(ns), N._stream(x1)), "einx_essential_5pt")
+    return E, ns

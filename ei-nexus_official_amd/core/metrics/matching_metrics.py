@@ -1,9 +1,12 @@
 """MatchingRatio / MeanMatchingAccuracy with the reference's class names and `update_one` signatures
-(core/metrics/matching_metrics.py:30-51, :84-156), computed by csrc/metrics.hip.  HomographyEstimation
-and RelativePoseEstimation stay on the CPU in the reference (cv2 RANSAC) and are out of scope."""
+(core/metrics/matching_metrics.py:30-51, :84-156), computed by csrc/metrics.hip.  RelativePoseEstimation
+(:347-559) runs its RANSAC essential matrix and recoverPose on the device (csrc/pose.hip, DESIGN.md 8b: the
+written algorithm, not bit parity with cv2).  HomographyEstimation (cv2.findHomography on the host in the
+reference) is out of scope."""
+import numpy as np
 import torch
 
-from ._native_metrics import single_pair
+from ._native_metrics import POSE_STATUS, single_pair, relative_pose
 
 
 class MatchingRatio:
@@ -53,9 +56,9 @@ def compute_auc(errors, thresholds):
 
 
 class _NeedsOpenCV:
-    """HomographyEstimation / RelativePoseEstimation (matching_metrics.py:188-345, :347-470) are cv2 RANSAC
-    estimators on the host: downstream of the hot path and out of this build's scope.  The names
-    exist so that the evaluation scripts' import lines resolve; constructing one says what is missing."""
+    """HomographyEstimation (matching_metrics.py:188-345) is a cv2 RANSAC estimator on the host: downstream of the hot
+    path and out of this build's scope.  The name exists so that the evaluation scripts' import lines
+    resolve; constructing one says what is missing."""
 
     def __init__(self, *a, **k):
         raise NotImplementedError(f"{type(self).__name__} needs OpenCV's RANSAC estimators (cv2.findHomography / cv2.findEssentialMat); "
@@ -66,5 +69,110 @@ class HomographyEstimation(_NeedsOpenCV):
     pass
 
 
-class RelativePoseEstimation(_NeedsOpenCV):
-    pass
+class RelativePoseEstimation:
+    """matching_metrics.py:347-559 with the reference's constructor, attributes and methods; estimate_pose runs csrc/pose.hip
+    for the one pair (RANSAC essential matrix, recoverPose's cheirality vote) and hands back numpy like cv2 does."""
+
+    def __init__(self, name, pose_thresh, ransac_thresh=1.0, ransac_conf=0.999, ordering="yx") -> None:
+        self.metric_name = name
+        self.to_device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+        self.pose_thresh = pose_thresh
+        self.ransac_thresh = ransac_thresh
+        self.ransac_conf = ransac_conf
+        self.ordering = ordering
+        self.error_list = []
+        assert ordering in {"xy", "yx"}
+
+    def _device_pose(self, matched_keypoints1, matched_keypoints2, K0, K1, T_0to1, thresh, conf, ordering):
+        dev = matched_keypoints1.device if matched_keypoints1.is_cuda else self.to_device
+        n = len(matched_keypoints1)
+        cols = matched_keypoints1.shape[1]
+        cap = max(n, 1)
+        mk0 = torch.zeros((1, cap, cols), dtype=torch.float32, device=dev)
+        mk1 = torch.zeros((1, cap, cols), dtype=torch.float32, device=dev)
+        mk0[0, :n] = matched_keypoints1.to(dev, torch.float32)
+        mk1[0, :n] = matched_keypoints2.to(dev, torch.float32)
+        nm = torch.tensor([n], dtype=torch.int32, device=dev)
+        k = lambda v: torch.as_tensor(v).to(dev)[None]  # noqa: E731
+        T = None if T_0to1 is None else k(T_0to1)
+        return relative_pose(mk0, mk1, nm, k(K0), k(K1), T, thresh, conf, ordering)
+
+    def estimate_pose(self, matched_keypoints1, matched_keypoints2, K0, K1, thresh, conf, ordering="yx"):
+        """(R [3,3], t [3], inlier mask [N] bool) as numpy, or None (printing the reference's messages)"""
+        assert len(matched_keypoints1) == len(matched_keypoints2)
+        assert matched_keypoints1.shape[1] in (2, 3)
+        if len(matched_keypoints1) < 5:
+            print("Not enough points to estimate pose")
+            return None
+        R, t, mask, status, _ = self._device_pose(matched_keypoints1, matched_keypoints2, K0, K1, None, thresh, conf, ordering)
+        st = int(status[0])
+        if POSE_STATUS.get(st) == "noE":
+            print("\nE is None while trying to recover pose.\n")
+        if st < 0:
+            return None
+        n = len(matched_keypoints1)
+        return R[0].cpu().numpy(), t[0].cpu().numpy(), mask[0, :n].cpu().numpy()
+
+    def relative_pose_error(self, T_0to1, R, t, ignore_gt_t_thr=0.0):
+        T_0to1 = T_0to1.detach().cpu().numpy() if torch.is_tensor(T_0to1) else np.asarray(T_0to1)
+        t_gt = T_0to1[:3, 3]
+        n = np.linalg.norm(t) * np.linalg.norm(t_gt)
+        t_err = np.rad2deg(np.arccos(np.clip(np.dot(t, t_gt) / n, -1.0, 1.0)))
+        t_err = np.minimum(t_err, 180 - t_err)  # handle E ambiguity
+        if not np.isfinite(np.linalg.norm(t_gt)):  # pure rotation is challenging
+            t_err = 0.0
+        R_gt = T_0to1[:3, :3]
+        cos = (np.trace(np.dot(R.T, R_gt)) - 1) / 2
+        cos = np.clip(cos, -1.0, 1.0)  # handle numercial errors
+        R_err = np.rad2deg(np.abs(np.arccos(cos)))
+        return t_err, R_err
+
+    def compute_all_auc(self):
+        return compute_auc(self.error_list, self.pose_thresh)
+
+    def _fail(self, out_dict):
+        out_dict[self.metric_name + "_R_errs"] = np.inf
+        out_dict[self.metric_name + "_t_errs"] = np.inf
+        out_dict[self.metric_name + "_pose_errs"] = np.inf
+        out_dict[self.metric_name + "_inliers"] = 0.0
+        for i in range(len(self.pose_thresh)):
+            out_dict[f"{self.metric_name}@{self.pose_thresh[i]}_ratio"] = 0.0
+        self.error_list.append(np.inf)
+        return out_dict
+
+    @torch.no_grad()
+    def update_one(self, matched_keypoints1, matched_keypoints2, K0, K1, T_0to1):
+        out_dict = {}
+        ret = self.estimate_pose(matched_keypoints1, matched_keypoints2, K0, K1, thresh=self.ransac_thresh, conf=self.ransac_conf,
+                                 ordering=self.ordering)
+        if ret is None:
+            return self._fail(out_dict)
+        R, t, inliers = ret
+        t_err, R_err = self.relative_pose_error(T_0to1, R, t, ignore_gt_t_thr=0.0)
+        pose_err = np.max([R_err, t_err]) if np.isfinite(t_err) else R_err
+        out_dict[self.metric_name + "_R_errs"] = R_err
+        out_dict[self.metric_name + "_t_errs"] = t_err
+        out_dict[self.metric_name + "_pose_errs"] = pose_err
+        out_dict[self.metric_name + "_inliers"] = inliers.mean().item()
+        for i in range(len(self.pose_thresh)):
+            out_dict[f"{self.metric_name}@{self.pose_thresh[i]}_ratio"] = (pose_err <= self.pose_thresh[i]).astype(np.float32)
+        self.error_list.append(pose_err)
+        return out_dict
+
+    @torch.no_grad()
+    def update_batch(self, matched_keypoints1, matched_keypoints2, K0, K1, T_0to1):
+        out_dict = {}
+        self.error_list = []
+        assert len(matched_keypoints1) == len(matched_keypoints2) == len(K0) == len(K1) == len(T_0to1)
+        for i in range(len(matched_keypoints1)):
+            one_out_dict = self.update_one(matched_keypoints1[i], matched_keypoints2[i], K0[i], K1[i], T_0to1[i])
+            for k, v in one_out_dict.items():
+                out_dict.setdefault(k, []).append(v)
+        auc = self.compute_all_auc()
+        for k in out_dict.keys():
+            v = np.array(out_dict[k])
+            v = v[np.isfinite(v)]
+            out_dict[k] = np.mean(v)
+        for k in self.pose_thresh:
+            out_dict[f"{self.metric_name}@{k}_auc"] = auc[f"{k}"]
+        return out_dict

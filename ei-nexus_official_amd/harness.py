@@ -5,12 +5,15 @@
                --(EIM: conv/detect/desc/mnn|lightglue kernels)--> keypoints, descriptors, matches
                --(metrics.hip)--> MR, MMA@1/3, VDD@1/3 per pair  --> means (all-reduced across ranks)
 
-HomographyEstimation / RelativePoseEstimation (cv2 RANSAC on the CPU in the reference) are out of scope;
-DifferentTimeEvaluator hands over exactly what the reference passes to them.
+               --(pose.hip, DifferentTimeEvaluator with poses)--> RANSAC relative pose, R / t / pose errors per pair
+                  --> RPE means and AUC@t (per-pair errors all-gathered across ranks)
+
+HomographyEstimation (cv2 RANSAC on the CPU in the reference) is out of scope.
 """
+import numpy as np
 import torch
 
-from .core.metrics._native_metrics import batch_metrics, metric_names
+from .core.metrics._native_metrics import batch_metrics, batch_relative_pose, metric_names
 from .datasets.representations import EventStage, events_representation_batch
 
 
@@ -47,7 +50,7 @@ class SameTimeEvaluator:
             ef, imf, matches = self.model._finish(self.model._enqueue(events_rep, images, events_mask, image_feats=im))
         return self._account(ef, imf, matches, homography)
 
-    def _account(self, ef, imf, matches, homography):
+    def _account(self, ef, imf, matches, homography, pose=None):
         rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, homography, self.mma_thr, self.vdd_thr)
         # the running sums are folded lazily (`_fold`): eight small reductions per batch on the forward's stream were a third of
         # what the evaluation loop cost on top of the forward (profiles/r06_notes.md 3)
@@ -80,7 +83,7 @@ class SameTimeEvaluator:
     @torch.no_grad()
     def run(self, batches, depth=2):
         """The evaluation LOOP (test_events-image_same-time.py:130-194 iterates a DataLoader): `batches` yields
-        (events_list, images[, homography]) like the arguments of `step`; one `step` result per batch comes back, in order.
+        (events_list, images[, homography[, pose]]) like the arguments of `step`; one `step` result per batch comes back, in order.
         Up to `depth` batches are in flight: batch i + 1's events are concatenated into page-locked memory, uploaded with
         non-blocking copies and its kernels enqueued (EIM.forward_stream's mechanism) BEFORE the host waits for batch i's
         counts, so packing and the PCIe transfer hide under the device's work instead of adding to it.  Same kernels, same
@@ -94,12 +97,13 @@ class SameTimeEvaluator:
         k = 0
 
         def finish(entry):
-            p, hom = entry
-            return self._account(*self.model._finish(p), hom)
+            p, hom, pose = entry
+            return self._account(*self.model._finish(p), hom, pose)
 
         for item in batches:
             events_list, images = item[0], item[1]
             homography = item[2] if len(item) > 2 else None
+            pose = item[3] if len(item) > 3 else None
             slot = k % depth
             dev = images.device
             with torch.cuda.device(dev):
@@ -112,7 +116,7 @@ class SameTimeEvaluator:
                 # same: 8.89 vs 8.84 ms per batch, profiles/r06_notes.md.)
                 rep, mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage, on_stage_stream=True)
                 self.last_inputs = (rep, mask)  # of the batch enqueued last (results lag by up to depth - 1 batches)
-                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography))
+                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose))
             k += 1
             if len(pending) >= depth:
                 yield finish(pending.popleft())
@@ -129,6 +133,44 @@ class SameTimeEvaluator:
         return dict(zip(self.names, mean))
 
 
+def gather_pose_rows(rows):
+    """[P,4] per-pair pose rows of this rank -> the rows of every rank (concatenated in rank order).  An AUC cannot be
+    all-reduced from sums: the rows are all-gathered, padded to the largest count (on the CPU under gloo)."""
+    if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+        return rows
+    world = torch.distributed.get_world_size()
+    dev = rows.device if torch.distributed.get_backend() == "nccl" else torch.device("cpu")
+    rows = rows.to(dev, torch.float64)
+    n = torch.tensor([rows.shape[0]], dtype=torch.int64, device=dev)
+    counts = [torch.zeros_like(n) for _ in range(world)]
+    torch.distributed.all_gather(counts, n)
+    counts = [int(c) for c in counts]
+    pad = torch.full((max(counts), rows.shape[1]), float("nan"), dtype=torch.float64, device=dev)
+    pad[:rows.shape[0]] = rows
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    torch.distributed.all_gather(parts, pad)
+    return torch.cat([p[:c] for p, c in zip(parts, counts)], 0)
+
+
+def rpe_summary(rows, pose_thresh=(5, 10, 20), name="RPE"):
+    """rpe_dict of test_events-image_different_time.py:326-334 from per-pair rows (R_err, t_err, pose_err, inlier ratio; inf
+    errors for a pair without a pose): the mean of each key over its finite values, AUC@t over the finite pose errors"""
+    from .core.metrics.matching_metrics import compute_auc
+    r = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64).reshape(-1, 4)
+    ok = np.isfinite(r[:, 0])
+    cols = {f"{name}_R_errs": r[:, 0], f"{name}_t_errs": r[:, 1], f"{name}_pose_errs": r[:, 2], f"{name}_inliers": r[:, 3]}
+    for t in pose_thresh:
+        cols[f"{name}@{t}_ratio"] = np.where(ok, (r[:, 2] <= t).astype(np.float32), 0.0)
+    out = {}
+    for k, v in cols.items():
+        v = v[np.isfinite(v)]
+        out[k] = np.mean(v)
+    auc = compute_auc(list(r[:, 2]), pose_thresh)
+    for t in pose_thresh:
+        out[f"{name}@{t}_auc"] = auc[f"{t}"]
+    return out
+
+
 class DifferentTimeEvaluator(SameTimeEvaluator):
     """Call pattern of test_events-image_different_time.py:187-264: the events come from frame i, the image from a LATER
     frame j of the sequence, and the two views are related by a known motion instead of the identity.
@@ -136,11 +178,53 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
     * `step(events_list, images, homography)`: as SameTimeEvaluator.step, with the image-0 -> image-1 homography [B,3,3]
       of the pair (planar scenes / pure rotations; None = identity) going into MMA@t and VDD@t (metrics.hip warps the
       keypoints exactly like core/metrics/util.py:warp_points).
+    * `step(events_list, images, homography, pose=(K0, K1, T_0to1))`: with the intrinsics [B,3,3] and the ground-truth motion
+      [B,4,4] of the pair on the device, the RANSAC relative pose of every pair runs on the device as well (csrc/pose.hip, what
+      RelativePoseEstimation.update_one computes, :251-257), with no host synchronisation; the returned rows are unchanged.
+      `run()` items may carry the same tuple as a 4th element.
+    * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
+      RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
+      all-gathered before the AUC.
     * `pose_inputs(matches, b)`: what the reference feeds RelativePoseEstimation.update_one for pair b
       (`matches["matched_kpts0"][b]`, `matches["matched_kpts1"][b]`, :251-257), plus the (x, y) views of
-      test_events-image_different_time.py:217-224 (`[..., :2]`, flipped when the extractor's ordering is "yx").  The pose
-      solver itself (cv2.findEssentialMat / recoverPose on the CPU) is outside this build.
+      test_events-image_different_time.py:217-224 (`[..., :2]`, flipped when the extractor's ordering is "yx").
     """
+
+    def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
+                 ransac_conf=0.999):
+        super().__init__(model, bins, resolution, mma_thr, vdd_thr)
+        self.pose_thresh = tuple(pose_thresh)
+        self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
+        self._pose_rows = []
+
+    @torch.no_grad()
+    def step(self, events_list, images, homography=None, pose=None):
+        self._pose_next = pose
+        try:
+            return super().step(events_list, images, homography)
+        finally:
+            self._pose_next = None
+
+    def _account(self, ef, imf, matches, homography, pose=None):
+        if pose is None:
+            pose = getattr(self, "_pose_next", None)
+        out = super()._account(ef, imf, matches, homography)
+        if pose is not None:
+            K0, K1, T = pose
+            _, _, _, _, prow = batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
+                                                   ordering=ef._batched.ordering)
+            self._pose_rows.append(prow)
+        return out
+
+    def result(self):
+        out = super().result()
+        rows = torch.cat(self._pose_rows, 0) if self._pose_rows else torch.empty((0, 4), dtype=torch.float64)
+        # every rank takes part in the gather, with zero rows if it was given no poses: a rank that skipped the collective
+        # would leave the others waiting in it
+        rows = gather_pose_rows(rows)
+        if rows.shape[0]:
+            out.update(rpe_summary(rows, self.pose_thresh))
+        return out
 
     def pose_inputs(self, matches, b=0):
         mk0, mk1 = matches["matched_kpts0"][b], matches["matched_kpts1"][b]

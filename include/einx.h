@@ -509,6 +509,37 @@ int einx_pair_metrics(const einx_metric_params* p, const float* kpts0, const flo
                       const int32_t* n, const int32_t* m, const float* mk0, const float* mk1, const int32_t* nmatch,
                       const float* homography, void* ws, double* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Relative pose of the different-time evaluation (csrc/pose.hip)
+ *   RelativePoseEstimation   core/metrics/matching_metrics.py:347-559 (cv2.findEssentialMat RANSAC + cv2.recoverPose)
+ * B pairs of matched keypoints mk0 / mk1 [B,cap,cols] float32 + nmatch int32 [B] (einx_gather_matches' layout), K0 / K1
+ * [B,3,3] (float32 or float64, k_f64), T_0to1 [B,4,4] float64 or NULL.  The written algorithm of DESIGN.md 8b, not bit parity
+ * with OpenCV (its random draws and root order are not reproduced).  Outputs:
+ *   R_out [B,9] / t_out [B,3] float64 (zeros without a pose), mask_out [B,cap] uint8 (the recoverPose mask),
+ *   status [B] int32: >= 0 pose found, = 16 * RANSAC iteration + solution index of the chosen model (the solution index
+ *     alone for exactly 5 matches); -1 fewer than 5 matches, -2 no essential matrix, -3 no point passes the cheirality test,
+ *   rows_out [B,4] float64 or NULL: R_err, t_err, pose_err (degrees), inlier ratio -- update_one's values (inf, inf, inf, 0
+ *     without a pose; NaN errors when T_0to1 is NULL).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_pose_params {
+  size_t struct_size; /* sizeof(einx_pose_params) (checked) */
+  int32_t B, cap, cols;
+  int32_t kp_yx;      /* 1: keypoints are (y,x,..) */
+  int32_t k_f64;      /* 0: K0 / K1 float32, 1: float64 (numpy's dtype of the normalisation and the threshold) */
+  int32_t max_iters;  /* RANSAC iterations (1000: findEssentialMat's maxIters) */
+  double thresh;      /* pixels; divided by mean(K0[0,0], K1[1,1], K0[0,0], K1[1,1]) */
+  double conf;        /* RANSAC confidence (0.999) */
+  uint64_t seed;      /* counter-based generator key */
+} einx_pose_params;
+size_t einx_relative_pose_ws_bytes(const einx_pose_params* p);
+int einx_relative_pose(const einx_pose_params* p, const float* mk0, const float* mk1, const int32_t* nmatch, const void* K0, const void* K1,
+                       const double* T_0to1, void* ws, double* R_out, double* t_out, uint8_t* mask_out, int32_t* status, double* rows_out,
+                       void* stream);
+/* The minimal solver alone (test aid, like einx_math_eval): x1 / x2 [n,5,2] float64 normalised points; E_out [n,10,9] float64 gets
+ * every real essential matrix of each problem ordered by ascending E[2,1] / E[2,2] (scaled to E[2,2] = 1), n_solutions [n] int32
+ * their count (0 for a singular sample). */
+int einx_essential_5pt(const double* x1, const double* x2, int n_problems, double* E_out, int32_t* n_solutions, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
