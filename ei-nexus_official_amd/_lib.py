@@ -57,6 +57,11 @@ class PoseParams(ctypes.Structure):
                [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
+class HomographyParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap", "cols", "kp_yx", "max_iters", "n_thr")] + \
+               [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("he_thr", c_float * 4), ("seed", ctypes.c_uint64)]
+
+
 class EventArrays(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("y", c_void_p), ("t", c_void_p), ("p", c_void_p), ("x_type", ctypes.c_int32), ("y_type", ctypes.c_int32),
                 ("t_type", ctypes.c_int32), ("p_type", ctypes.c_int32), ("n", ctypes.c_int64)]
@@ -143,6 +148,9 @@ SIGNATURES = {
     "einx_relative_pose_ws_bytes": (c_size_t, [ctypes.POINTER(PoseParams)]),
     "einx_relative_pose": (c_int, [ctypes.POINTER(PoseParams)] + [c_void_p] * 13),
     "einx_essential_5pt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_homography_ws_bytes": (c_size_t, [ctypes.POINTER(HomographyParams)]),
+    "einx_homography": (c_int, [ctypes.POINTER(HomographyParams)] + [c_void_p] * 11),
+    "einx_homography_dlt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "einx_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "einx_lg_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "einx_lg_ws_bytes_heads": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

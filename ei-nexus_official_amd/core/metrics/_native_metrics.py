@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import MetricParams, PoseParams, check
+from ..._lib import HomographyParams, MetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -135,3 +135,59 @@ def essential_5pt(x1, x2):
     ns = torch.empty((n,), dtype=torch.int32, device=x1.device)
     check(N.lib().einx_essential_5pt(N._ptr(x1), N._ptr(x2), n, N._ptr(E), N._ptr(ns), N._stream(x1)), "einx_essential_5pt")
     return E, ns
+
+
+HOMOGRAPHY_STATUS = {-1: "few", -2: "noH"}  # einx.h: >= 0 the chosen RANSAC iteration, negative: why there is no homography
+
+
+@on_input_device
+def homography(mk0, mk1, nmatch, img_shape=None, H_true=None, thresh=3.0, conf=0.995, ordering="yx", max_iters=2000, he_thr=(3, 5, 10),
+               seed=POSE_SEED):
+    """RANSAC homography + refit + LM polish + update_one's corner error for a batch (csrc/homography.hip), no host
+    sync.  mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the device; img_shape (H, W) for every pair or [B,2], H_true
+    [B,3,3] (cast to float32 as update_one does), or None for both.  Returns device tensors (H [B,3,3] f64, mask [B,cap] bool,
+    status [B] int32, rows [B,len(he_thr)+2] f64 = (error <= t) per threshold, mean corner error, inlier ratio)."""
+    B, cap, cols = mk0.shape
+    dev = mk0.device
+    he_thr = tuple(he_thr)
+    if len(he_thr) > 4:
+        raise ValueError("at most 4 correctness thresholds")
+    if img_shape is not None:
+        img_shape = torch.as_tensor(img_shape).to(dev, torch.int32)
+        img_shape = (img_shape.reshape(1, 2).expand(B, 2) if img_shape.numel() == 2 else img_shape.reshape(B, 2)).contiguous()
+    Ht = None if H_true is None else H_true.to(dev, torch.float32).reshape(B, 9).contiguous()
+    p = HomographyParams()
+    p.struct_size = ctypes.sizeof(HomographyParams)
+    p.B, p.cap, p.cols, p.kp_yx, p.max_iters, p.n_thr = B, cap, cols, int(ordering == "yx"), int(max_iters), len(he_thr)
+    p.thresh, p.conf, p.seed = float(thresh), float(conf), int(seed)
+    for i, t in enumerate(he_thr):
+        p.he_thr[i] = float(t)
+    L = N.lib()
+    N._dev_check(mk0, mk1)
+    N._dev_check(nmatch, dt=torch.int32)
+    ws = torch.empty(L.einx_homography_ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    H = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
+    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    rows = torch.empty((B, len(he_thr) + 2), dtype=torch.float64, device=dev)
+    check(L.einx_homography(ctypes.byref(p), N._ptr(mk0), N._ptr(mk1), N._ptr(nmatch), N._ptr(img_shape), N._ptr(Ht), N._ptr(ws), N._ptr(H),
+                            N._ptr(mask), N._ptr(status), N._ptr(rows), N._stream(mk0)), "einx_homography")
+    return H, mask.bool(), status, rows
+
+
+@on_input_device
+def batch_homography(mr, img_shape=None, H_true=None, thresh=3.0, conf=0.995, ordering="yx", he_thr=(3, 5, 10)):
+    """homography of an EIM match result (MatchResult: mk0 / mk1 / nmatch), no host sync"""
+    return homography(mr.mk0, mr.mk1, mr.nmatch, img_shape, H_true, thresh, conf, ordering, he_thr=he_thr)
+
+
+@on_input_device
+def homography_dlt(x1, x2):
+    """the normalised DLT alone (test aid): x1 / x2 [n,npts,2] float64 -> (H [n,3,3] float64, ok [n] int32)"""
+    n, npts = x1.shape[0], x1.shape[1]
+    x1 = x1.to(torch.float64).contiguous()
+    x2 = x2.to(torch.float64).contiguous()
+    H = torch.zeros((n, 3, 3), dtype=torch.float64, device=x1.device)
+    ok = torch.empty((n,), dtype=torch.int32, device=x1.device)
+    check(N.lib().einx_homography_dlt(N._ptr(x1), N._ptr(x2), n, npts, N._ptr(H), N._ptr(ok), N._stream(x1)), "einx_homography_dlt")
+    return H, ok

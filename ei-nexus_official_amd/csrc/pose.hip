@@ -13,6 +13,7 @@
 //   pose_select_kernel   one lane per pair: OpenCV's sequential scan with its shrinking iteration bound, resumed per round
 //   pose_recover_kernel  one workgroup per pair: decomposition, cheirality vote, mask, errors
 #include "einx_common.h"
+#include "ransac.h"
 
 namespace {
 
@@ -61,13 +62,6 @@ size_t ws_total(const einx_pose_params* p) {
   const size_t B = p->B, cap = p->cap, it = p->max_iters;
   return al(B * cap * sizeof(double4)) + al(B * 4) + al(B * it * MAXS * 9 * 8) + al(B * it * 4) + al(B * it * MAXS * 4) + al(B * 4) +
          al(B * 12) + al(B * cap) + al(B * cap) + 256;
-}
-
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  unsigned long long z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
 }
 
 // five distinct indices of [0, n) for iteration `it`; false when a draw finds no new index within RETRIES tries
@@ -593,19 +587,6 @@ __global__ __launch_bounds__(256) void pose_score_kernel(const PoseArgs a, int i
   if (tid < ns) a.w.cnt[h * MAXS + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
-// RANSACUpdateNumIters with (1 - ep)^5 as four products
-__device__ int update_iters(double conf, double ep, int bound) {
-  const double p = fmin(fmax(conf, 0.0), 1.0);
-  ep = fmin(fmax(ep, 0.0), 1.0);
-  double num = fmax(1.0 - p, 2.2250738585072014e-308);
-  const double q = 1.0 - ep;
-  double denom = 1.0 - q * q * q * q * q;
-  if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num);
-  denom = log(denom);
-  return denom >= 0 || -num >= bound * (-denom) ? bound : (int)floor(num / denom + 0.5);
-}
-
 // the selection scan over one round [it0, it1), resumed from the state the previous round left
 __global__ void pose_select_kernel(const PoseArgs a, int it0, int it1) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -621,7 +602,7 @@ __global__ void pose_select_kernel(const PoseArgs a, int it0, int it1) {
       if (c > max(best_cnt, 4)) {
         best = it * 16 + s;
         best_cnt = c;
-        bound = update_iters(a.p.conf, (double)(n - c) / (double)n, bound);
+        bound = ransac_update_iters<5>(a.p.conf, (double)(n - c) / (double)n, bound);
       }
     }
   }

@@ -8,18 +8,29 @@
                --(pose.hip, DifferentTimeEvaluator with poses)--> RANSAC relative pose, R / t / pose errors per pair
                   --> RPE means and AUC@t (per-pair errors all-gathered across ranks)
 
-HomographyEstimation (cv2 RANSAC on the CPU in the reference) is out of scope.
+               --(homography.hip, evaluators built with he_thresh, steps given a homography)--> RANSAC homography, refit, LM
+                  polish, mean corner error per pair --> HE means and AUC@t (per-pair rows all-gathered across ranks)
 """
 import numpy as np
 import torch
 
-from .core.metrics._native_metrics import batch_metrics, batch_relative_pose, metric_names
+from .core.metrics._native_metrics import batch_homography, batch_metrics, batch_relative_pose, metric_names
 from .datasets.representations import EventStage, events_representation_batch
 
 
 class SameTimeEvaluator:
-    def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3)):
-        """model: EIM (eval mode); bins: voxel-grid channels; resolution: (W, H) like MVSECDataset.RESOLUTION."""
+    def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), he_thresh=None, he_ransac_thresh=3.0,
+                 he_conf=0.995):
+        """model: EIM (eval mode); bins: voxel-grid channels; resolution: (W, H) like MVSECDataset.RESOLUTION.
+        he_thresh: HomographyEstimation's correctness thresholds (the script's [3, 5, 10]); None (default): no homography
+        estimation, nothing is launched for it and result() has no HE key.  With thresholds, every batch whose `homography` is
+        given also runs the RANSAC homography of its matches on the device (csrc/homography.hip; the script's
+        HE.update_one, test_events-image_same-time.py:189-194) with no host synchronisation, and result() adds HE@t_ratio,
+        HE_errors, HE_inliers and HE@t_auc (:269-277)."""
+        self.he_thresh = None if he_thresh is None else tuple(he_thresh)
+        self.he_ransac_thresh, self.he_conf = float(he_ransac_thresh), float(he_conf)
+        self._he_rows = []
+        self._he_shapes = {}
         self.model = model
         self.bins = int(bins)
         self.resolution = tuple(int(v) for v in resolution)
@@ -58,6 +69,14 @@ class SameTimeEvaluator:
         if len(self._rows) >= 64:
             self._fold()
         self.pairs += rows.shape[0]
+        if self.he_thresh is not None and homography is not None:
+            mr = self.model._last_match
+            key = (tuple(ef._batched.image_size), mr.mk0.shape[0], mr.mk0.device)
+            shape = self._he_shapes.get(key)
+            if shape is None:  # (H, W) of the forward for every pair, uploaded once
+                shape = self._he_shapes[key] = torch.tensor([key[0]] * key[1], dtype=torch.int32, device=key[2])
+            self._he_rows.append(batch_homography(mr, shape, homography, self.he_ransac_thresh, self.he_conf, ordering=ef._batched.ordering,
+                                                  he_thr=self.he_thresh)[3])
         return rows, (ef, imf, matches)
 
     def _fold(self):
@@ -130,12 +149,21 @@ class SameTimeEvaluator:
             torch.distributed.all_reduce(s)
             torch.distributed.all_reduce(c)
         mean = (s / c.clamp_min(1)).tolist()
-        return dict(zip(self.names, mean))
+        out = dict(zip(self.names, mean))
+        if self.he_thresh is not None:
+            width = len(self.he_thresh) + 2
+            rows = torch.cat(self._he_rows, 0) if self._he_rows else torch.empty((0, width), dtype=torch.float64)
+            # every rank of an evaluator built with he_thresh takes part in the gather, with zero rows if it saw no homography
+            rows = gather_rows(rows)
+            if rows.shape[0]:
+                out.update(he_summary(rows, self.he_thresh))
+        return out
 
 
-def gather_pose_rows(rows):
-    """[P,4] per-pair pose rows of this rank -> the rows of every rank (concatenated in rank order).  An AUC cannot be
-    all-reduced from sums: the rows are all-gathered, padded to the largest count (on the CPU under gloo)."""
+def gather_rows(rows):
+    """[P,K] per-pair rows of this rank (pose rows: K = 4, homography rows: K = thresholds + 2; the same K on every rank) -> the
+    rows of every rank (concatenated in rank order).  An AUC cannot be all-reduced from sums: the rows are all-gathered, padded
+    to the largest count (on the CPU under gloo)."""
     if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
         return rows
     world = torch.distributed.get_world_size()
@@ -150,6 +178,29 @@ def gather_pose_rows(rows):
     parts = [torch.empty_like(pad) for _ in range(world)]
     torch.distributed.all_gather(parts, pad)
     return torch.cat([p[:c] for p, c in zip(parts, counts)], 0)
+
+
+gather_pose_rows = gather_rows  # the name it had while the pose rows were its only user
+
+
+def he_summary(rows, he_thresh=(3, 5, 10), name="HE"):
+    """the HE keys of test_events-image_same-time.py:269-277 from per-pair rows ((error <= t) per threshold, mean corner error,
+    inlier ratio; 0.., inf, 0 for a pair without a homography): the mean of each key over its finite values, as the script forms
+    every key of its result_dict, and AUC@t over the finite errors"""
+    from .core.metrics.matching_metrics import compute_auc
+    nt = len(he_thresh)
+    r = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64).reshape(-1, nt + 2)
+    cols = {f"{name}@{t}_ratio": r[:, i] for i, t in enumerate(he_thresh)}
+    cols[f"{name}_errors"] = r[:, nt]
+    cols[f"{name}_inliers"] = r[:, nt + 1]
+    out = {}
+    for k, v in cols.items():
+        v = v[np.isfinite(v)]
+        out[k] = np.mean(v)
+    auc = compute_auc(list(r[:, nt]), he_thresh)
+    for t in he_thresh:
+        out[f"{name}@{t}_auc"] = auc[f"{t}"]
+    return out
 
 
 def rpe_summary(rows, pose_thresh=(5, 10, 20), name="RPE"):
@@ -191,8 +242,8 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
     """
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
-                 ransac_conf=0.999):
-        super().__init__(model, bins, resolution, mma_thr, vdd_thr)
+                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995):
+        super().__init__(model, bins, resolution, mma_thr, vdd_thr, he_thresh, he_ransac_thresh, he_conf)
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
         self._pose_rows = []

@@ -540,6 +540,39 @@ int einx_relative_pose(const einx_pose_params* p, const float* mk0, const float*
  * their count (0 for a singular sample). */
 int einx_essential_5pt(const double* x1, const double* x2, int n_problems, double* E_out, int32_t* n_solutions, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Homography of the same-time evaluation (csrc/homography.hip)
+ *   HomographyEstimation   core/metrics/matching_metrics.py:188-345 (cv2.findHomography(RANSAC) with its defaults + the corner
+ *                          distances of update_one, :232-297)
+ * B pairs of matched keypoints mk0 / mk1 [B,cap,cols] float32 + nmatch int32 [B] (einx_gather_matches' layout), img_shape
+ * [B,2] int32 (H, W) or NULL, H_true [B,9] float32 or NULL.  The written algorithm of DESIGN.md 8c, not bit parity with OpenCV
+ * (its random draws are not reproduced).  Outputs:
+ *   H_out [B,9] float64 (H[2,2] = 1; zeros without a homography), mask_out [B,cap] uint8 (the RANSAC mask, not re-evaluated
+ *     after the refit and the polish),
+ *   status [B] int32: >= 0 the chosen RANSAC iteration (0 for exactly 4 matches); -1 fewer than 4 matches, -2 no homography (no
+ *     sample passed checkSubset and the fit, or the refit on the inliers failed),
+ *   rows_out [B,n_thr+2] float64 or NULL: (mean corner distance <= he_thr[i]) for i < n_thr, the mean corner distance (float32
+ *     arithmetic, as update_one), the inlier ratio -- 0.., inf, 0 without a homography; NaN ratios and error when img_shape or
+ *     H_true is NULL.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_homography_params {
+  size_t struct_size; /* sizeof(einx_homography_params) (checked) */
+  int32_t B, cap, cols;
+  int32_t kp_yx;      /* 1: keypoints are (y,x,..) */
+  int32_t max_iters;  /* RANSAC iterations (2000: findHomography's maxIters) */
+  int32_t n_thr;      /* correctness thresholds in he_thr (0..4) */
+  double thresh;      /* ransacReprojThreshold in pixels (3.0) */
+  double conf;        /* RANSAC confidence (0.995) */
+  float he_thr[4];    /* update_one's correctness_thresh */
+  uint64_t seed;      /* counter-based generator key */
+} einx_homography_params;
+size_t einx_homography_ws_bytes(const einx_homography_params* p);
+int einx_homography(const einx_homography_params* p, const float* mk0, const float* mk1, const int32_t* nmatch, const int32_t* img_shape,
+                    const float* H_true, void* ws, double* H_out, uint8_t* mask_out, int32_t* status, double* rows_out, void* stream);
+/* The fit alone (test aid, like einx_essential_5pt): x1 / x2 [n,n_points,2] float64 points (rounded to the float32 the estimator
+ * stores); H_out [n,9] float64 gets the normalised DLT of each problem (H[2,2] = 1), ok [n] int32 is 0 where it has none. */
+int einx_homography_dlt(const double* x1, const double* x2, int n_problems, int n_points, double* H_out, int32_t* ok, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
