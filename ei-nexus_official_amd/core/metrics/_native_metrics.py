@@ -88,32 +88,43 @@ POSE_SEED = 0x5EED0F5E
 POSE_STATUS = {-1: "few", -2: "noE", -3: "cheir"}  # einx.h: >= 0 pose found, negative: why not
 
 
+def _ransac_call(params, ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering, max_iters, seed, row_width, **fields):
+    """What a call of either RANSAC estimator starts with: the params struct (the fields both structs have; `fields` are the
+    estimator's own), the input checks, and the workspace / mask / status / rows it writes.  Returns (p, ws, mask, status, rows)."""
+    B, cap, cols = mk0.shape
+    dev = mk0.device
+    p = params()
+    p.struct_size = ctypes.sizeof(params)
+    p.B, p.cap, p.cols, p.kp_yx, p.max_iters = B, cap, cols, int(ordering == "yx"), int(max_iters)
+    p.thresh, p.conf, p.seed = float(thresh), float(conf), int(seed)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    N._dev_check(mk0, mk1)
+    N._dev_check(nmatch, dt=torch.int32)
+    ws = torch.empty(ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    rows = torch.empty((B, row_width), dtype=torch.float64, device=dev)
+    return p, ws, mask, status, rows
+
+
 @on_input_device
 def relative_pose(mk0, mk1, nmatch, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx", max_iters=1000, seed=POSE_SEED):
     """RANSAC essential matrix + recoverPose + update_one's errors for a batch (csrc/pose.hip), no host sync.
     mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the device, K0 / K1 [B,3,3] float32 or float64 (numpy's dtype rules
     follow K's), T_0to1 [B,4,4] or None.  Returns device tensors (R [B,3,3] f64, t [B,3] f64, mask [B,cap] bool,
     status [B] int32, rows [B,4] f64 = R_err, t_err, pose_err, inlier ratio)."""
-    B, cap, cols = mk0.shape
-    dev = mk0.device
+    B, dev = mk0.shape[0], mk0.device
     k_f64 = K0.dtype == torch.float64 or K1.dtype == torch.float64
     kdt = torch.float64 if k_f64 else torch.float32
     K0 = K0.to(dev, kdt).reshape(B, 9).contiguous()
     K1 = K1.to(dev, kdt).reshape(B, 9).contiguous()
     T = None if T_0to1 is None else T_0to1.to(dev, torch.float64).reshape(B, 16).contiguous()
-    p = PoseParams()
-    p.struct_size = ctypes.sizeof(PoseParams)
-    p.B, p.cap, p.cols, p.kp_yx, p.k_f64, p.max_iters = B, cap, cols, int(ordering == "yx"), int(k_f64), int(max_iters)
-    p.thresh, p.conf, p.seed = float(thresh), float(conf), int(seed)
     L = N.lib()
-    N._dev_check(mk0, mk1)
-    N._dev_check(nmatch, dt=torch.int32)
-    ws = torch.empty(L.einx_relative_pose_ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    p, ws, mask, status, rows = _ransac_call(PoseParams, L.einx_relative_pose_ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering, max_iters,
+                                             seed, 4, k_f64=int(k_f64))
     R = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
     t = torch.empty((B, 3), dtype=torch.float64, device=dev)
-    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, 4), dtype=torch.float64, device=dev)
     check(L.einx_relative_pose(ctypes.byref(p), N._ptr(mk0), N._ptr(mk1), N._ptr(nmatch), N._ptr(K0), N._ptr(K1), N._ptr(T), N._ptr(ws),
                                N._ptr(R), N._ptr(t), N._ptr(mask), N._ptr(status), N._ptr(rows), N._stream(mk0)), "einx_relative_pose")
     return R, t, mask.bool(), status, rows
@@ -147,8 +158,7 @@ def homography(mk0, mk1, nmatch, img_shape=None, H_true=None, thresh=3.0, conf=0
     sync.  mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the device; img_shape (H, W) for every pair or [B,2], H_true
     [B,3,3] (cast to float32 as update_one does), or None for both.  Returns device tensors (H [B,3,3] f64, mask [B,cap] bool,
     status [B] int32, rows [B,len(he_thr)+2] f64 = (error <= t) per threshold, mean corner error, inlier ratio)."""
-    B, cap, cols = mk0.shape
-    dev = mk0.device
+    B, dev = mk0.shape[0], mk0.device
     he_thr = tuple(he_thr)
     if len(he_thr) > 4:
         raise ValueError("at most 4 correctness thresholds")
@@ -156,20 +166,12 @@ def homography(mk0, mk1, nmatch, img_shape=None, H_true=None, thresh=3.0, conf=0
         img_shape = torch.as_tensor(img_shape).to(dev, torch.int32)
         img_shape = (img_shape.reshape(1, 2).expand(B, 2) if img_shape.numel() == 2 else img_shape.reshape(B, 2)).contiguous()
     Ht = None if H_true is None else H_true.to(dev, torch.float32).reshape(B, 9).contiguous()
-    p = HomographyParams()
-    p.struct_size = ctypes.sizeof(HomographyParams)
-    p.B, p.cap, p.cols, p.kp_yx, p.max_iters, p.n_thr = B, cap, cols, int(ordering == "yx"), int(max_iters), len(he_thr)
-    p.thresh, p.conf, p.seed = float(thresh), float(conf), int(seed)
+    L = N.lib()
+    p, ws, mask, status, rows = _ransac_call(HomographyParams, L.einx_homography_ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering,
+                                             max_iters, seed, len(he_thr) + 2, n_thr=len(he_thr))
     for i, t in enumerate(he_thr):
         p.he_thr[i] = float(t)
-    L = N.lib()
-    N._dev_check(mk0, mk1)
-    N._dev_check(nmatch, dt=torch.int32)
-    ws = torch.empty(L.einx_homography_ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
     H = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
-    mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    rows = torch.empty((B, len(he_thr) + 2), dtype=torch.float64, device=dev)
     check(L.einx_homography(ctypes.byref(p), N._ptr(mk0), N._ptr(mk1), N._ptr(nmatch), N._ptr(img_shape), N._ptr(Ht), N._ptr(ws), N._ptr(H),
                             N._ptr(mask), N._ptr(status), N._ptr(rows), N._stream(mk0)), "einx_homography")
     return H, mask.bool(), status, rows

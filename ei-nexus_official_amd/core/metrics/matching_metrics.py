@@ -55,6 +55,16 @@ def compute_auc(errors, thresholds):
     return aucs
 
 
+def _batch_of_one(matched_keypoints1, matched_keypoints2, to_device):
+    """one pair's matches as the batch of one the device estimators take: (mk0, mk1 [1,N,cols] float32, nmatch [1] int32), on the
+    keypoints' device when that is a GPU, else on to_device"""
+    dev = matched_keypoints1.device if matched_keypoints1.is_cuda else to_device
+    n, cols = matched_keypoints1.shape
+    mk0 = matched_keypoints1.detach().to(dev, torch.float32).reshape(1, n, cols).contiguous()
+    mk1 = matched_keypoints2.detach().to(dev, torch.float32).reshape(1, n, cols).contiguous()
+    return mk0, mk1, torch.tensor([n], dtype=torch.int32, device=dev)
+
+
 _MISSING = object()
 
 
@@ -88,12 +98,7 @@ class HomographyEstimation:
         if n < 4:
             print("Not enough points to estimate homography")
             return None, None
-        dev = matched_keypoints1.device if matched_keypoints1.is_cuda else self.to_device
-        cols = matched_keypoints1.shape[1]
-        mk0 = matched_keypoints1.detach().to(dev, torch.float32).reshape(1, n, cols).contiguous()
-        mk1 = matched_keypoints2.detach().to(dev, torch.float32).reshape(1, n, cols).contiguous()
-        nm = torch.tensor([n], dtype=torch.int32, device=dev)
-        H, mask, status, _ = homography(mk0, mk1, nm, ordering=ordering, he_thr=())
+        H, mask, status, _ = homography(*_batch_of_one(matched_keypoints1, matched_keypoints2, self.to_device), ordering=ordering, he_thr=())
         st = int(status[0])
         if st < 0:
             assert HOMOGRAPHY_STATUS[st] == "noH"
@@ -169,20 +174,6 @@ class RelativePoseEstimation:
         self.error_list = []
         assert ordering in {"xy", "yx"}
 
-    def _device_pose(self, matched_keypoints1, matched_keypoints2, K0, K1, T_0to1, thresh, conf, ordering):
-        dev = matched_keypoints1.device if matched_keypoints1.is_cuda else self.to_device
-        n = len(matched_keypoints1)
-        cols = matched_keypoints1.shape[1]
-        cap = max(n, 1)
-        mk0 = torch.zeros((1, cap, cols), dtype=torch.float32, device=dev)
-        mk1 = torch.zeros((1, cap, cols), dtype=torch.float32, device=dev)
-        mk0[0, :n] = matched_keypoints1.to(dev, torch.float32)
-        mk1[0, :n] = matched_keypoints2.to(dev, torch.float32)
-        nm = torch.tensor([n], dtype=torch.int32, device=dev)
-        k = lambda v: torch.as_tensor(v).to(dev)[None]  # noqa: E731
-        T = None if T_0to1 is None else k(T_0to1)
-        return relative_pose(mk0, mk1, nm, k(K0), k(K1), T, thresh, conf, ordering)
-
     def estimate_pose(self, matched_keypoints1, matched_keypoints2, K0, K1, thresh, conf, ordering="yx"):
         """(R [3,3], t [3], inlier mask [N] bool) as numpy, or None (printing the reference's messages)"""
         assert len(matched_keypoints1) == len(matched_keypoints2)
@@ -190,7 +181,9 @@ class RelativePoseEstimation:
         if len(matched_keypoints1) < 5:
             print("Not enough points to estimate pose")
             return None
-        R, t, mask, status, _ = self._device_pose(matched_keypoints1, matched_keypoints2, K0, K1, None, thresh, conf, ordering)
+        mk0, mk1, nm = _batch_of_one(matched_keypoints1, matched_keypoints2, self.to_device)
+        R, t, mask, status, _ = relative_pose(mk0, mk1, nm, torch.as_tensor(K0).to(mk0.device)[None], torch.as_tensor(K1).to(mk0.device)[None],
+                                              None, thresh, conf, ordering)
         st = int(status[0])
         if POSE_STATUS.get(st) == "noE":
             print("\nE is None while trying to recover pose.\n")

@@ -11,14 +11,13 @@
 //   in rounds of iterations (32, 32, 64, 128, ...), each pair skipping the iterations at or past its current scan bound:
 //   hg_solve_kernel   one wave per (iteration, pair): four draws that pass checkSubset, the DLT -> one H per sample
 //   hg_score_kernel   one workgroup per (iteration, pair): reprojection inlier count of the sample's H
-//   hg_select_kernel  one lane per pair: OpenCV's sequential scan with its shrinking iteration bound, resumed per round
+//   ransac_select_kernel  one lane per pair: OpenCV's sequential scan with its shrinking iteration bound, resumed per round
 //   hg_refine_kernel  one workgroup per pair: mask, DLT refit on the inliers, LM polish, corner errors
 #include "einx_common.h"
 #include "ransac.h"
 
 namespace {
 
-constexpr int RETRIES = 64;   // tries of one draw for an index not drawn before
 constexpr int ATTEMPTS = 16;  // samples drawn for one iteration until one passes checkSubset
 constexpr int SWEEPS = 12;    // cyclic Jacobi sweeps over the 9x9
 constexpr int LM_ITERS = 10;
@@ -26,31 +25,21 @@ constexpr double DBL_EPS = 2.220446049250313e-16;
 constexpr double FLT_EPS = 1.1920928955078125e-07;
 
 struct HgWs {
-  double* H;      // [B,iters,9]
-  int32_t* cnt;   // [B,iters] inlier count of the iteration's H, -1: no model
-  int32_t* best;  // [B] iteration of the RANSAC model, -1 none
-  int32_t* scan;  // [B][2] the selection scan's state between rounds: best count, iteration bound
+  double* H;         // [B,iters,9]
+  int32_t* cnt;      // [B,iters] inlier count of the iteration's H, -1: no model
+  RansacScan* scan;  // [B] best = iteration
 };
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-HgWs carve(const einx_homography_params* p, void* ws) {
+// the workspace's regions; ws == nullptr: only their total size in *bytes
+HgWs carve(const einx_homography_params* p, void* ws, size_t* bytes = nullptr) {
   const size_t B = p->B, it = p->max_iters;
-  char* q = (char*)ws;
+  WsCarver c{(char*)ws};
   HgWs w;
-  w.H = (double*)q;
-  q += al(B * it * 9 * 8);
-  w.cnt = (int32_t*)q;
-  q += al(B * it * 4);
-  w.best = (int32_t*)q;
-  q += al(B * 4);
-  w.scan = (int32_t*)q;
+  w.H = c.take<double>(B * it * 9);
+  w.cnt = c.take<int32_t>(B * it);
+  w.scan = c.take<RansacScan>(B);
+  if (bytes) *bytes = c.bytes;
   return w;
-}
-
-size_t ws_total(const einx_homography_params* p) {
-  const size_t B = p->B, it = p->max_iters;
-  return al(B * it * 9 * 8) + al(B * it * 4) + al(B * 4) + al(B * 8) + 256;
 }
 
 struct HgArgs {
@@ -74,28 +63,6 @@ __device__ __forceinline__ Pt load_pt(const HgArgs& a, int b, int j) {
   const float* q0 = a.mk0 + ((size_t)b * a.p.cap + j) * cols;
   const float* q1 = a.mk1 + ((size_t)b * a.p.cap + j) * cols;
   return Pt{q0[xi], q0[yi], q1[xi], q1[yi]};
-}
-
-// four distinct indices of [0, n) for attempt `att` of iteration `it`; false when a draw finds no new index within RETRIES tries
-__device__ __forceinline__ bool draw4(unsigned long long seed, int it, int att, int n, int* idx) {
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    bool got = false;
-    for (int r = 0; r < RETRIES && !got; ++r) {
-      const unsigned long long key =
-          ((unsigned long long)att << 32) | ((unsigned long long)it << 16) | ((unsigned long long)d << 8) | (unsigned long long)r;
-      const int v = (int)(splitmix64(seed ^ key) % (unsigned long long)n);
-      bool dup = false;
-#pragma unroll
-      for (int e = 0; e < 3; ++e) dup |= e < d && idx[e] == v;
-      if (!dup) {
-        idx[d] = v;
-        got = true;
-      }
-    }
-    if (!got) return false;
-  }
-  return true;
 }
 
 // haveCollinearPoints' test for the triplet (a, b, c), a < b < c, based at c
@@ -286,27 +253,24 @@ __device__ bool dlt_fit(DltLds& L, int n, F get, double* H) {
 __global__ void hg_init_kernel(const HgArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.p.B) return;
-  a.w.best[b] = -1;
-  a.w.scan[2 * b + 0] = 0;              // best count
-  a.w.scan[2 * b + 1] = a.p.max_iters;  // iteration bound
+  ransac_scan_init(a.w.scan[b], a.p.max_iters);
 }
 
-// one round of iterations [it0, it0 + gridDim.x): an iteration at or past the pair's current bound is skipped -- the bound only
-// shrinks, so the selection scan never reaches it
+// one round of iterations [it0, it0 + gridDim.x)
 __global__ __launch_bounds__(64) void hg_solve_kernel(const HgArgs a, int it0) {
   __shared__ DltLds L;
   const int it = it0 + blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int n = min(a.nmatch[b], a.p.cap);
   const size_t h = (size_t)b * a.p.max_iters + it;
   // n == 4: OpenCV solves the one sample directly (iteration 0 holds it); n < 4: no homography
-  if (n < 4 || (n == 4 && it > 0) || it >= a.w.scan[2 * b + 1]) {
+  if (n < 4 || (n == 4 && it > 0) || !ransac_live(a.w.scan[b], it)) {
     if (tid == 0) a.w.cnt[h] = -1;
     return;
   }
   int idx[4] = {0, 1, 2, 3};
   bool ok = n == 4;
   for (int att = 0; att < ATTEMPTS && !ok; ++att) {
-    if (!draw4(a.p.seed, it, att, n, idx)) continue;
+    if (!ransac_draw<4>(a.p.seed, it, att, n, idx)) continue;
     Pt q[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) q[e] = load_pt(a, b, idx[e]);
@@ -344,7 +308,7 @@ __global__ __launch_bounds__(256) void hg_score_kernel(const HgArgs a, int it0) 
   __shared__ int red[4];
   const int it = it0 + blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int n = min(a.nmatch[b], a.p.cap);
-  if (n <= 4 || it >= a.w.scan[2 * b + 1]) return;
+  if (n <= 4 || !ransac_live(a.w.scan[b], it)) return;
   const size_t h = (size_t)b * a.p.max_iters + it;
   if (a.w.cnt[h] < 0) return;
   float Hf[8];
@@ -364,25 +328,12 @@ __global__ __launch_bounds__(256) void hg_score_kernel(const HgArgs a, int it0) 
   if (tid == 0) a.w.cnt[h] = red[0] + red[1] + red[2] + red[3];
 }
 
-// the selection scan over one round [it0, it1), resumed from the state the previous round left
-__global__ void hg_select_kernel(const HgArgs a, int it0, int it1) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.p.B) return;
-  const int n = min(a.nmatch[b], a.p.cap);
-  if (n <= 4) return;
-  int best = a.w.best[b], best_cnt = a.w.scan[2 * b], bound = a.w.scan[2 * b + 1];
-  for (int it = it0; it < it1 && it < bound; ++it) {
-    const int c = a.w.cnt[(size_t)b * a.p.max_iters + it];
-    if (c > max(best_cnt, 3)) {
-      best = it;
-      best_cnt = c;
-      bound = ransac_update_iters<4>(a.p.conf, (double)(n - c) / (double)n, bound);
-    }
-  }
-  a.w.best[b] = best;
-  a.w.scan[2 * b] = best_cnt;
-  a.w.scan[2 * b + 1] = bound;
-}
+// the one model of an iteration for the selection scan (an iteration without a model counts -1 inliers)
+struct HgModels {
+  const int32_t* cnt;
+  __device__ int count(size_t) const { return 1; }
+  __device__ int inliers(size_t h, int) const { return cnt[h]; }
+};
 
 struct RefineLds {
   DltLds D;
@@ -421,37 +372,6 @@ __device__ void lm_pass(DltLds& L, int n, F get, const double* h) {
   block_sum<45>(L, acc);
 }
 
-// Gauss-Jordan with partial pivoting on the 8x9 system in L.M; d = the solution.  false: a pivot that is not > 0
-__device__ bool solve8(RefineLds& L, double* d) {
-  const int tid = threadIdx.x;
-  for (int c = 0; c < 8; ++c) {
-    int p = c;
-    for (int r = c + 1; r < 8; ++r)
-      if (fabs(L.M[r][c]) > fabs(L.M[p][c])) p = r;
-    if (!(fabs(L.M[p][c]) > 0.0)) return false;  // uniform across the workgroup
-    __syncthreads();
-    if (tid < 9 && p != c) {
-      const double t = L.M[c][tid];
-      L.M[c][tid] = L.M[p][tid];
-      L.M[p][tid] = t;
-    }
-    __syncthreads();
-    const double piv = L.M[c][c];
-    __syncthreads();
-    if (tid < 9) L.M[c][tid] = L.M[c][tid] / piv;
-    if (tid < 8) L.fac[tid] = L.M[tid][c];
-    __syncthreads();
-    if (tid < 72) {
-      const int r = tid / 9, k = tid % 9;
-      if (r != c) L.M[r][k] = L.M[r][k] - L.fac[r] * L.M[c][k];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d[i] = L.M[i][8];
-  return true;
-}
-
 __global__ __launch_bounds__(256) void hg_refine_kernel(const HgArgs a) {
   __shared__ RefineLds L;
   __shared__ int red[4];
@@ -462,7 +382,7 @@ __global__ __launch_bounds__(256) void hg_refine_kernel(const HgArgs a) {
   for (size_t j = tid; j < cap; j += 256) mout[j] = 0;
   int status = n < 4 ? -1 : -2, ninl = 0;
   double H[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const int bi = n == 4 ? 0 : (n > 4 ? a.w.best[b] : -1);
+  const int bi = n == 4 ? 0 : (n > 4 ? a.w.scan[b].best : -1);
   if (bi >= 0 && a.w.cnt[(size_t)b * a.p.max_iters + bi] >= 0) {  // uniform across the workgroup
     const double* Hb = a.w.H + ((size_t)b * a.p.max_iters + bi) * 9;
 #pragma unroll
@@ -508,7 +428,9 @@ __global__ __launch_bounds__(256) void hg_refine_kernel(const HgArgs a) {
           }
           __syncthreads();
           double d[8], hd[8], dmax = 0.0;
-          if (!solve8(L, d)) break;
+          if (!gauss_jordan<8, 9>(L.M, L.fac, 0.0)) break;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) d[e] = L.M[e][8];
           bool fin = true;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
@@ -607,7 +529,9 @@ __global__ __launch_bounds__(256) void hg_dlt_kernel(const double* x1, const dou
 
 EINX_EXPORT size_t einx_homography_ws_bytes(const einx_homography_params* p) {
   if (!p || p->struct_size != sizeof(einx_homography_params) || p->B <= 0 || p->cap <= 0 || p->max_iters <= 0) return 0;
-  return ws_total(p);
+  size_t bytes = 0;
+  carve(p, nullptr, &bytes);
+  return bytes;
 }
 
 EINX_EXPORT int einx_homography(const einx_homography_params* p, const float* mk0, const float* mk1, const int32_t* nmatch,
@@ -635,19 +559,17 @@ EINX_EXPORT int einx_homography(const einx_homography_params* p, const float* mk
   const unsigned B = (unsigned)p->B;
   hipLaunchKernelGGL(hg_init_kernel, dim3((unsigned)einx_cdiv(p->B, 64)), dim3(64), 0, s, a);
   EINX_CHECK_LAUNCH();
-  // rounds of 32, 32, 64, 128, 256, 512.. iterations: solve, score, then the scan; each pair's workgroups past its bound exit at
-  // once.  The schedule is fixed (no host sync, capturable); the scan's result does not depend on it.
-  for (int it0 = 0, len = 32; it0 < p->max_iters;) {
-    const int it1 = it0 + len < p->max_iters ? it0 + len : p->max_iters;
+  // a failed launch ends the rounds and stays pending for the check below
+  ransac_rounds(p->max_iters, [&](int it0, int it1) {
     hipLaunchKernelGGL(hg_solve_kernel, dim3((unsigned)(it1 - it0), B), dim3(64), 0, s, a, it0);
-    EINX_CHECK_LAUNCH();
+    if (hipPeekAtLastError() != hipSuccess) return false;
     hipLaunchKernelGGL(hg_score_kernel, dim3((unsigned)(it1 - it0), B), dim3(256), 0, s, a, it0);
-    EINX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(hg_select_kernel, dim3((unsigned)einx_cdiv(p->B, 64)), dim3(64), 0, s, a, it0, it1);
-    EINX_CHECK_LAUNCH();
-    if (it1 >= 64) len *= 2;
-    it0 = it1;
-  }
+    if (hipPeekAtLastError() != hipSuccess) return false;
+    hipLaunchKernelGGL((ransac_select_kernel<4, 1, HgModels>), dim3((unsigned)einx_cdiv(p->B, 64)), dim3(64), 0, s, a.w.scan, nmatch, p->B,
+                       p->cap, p->max_iters, p->conf, it0, it1, HgModels{a.w.cnt});
+    return hipPeekAtLastError() == hipSuccess;
+  });
+  EINX_CHECK_LAUNCH();
   hipLaunchKernelGGL(hg_refine_kernel, dim3(B), dim3(256), 0, s, a);
   EINX_CHECK_LAUNCH();
   return EINX_OK;

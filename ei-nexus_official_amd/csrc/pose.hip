@@ -10,7 +10,7 @@
 //   in rounds of iterations (32, 32, 64, 128, ...), each pair skipping the iterations at or past its current scan bound:
 //   pose_solve_kernel    one wave per (iteration, pair): five draws, the minimal solver -> up to 10 E per sample
 //   pose_score_kernel    one workgroup per (iteration, pair): Sampson inlier counts of the sample's models
-//   pose_select_kernel   one lane per pair: OpenCV's sequential scan with its shrinking iteration bound, resumed per round
+//   ransac_select_kernel one lane per pair: OpenCV's sequential scan with its shrinking iteration bound, resumed per round
 //   pose_recover_kernel  one workgroup per pair: decomposition, cheirality vote, mask, errors
 #include "einx_common.h"
 #include "ransac.h"
@@ -18,71 +18,33 @@
 namespace {
 
 constexpr int MAXS = 10;  // real solutions of one five-point sample
-constexpr int RETRIES = 64;
 
 struct PoseWs {
-  double4* xn;    // [B,cap] (u1, v1, u2, v2) normalised
-  float* thr2;    // [B] (float)(thr * thr)
-  double* E;      // [B,iters,MAXS,9]
-  int32_t* nsol;  // [B,iters]
-  int32_t* cnt;   // [B,iters,MAXS]
-  int32_t* best;  // [B] iteration * 16 + solution of the RANSAC model, -1 none
-  int32_t* scan;  // [B][3] the selection scan's state between rounds: best count, iteration bound, (unused)
-  uint8_t* cur;   // [B,cap] the recoverPose in/out mask
-  uint8_t* ok;    // [B,cap] cheirality bits of the four candidates
+  double4* xn;       // [B,cap] (u1, v1, u2, v2) normalised
+  float* thr2;       // [B] (float)(thr * thr)
+  double* E;         // [B,iters,MAXS,9]
+  int32_t* nsol;     // [B,iters]
+  int32_t* cnt;      // [B,iters,MAXS]
+  RansacScan* scan;  // [B] best = iteration * 16 + solution
+  uint8_t* cur;      // [B,cap] the recoverPose in/out mask
+  uint8_t* ok;       // [B,cap] cheirality bits of the four candidates
 };
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-PoseWs carve(const einx_pose_params* p, void* ws) {
+// the workspace's regions; ws == nullptr: only their total size in *bytes
+PoseWs carve(const einx_pose_params* p, void* ws, size_t* bytes = nullptr) {
   const size_t B = p->B, cap = p->cap, it = p->max_iters;
-  char* q = (char*)ws;
+  WsCarver c{(char*)ws};
   PoseWs w;
-  w.xn = (double4*)q;
-  q += al(B * cap * sizeof(double4));
-  w.thr2 = (float*)q;
-  q += al(B * 4);
-  w.E = (double*)q;
-  q += al(B * it * MAXS * 9 * 8);
-  w.nsol = (int32_t*)q;
-  q += al(B * it * 4);
-  w.cnt = (int32_t*)q;
-  q += al(B * it * MAXS * 4);
-  w.best = (int32_t*)q;
-  q += al(B * 4);
-  w.scan = (int32_t*)q;
-  q += al(B * 12);
-  w.cur = (uint8_t*)q;
-  q += al(B * cap);
-  w.ok = (uint8_t*)q;
+  w.xn = c.take<double4>(B * cap);
+  w.thr2 = c.take<float>(B);
+  w.E = c.take<double>(B * it * MAXS * 9);
+  w.nsol = c.take<int32_t>(B * it);
+  w.cnt = c.take<int32_t>(B * it * MAXS);
+  w.scan = c.take<RansacScan>(B);
+  w.cur = c.take<uint8_t>(B * cap);
+  w.ok = c.take<uint8_t>(B * cap);
+  if (bytes) *bytes = c.bytes;
   return w;
-}
-
-size_t ws_total(const einx_pose_params* p) {
-  const size_t B = p->B, cap = p->cap, it = p->max_iters;
-  return al(B * cap * sizeof(double4)) + al(B * 4) + al(B * it * MAXS * 9 * 8) + al(B * it * 4) + al(B * it * MAXS * 4) + al(B * 4) +
-         al(B * 12) + al(B * cap) + al(B * cap) + 256;
-}
-
-// five distinct indices of [0, n) for iteration `it`; false when a draw finds no new index within RETRIES tries
-__device__ __forceinline__ bool draw5(unsigned long long seed, int it, int n, int* idx) {
-#pragma unroll
-  for (int d = 0; d < 5; ++d) {
-    bool got = false;
-    for (int r = 0; r < RETRIES && !got; ++r) {
-      const int v = (int)(splitmix64(seed ^ (((unsigned long long)it << 16) | ((unsigned long long)d << 8) | (unsigned long long)r)) %
-                          (unsigned long long)n);
-      bool dup = false;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dup |= e < d && idx[e] == v;
-      if (!dup) {
-        idx[d] = v;
-        got = true;
-      }
-    }
-    if (!got) return false;
-  }
-  return true;
 }
 
 // monomial x^ex y^ey z^ez (total degree 3 or less) -> column of Nister's ordering
@@ -208,30 +170,7 @@ __device__ int solve5(SolveLds& L, const double4* x, double* E_out) {
   // Gauss-Jordan with partial pivoting over the first five columns (tests/pose_f64.py:null_basis)
   double amax = 0.0;
   for (int i = 0; i < 45; ++i) amax = fmax(amax, fabs(L.A[i / 9][i % 9]));
-  const double tol = 1e-9 * amax;
-  for (int c = 0; c < 5; ++c) {
-    int p = c;
-    for (int r = c + 1; r < 5; ++r)
-      if (fabs(L.A[r][c]) > fabs(L.A[p][c])) p = r;
-    if (!(fabs(L.A[p][c]) > tol)) return 0;  // uniform across the workgroup
-    __syncthreads();
-    if (lane < 9 && p != c) {
-      const double t = L.A[c][lane];
-      L.A[c][lane] = L.A[p][lane];
-      L.A[p][lane] = t;
-    }
-    __syncthreads();
-    const double piv = L.A[c][c];
-    __syncthreads();
-    if (lane < 9) L.A[c][lane] = L.A[c][lane] / piv;
-    if (lane < 5) L.fac[lane] = L.A[lane][c];
-    __syncthreads();
-    if (lane < 45) {
-      const int r = lane / 9, k = lane % 9;
-      if (r != c) L.A[r][k] = L.A[r][k] - L.fac[r] * L.A[c][k];
-    }
-    __syncthreads();
-  }
+  if (!gauss_jordan<5, 9>(L.A, L.fac, 1e-9 * amax)) return 0;  // uniform across the workgroup
   if (lane < 36) {
     const int e = lane / 4, k = lane % 4;
     L.Ec[e][k] = e < 5 ? -L.A[e][5 + k] : (e - 5 == k ? 1.0 : 0.0);
@@ -270,30 +209,7 @@ __device__ int solve5(SolveLds& L, const double4* x, double* E_out) {
   __syncthreads();
   double mmax = 0.0;
   for (int i = 0; i < 100; ++i) mmax = fmax(mmax, fabs(L.M[i / 10][i % 10]));
-  const double mtol = 1e-13 * mmax;
-  for (int c = 0; c < 10; ++c) {
-    int p = c;
-    for (int r = c + 1; r < 10; ++r)
-      if (fabs(L.M[r][c]) > fabs(L.M[p][c])) p = r;
-    if (!(fabs(L.M[p][c]) > mtol)) return 0;
-    __syncthreads();
-    if (lane < 20 && p != c) {
-      const double t = L.M[c][lane];
-      L.M[c][lane] = L.M[p][lane];
-      L.M[p][lane] = t;
-    }
-    __syncthreads();
-    const double piv = L.M[c][c];
-    __syncthreads();
-    if (lane < 20) L.M[c][lane] = L.M[c][lane] / piv;
-    if (lane < 10) L.fac[lane] = L.M[lane][c];
-    __syncthreads();
-    for (int q = lane; q < 200; q += 64) {
-      const int r = q / 20, k = q % 20;
-      if (r != c) L.M[r][k] = L.M[r][k] - L.fac[r] * L.M[c][k];
-    }
-    __syncthreads();
-  }
+  if (!gauss_jordan<10, 20>(L.M, L.fac, 1e-13 * mmax)) return 0;
   if (lane < 60) L.Bz[lane / 10][lane % 10] = L.M[4 + lane / 10][10 + lane % 10];
   __syncthreads();
   // <k> = <e> - z<f>, <l> = <g> - z<h>, <m> = <i> - z<j>: a 3x3 matrix of polynomials in z acting on (x, y, 1);
@@ -489,11 +405,7 @@ __global__ void pose_norm_kernel(const PoseArgs a) {
   const int b = blockIdx.y;
   const int n = min(a.nmatch[b], a.p.cap);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) {
-    a.w.best[b] = -1;
-    a.w.scan[3 * b + 0] = 0;            // best count
-    a.w.scan[3 * b + 1] = a.p.max_iters;  // iteration bound
-  }
+  if (t == 0) ransac_scan_init(a.w.scan[b], a.p.max_iters);
   if (t >= n) return;
   if (a.p.k_f64)
     norm_pair<double>(a, b, t);
@@ -501,8 +413,7 @@ __global__ void pose_norm_kernel(const PoseArgs a) {
     norm_pair<float>(a, b, t);
 }
 
-// one round of iterations [it0, it0 + gridDim.x): an iteration at or past the pair's current bound is skipped -- the bound only
-// shrinks, so the selection scan never reaches it
+// one round of iterations [it0, it0 + gridDim.x)
 __global__ __launch_bounds__(64) void pose_solve_kernel(const PoseArgs a, int it0) {
   __shared__ SolveLds L;
   __shared__ double4 xs[5];
@@ -511,12 +422,12 @@ __global__ __launch_bounds__(64) void pose_solve_kernel(const PoseArgs a, int it
   int32_t* nsol = a.w.nsol + (size_t)b * a.p.max_iters + it;
   double* E = a.w.E + ((size_t)b * a.p.max_iters + it) * MAXS * 9;
   // n == 5: OpenCV solves the one sample and keeps every solution (iteration 0 holds it); n < 5: no pose
-  if (n < 5 || (n == 5 && it > 0) || it >= a.w.scan[3 * b + 1]) {
+  if (n < 5 || (n == 5 && it > 0) || !ransac_live(a.w.scan[b], it)) {
     if (threadIdx.x == 0) *nsol = 0;
     return;
   }
   int idx[5] = {0, 1, 2, 3, 4};
-  if (n > 5 && !draw5(a.p.seed, it, n, idx)) {
+  if (n > 5 && !ransac_draw<5>(a.p.seed, it, 0, n, idx)) {
     if (threadIdx.x == 0) *nsol = 0;
     return;
   }
@@ -563,7 +474,7 @@ __global__ __launch_bounds__(256) void pose_score_kernel(const PoseArgs a, int i
   __shared__ int red[4][MAXS];
   const int it = it0 + blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int n = min(a.nmatch[b], a.p.cap);
-  if (n <= 5 || it >= a.w.scan[3 * b + 1]) return;
+  if (n <= 5 || !ransac_live(a.w.scan[b], it)) return;
   const size_t h = (size_t)b * a.p.max_iters + it;
   const int ns = a.w.nsol[h];
   if (ns == 0) return;
@@ -587,29 +498,12 @@ __global__ __launch_bounds__(256) void pose_score_kernel(const PoseArgs a, int i
   if (tid < ns) a.w.cnt[h * MAXS + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
-// the selection scan over one round [it0, it1), resumed from the state the previous round left
-__global__ void pose_select_kernel(const PoseArgs a, int it0, int it1) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= a.p.B) return;
-  const int n = min(a.nmatch[b], a.p.cap);
-  if (n <= 5) return;
-  int best = a.w.best[b], best_cnt = a.w.scan[3 * b], bound = a.w.scan[3 * b + 1];
-  for (int it = it0; it < it1 && it < bound; ++it) {
-    const size_t h = (size_t)b * a.p.max_iters + it;
-    const int ns = a.w.nsol[h];
-    for (int s = 0; s < ns; ++s) {
-      const int c = a.w.cnt[h * MAXS + s];
-      if (c > max(best_cnt, 4)) {
-        best = it * 16 + s;
-        best_cnt = c;
-        bound = ransac_update_iters<5>(a.p.conf, (double)(n - c) / (double)n, bound);
-      }
-    }
-  }
-  a.w.best[b] = best;
-  a.w.scan[3 * b] = best_cnt;
-  a.w.scan[3 * b + 1] = bound;
-}
+// the models of one iteration for the selection scan
+struct PoseModels {
+  const int32_t *nsol, *cnt;
+  __device__ int count(size_t h) const { return nsol[h]; }
+  __device__ int inliers(size_t h, int s) const { return cnt[h * MAXS + s]; }
+};
 
 // DLT triangulation against [I|0] and [R|t] (smallest eigenvector of A^T A, cyclic Jacobi) and recoverPose's depth tests
 __device__ bool cheiral(const double* R, const double* t, const double4 q) {
@@ -739,8 +633,8 @@ __global__ __launch_bounds__(256) void pose_recover_kernel(const PoseArgs a) {
     nmodels = a.w.nsol[(size_t)b * a.p.max_iters];
     models = a.w.E + (size_t)b * a.p.max_iters * MAXS * 9;
     for (int j = tid; j < n; j += 256) cur[j] = 1;
-  } else if (n > 5 && a.w.best[b] >= 0) {
-    const int bi = a.w.best[b];
+  } else if (n > 5 && a.w.scan[b].best >= 0) {
+    const int bi = a.w.scan[b].best;
     nmodels = 1;
     models = a.w.E + (((size_t)b * a.p.max_iters + (bi >> 4)) * MAXS + (bi & 15)) * 9;
     const float thr2 = a.w.thr2[b];
@@ -794,7 +688,7 @@ __global__ __launch_bounds__(256) void pose_recover_kernel(const PoseArgs a) {
     __syncthreads();
     if (ng > best_n) {
       best_n = ng;
-      status = n == 5 ? s : a.w.best[b];
+      status = n == 5 ? s : a.w.scan[b].best;
       if (tid < 12) keepR[tid] = cand[kbest][tid];
       for (int j = tid; j < n; j += 256) mout[j] = cur[j];
     }
@@ -855,7 +749,9 @@ __global__ __launch_bounds__(256) void pose_recover_kernel(const PoseArgs a) {
 
 EINX_EXPORT size_t einx_relative_pose_ws_bytes(const einx_pose_params* p) {
   if (!p || p->struct_size != sizeof(einx_pose_params) || p->B <= 0 || p->cap <= 0 || p->max_iters <= 0) return 0;
-  return ws_total(p);
+  size_t bytes = 0;
+  carve(p, nullptr, &bytes);
+  return bytes;
 }
 
 EINX_EXPORT int einx_relative_pose(const einx_pose_params* p, const float* mk0, const float* mk1, const int32_t* nmatch, const void* K0,
@@ -884,19 +780,17 @@ EINX_EXPORT int einx_relative_pose(const einx_pose_params* p, const float* mk0, 
   const unsigned B = (unsigned)p->B;
   hipLaunchKernelGGL(pose_norm_kernel, dim3((unsigned)einx_cdiv(p->cap, 256), B), dim3(256), 0, s, a);
   EINX_CHECK_LAUNCH();
-  // rounds of 32, 32, 64, 128, 256, 512.. iterations: solve, score, then the scan; each pair's workgroups past its bound exit at
-  // once.  The schedule is fixed (no host sync, capturable); the scan's result does not depend on it.
-  for (int it0 = 0, len = 32; it0 < p->max_iters;) {
-    const int it1 = it0 + len < p->max_iters ? it0 + len : p->max_iters;
+  // a failed launch ends the rounds and stays pending for the check below
+  ransac_rounds(p->max_iters, [&](int it0, int it1) {
     hipLaunchKernelGGL(pose_solve_kernel, dim3((unsigned)(it1 - it0), B), dim3(64), 0, s, a, it0);
-    EINX_CHECK_LAUNCH();
+    if (hipPeekAtLastError() != hipSuccess) return false;
     hipLaunchKernelGGL(pose_score_kernel, dim3((unsigned)(it1 - it0), B), dim3(256), 0, s, a, it0);
-    EINX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pose_select_kernel, dim3((unsigned)einx_cdiv(p->B, 64)), dim3(64), 0, s, a, it0, it1);
-    EINX_CHECK_LAUNCH();
-    if (it1 >= 64) len *= 2;
-    it0 = it1;
-  }
+    if (hipPeekAtLastError() != hipSuccess) return false;
+    hipLaunchKernelGGL((ransac_select_kernel<5, 16, PoseModels>), dim3((unsigned)einx_cdiv(p->B, 64)), dim3(64), 0, s, a.w.scan, nmatch,
+                       p->B, p->cap, p->max_iters, p->conf, it0, it1, PoseModels{a.w.nsol, a.w.cnt});
+    return hipPeekAtLastError() == hipSuccess;
+  });
+  EINX_CHECK_LAUNCH();
   hipLaunchKernelGGL(pose_recover_kernel, dim3(B), dim3(256), 0, s, a);
   EINX_CHECK_LAUNCH();
   return EINX_OK;

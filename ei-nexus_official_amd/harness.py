@@ -45,6 +45,9 @@ class SameTimeEvaluator:
     def step(self, events_list, images, homography=None):
         """events_list: B dicts {"x","y","t","p"} of numpy arrays; images: [B,1,H,W] float (0..255) on the device
         (scaled in place by SuperPoint exactly like the reference).  Returns the per-pair metric rows [B,K] (device)."""
+        return self._step(events_list, images, homography, None)
+
+    def _step(self, events_list, images, homography, pose):
         W, H = self.resolution
         dev = images.device
         if not hasattr(self, "_stages"):
@@ -59,7 +62,7 @@ class SameTimeEvaluator:
             events_rep, events_mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage)
             self.last_inputs = (events_rep, events_mask)  # what the extractors saw (deterministic since round 4: bit-equal run to run)
             ef, imf, matches = self.model._finish(self.model._enqueue(events_rep, images, events_mask, image_feats=im))
-        return self._account(ef, imf, matches, homography)
+        return self._account(ef, imf, matches, homography, pose)
 
     def _account(self, ef, imf, matches, homography, pose=None):
         rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, homography, self.mma_thr, self.vdd_thr)
@@ -151,12 +154,7 @@ class SameTimeEvaluator:
         mean = (s / c.clamp_min(1)).tolist()
         out = dict(zip(self.names, mean))
         if self.he_thresh is not None:
-            width = len(self.he_thresh) + 2
-            rows = torch.cat(self._he_rows, 0) if self._he_rows else torch.empty((0, width), dtype=torch.float64)
-            # every rank of an evaluator built with he_thresh takes part in the gather, with zero rows if it saw no homography
-            rows = gather_rows(rows)
-            if rows.shape[0]:
-                out.update(he_summary(rows, self.he_thresh))
+            out.update(_gathered_summary(self._he_rows, len(self.he_thresh) + 2, he_summary, self.he_thresh))
         return out
 
 
@@ -183,43 +181,50 @@ def gather_rows(rows):
 gather_pose_rows = gather_rows  # the name it had while the pose rows were its only user
 
 
+def _gathered_summary(batches, width, summary, thresholds):
+    """an estimator's keys of result(): its per-batch row tensors [P,width] concatenated, gathered over the ranks and summarised;
+    {} when no rank has a row.  Every rank takes part in the gather, with zero rows if it ran no estimation: a rank that skipped
+    the collective would leave the others waiting in it."""
+    rows = gather_rows(torch.cat(batches, 0) if batches else torch.empty((0, width), dtype=torch.float64))
+    return summary(rows, thresholds) if rows.shape[0] else {}
+
+
+def _summary(cols, errors, thresholds, name):
+    """per-pair columns {key: values} -> the mean of each key over its finite values, as the scripts form every key of their result
+    dicts, plus AUC@t over the finite errors"""
+    from .core.metrics.matching_metrics import compute_auc
+    out = {k: np.mean(v[np.isfinite(v)]) for k, v in cols.items()}
+    auc = compute_auc(list(errors), thresholds)
+    for t in thresholds:
+        out[f"{name}@{t}_auc"] = auc[f"{t}"]
+    return out
+
+
+def _rows_f64(rows, width):
+    return np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64).reshape(-1, width)
+
+
 def he_summary(rows, he_thresh=(3, 5, 10), name="HE"):
     """the HE keys of test_events-image_same-time.py:269-277 from per-pair rows ((error <= t) per threshold, mean corner error,
     inlier ratio; 0.., inf, 0 for a pair without a homography): the mean of each key over its finite values, as the script forms
     every key of its result_dict, and AUC@t over the finite errors"""
-    from .core.metrics.matching_metrics import compute_auc
     nt = len(he_thresh)
-    r = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64).reshape(-1, nt + 2)
+    r = _rows_f64(rows, nt + 2)
     cols = {f"{name}@{t}_ratio": r[:, i] for i, t in enumerate(he_thresh)}
     cols[f"{name}_errors"] = r[:, nt]
     cols[f"{name}_inliers"] = r[:, nt + 1]
-    out = {}
-    for k, v in cols.items():
-        v = v[np.isfinite(v)]
-        out[k] = np.mean(v)
-    auc = compute_auc(list(r[:, nt]), he_thresh)
-    for t in he_thresh:
-        out[f"{name}@{t}_auc"] = auc[f"{t}"]
-    return out
+    return _summary(cols, r[:, nt], he_thresh, name)
 
 
 def rpe_summary(rows, pose_thresh=(5, 10, 20), name="RPE"):
     """rpe_dict of test_events-image_different_time.py:326-334 from per-pair rows (R_err, t_err, pose_err, inlier ratio; inf
     errors for a pair without a pose): the mean of each key over its finite values, AUC@t over the finite pose errors"""
-    from .core.metrics.matching_metrics import compute_auc
-    r = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64).reshape(-1, 4)
+    r = _rows_f64(rows, 4)
     ok = np.isfinite(r[:, 0])
     cols = {f"{name}_R_errs": r[:, 0], f"{name}_t_errs": r[:, 1], f"{name}_pose_errs": r[:, 2], f"{name}_inliers": r[:, 3]}
     for t in pose_thresh:
         cols[f"{name}@{t}_ratio"] = np.where(ok, (r[:, 2] <= t).astype(np.float32), 0.0)
-    out = {}
-    for k, v in cols.items():
-        v = v[np.isfinite(v)]
-        out[k] = np.mean(v)
-    auc = compute_auc(list(r[:, 2]), pose_thresh)
-    for t in pose_thresh:
-        out[f"{name}@{t}_auc"] = auc[f"{t}"]
-    return out
+    return _summary(cols, r[:, 2], pose_thresh, name)
 
 
 class DifferentTimeEvaluator(SameTimeEvaluator):
@@ -250,15 +255,9 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
 
     @torch.no_grad()
     def step(self, events_list, images, homography=None, pose=None):
-        self._pose_next = pose
-        try:
-            return super().step(events_list, images, homography)
-        finally:
-            self._pose_next = None
+        return self._step(events_list, images, homography, pose)
 
     def _account(self, ef, imf, matches, homography, pose=None):
-        if pose is None:
-            pose = getattr(self, "_pose_next", None)
         out = super()._account(ef, imf, matches, homography)
         if pose is not None:
             K0, K1, T = pose
@@ -269,12 +268,7 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
 
     def result(self):
         out = super().result()
-        rows = torch.cat(self._pose_rows, 0) if self._pose_rows else torch.empty((0, 4), dtype=torch.float64)
-        # every rank takes part in the gather, with zero rows if it was given no poses: a rank that skipped the collective
-        # would leave the others waiting in it
-        rows = gather_pose_rows(rows)
-        if rows.shape[0]:
-            out.update(rpe_summary(rows, self.pose_thresh))
+        out.update(_gathered_summary(self._pose_rows, 4, rpe_summary, self.pose_thresh))
         return out
 
     def pose_inputs(self, matches, b=0):

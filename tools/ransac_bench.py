@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Device time of a batched RANSAC estimator, the relative pose (csrc/pose.hip) or the homography (csrc/homography.hip): B pairs of
+cap matches with realistic ragged counts (pose: MVSEC-like scenes, homography: 346 x 260 frames; 0.5 px noise, 30 % outliers),
+timed with device events around the whole launch sequence.  Only the public relative_pose / homography functions are used, so
+EINX_LIB=ab_libs/libeinx_X.so times an A/B build.
+
+    python tools/ransac_bench.py {pose,homography} [--B 32] [--cap 1024] [--iters 20] [--outliers 0.3]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def pose_workload(nm, scenes):
+    """(the estimator, its arguments after the matches, the estimator's keys of the result line)"""
+    import pose_f64 as P
+    K0, K1, T = (np.stack(v) for v in zip(*(s[2:] for s in scenes(P.scene))))
+
+    def report(out):
+        status = out[3].cpu().numpy()
+        return {"posed": int((status >= 0).sum()), "median_pose_err_deg": float(np.median(out[4][:, 2].cpu().numpy()))}
+    return nm.relative_pose, (K0, K1, T), report
+
+
+def homography_workload(nm, scenes):
+    import homography_f64 as Hm
+    Ht = np.stack([s[2] for s in scenes(Hm.scene)]).astype(np.float32)
+
+    def report(out):
+        status, err = out[2].cpu().numpy(), out[3][:, 3].cpu().numpy()
+        return {"found": int((status >= 0).sum()), "max_chosen_iteration": int(status.max()), "median_HE_error_px": float(np.median(err)),
+                "max_HE_error_px": float(np.max(err))}
+    return nm.homography, (np.array([Hm.IMG_SHAPE] * len(Ht), np.int32), Ht), report
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("estimator", choices=("pose", "homography"))
+    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--cap", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--outliers", type=float, default=0.3)
+    a = ap.parse_args()
+    from helpers import load_pkg
+    nm = importlib.import_module(load_pkg().__name__ + ".core.metrics._native_metrics")
+    rng = np.random.default_rng(0)
+    mk0 = np.zeros((a.B, a.cap, 3), np.float32)
+    mk1 = np.zeros((a.B, a.cap, 3), np.float32)
+    cnt = np.zeros(a.B, np.int32)
+
+    def scenes(scene):  # fills the matches and yields each pair's scene: (k0, k1, the estimator's ground truth...)
+        for b in range(a.B):
+            n = int(rng.integers(a.cap // 4, a.cap + 1))  # ragged: MNN keeps a quarter to all of the top-k keypoints
+            s = scene(rng, n, noise=0.5, outliers=a.outliers)
+            mk0[b, :n], mk1[b, :n], cnt[b] = s[0], s[1], n
+            yield s
+
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to("cuda:0")  # noqa: E731
+    run, extra, report = (pose_workload if a.estimator == "pose" else homography_workload)(nm, scenes)
+    args = tuple(t(x) for x in (mk0, mk1, cnt) + extra)
+    for _ in range(3):
+        run(*args)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = run(*args)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    print(json.dumps({"B": a.B, "cap": a.cap, "outliers": a.outliers, "mean_nmatch": float(cnt.mean()), "ms_median": float(np.median(times)),
+                      "ms_min": float(np.min(times)), "ms_max": float(np.max(times)), **report(out)}))
+
+
+if __name__ == "__main__":
+    main()
