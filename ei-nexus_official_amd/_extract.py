@@ -361,7 +361,7 @@ class ExtractorEngine:
         bf.det = det
         bf.sparse_desc = e(B, cap, D)
         nws = int(L.einx_extract_ws_bytes(h, B, H, W, cap, int(nms_iters)))
-        ws = e(nws, dt=torch.uint8)
+        ws = N._workspace(nws, dev)
         m8 = _mask_u8(mask, H, W)
         P = N._ptr
         bf.score_crop = e(B, 1, H, W)  # the dict's un-padded `score`, written by the score kernel (no crop + clone launch afterwards)

@@ -106,6 +106,12 @@ def on_input_device(fn):
     return wrapped
 
 
+def _workspace(nbytes, device):
+    """The caller-owned scratch of one op call: `nbytes` is what the op's *_ws_bytes query returned.  Every workspace of the
+    package is allocated here (the one seam tests/test_workspace_gpu.py puts its guard bytes behind)."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 def _stream(t):
     # (torch.cuda.current_stream builds a Stream object per call: 6-7 us, nine times per forward)
     return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(t.device.index if t.device.index is not None else torch.cuda.current_device()))
@@ -258,7 +264,7 @@ def detect(score, *, top_k, radius, det_thr, pads=(0, 0, 0, 0), ordering="yx", c
     p = DetectParams(B, Hp, Wp, H, W, h0, w0, int(radius), int(top_k or 0), float(det_thr), int(ordering == "xy"), cap, int(nms_iters))
     L = lib()
     dev = score.device
-    ws = torch.empty(L.einx_detect_ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.einx_detect_ws_bytes(ctypes.byref(p)), dev)
     d = Detection()
     d.positions = torch.empty((B, cap, 3), dtype=F32, device=dev)
     d.indices = torch.empty((B, cap), dtype=torch.int32, device=dev)
@@ -332,7 +338,7 @@ def mnn(desc0, n, desc1, m, want_la=True, ratio_thresh=None, distance_thresh=Non
     cap1 = desc1.shape[1]
     L = lib()
     dev = desc0.device
-    ws = torch.empty(L.einx_mnn_ws_bytes(B, cap0, cap1), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.einx_mnn_ws_bytes(B, cap0, cap1), dev)
     r = MatchResult()
     r.matches0 = torch.empty((B, cap0), dtype=torch.int64, device=dev)
     r.matches1 = torch.empty((B, cap1), dtype=torch.int64, device=dev)
@@ -403,7 +409,7 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False)
     nbytes = L.einx_lg_ws_bytes_heads(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim))
     if not nbytes:
         raise NotImplementedError("einx LightGlue: descriptor_dim must be num_heads x head_dim with head_dim a multiple of 4, at most 256")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     r = MatchResult()
     r.matches0 = torch.empty((B, cap0), dtype=torch.int64, device=dev)
     r.matches1 = torch.empty((B, cap1), dtype=torch.int64, device=dev)

@@ -37,7 +37,7 @@ def pair_metrics(kpts0, desc0, n, kpts1, desc1, m, mk0, mk1, nmatch, size0, size
     hom = None
     if homography is not None:
         hom = homography.to(dev, torch.float32).reshape(B, 9).contiguous()
-    ws = torch.empty(L.einx_metrics_ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    ws = N._workspace(L.einx_metrics_ws_bytes(ctypes.byref(p)), dev)
     out = torch.empty((B, 1 + p.n_mma + 3 * p.n_vdd), dtype=torch.float64, device=dev)
     N._dev_check(kpts0, kpts1, desc0, desc1, mk0, mk1)
     N._dev_check(n, m, nmatch, dt=torch.int32)
@@ -101,7 +101,7 @@ def _ransac_call(params, ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering, max
         setattr(p, k, v)
     N._dev_check(mk0, mk1)
     N._dev_check(nmatch, dt=torch.int32)
-    ws = torch.empty(ws_bytes(ctypes.byref(p)), dtype=torch.uint8, device=dev)
+    ws = N._workspace(ws_bytes(ctypes.byref(p)), dev)
     mask = torch.empty((B, cap), dtype=torch.uint8, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     rows = torch.empty((B, row_width), dtype=torch.float64, device=dev)

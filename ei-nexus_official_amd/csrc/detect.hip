@@ -1028,23 +1028,25 @@ EINX_EXPORT int einx_dense_positions(const float* score, int B, int H, int W, in
   return EINX_OK;
 }
 
+// einx_detect's workspace: the two maps that the NMS passes ping-pong between, the pass flags, 256 bytes of slack
+EinxDetectWs einx_detect_carve(WsCarver& c, const einx_detect_params* p) {
+  const size_t map = (size_t)p->B * p->Hp * p->Wp;
+  const EinxDetectWs w{c.take<float>(map), c.take<float>(map), c.take<int32_t>((size_t)p->B * (p->nms_iters > 0 ? p->nms_iters : 1)),
+                       p->radius > 0 ? p->B * p->nms_iters : 0};
+  c.slack(256);
+  return w;
+}
+
 EINX_EXPORT size_t einx_detect_ws_bytes(const einx_detect_params* p) {
   if (!p) return 0;
-  const size_t map = (size_t)p->B * p->Hp * p->Wp * sizeof(float);
-  const size_t flags = (size_t)p->B * (p->nms_iters > 0 ? p->nms_iters : 1) * sizeof(int32_t);
-  return 2 * map + ((flags + 255) & ~(size_t)255) + 256;
+  WsCarver c{nullptr};
+  einx_detect_carve(c, p);
+  return c.bytes;
 }
 
 EINX_EXPORT int einx_detect(const float* score, const einx_detect_params* p, void* ws, float* nms_out, float* positions,
                             int32_t* indices, int32_t* counts, float* thr, int32_t* not_converged, void* stream) {
   return einx_detect_prezeroed(score, p, ws, nms_out, positions, indices, counts, thr, not_converged, 0, nullptr, stream);
-}
-
-// where einx_detect keeps its B x nms_iters pass flags inside `ws` (einx_extract has the score kernel zero them)
-int32_t* einx_detect_flags(const einx_detect_params* p, void* ws, int* n) {
-  const size_t map_bytes = (size_t)p->B * p->Hp * p->Wp * sizeof(float);
-  *n = p->radius > 0 ? p->B * p->nms_iters : 0;
-  return (int32_t*)((char*)ws + 2 * map_bytes);
 }
 
 int einx_detect_prezeroed(const float* score, const einx_detect_params* p, void* ws, float* nms_out, float* positions, int32_t* indices,
@@ -1056,14 +1058,12 @@ int einx_detect_prezeroed(const float* score, const einx_detect_params* p, void*
   EINX_CHECK_ARG((size_t)p->Hp * p->Wp < (1u << 30), "map too large");
   hipStream_t s = (hipStream_t)stream;
   const int N = p->Hp * p->Wp;
-  const size_t map_bytes = (size_t)p->B * N * sizeof(float);
-  float* buf0 = (float*)ws;
-  float* buf1 = (float*)((char*)ws + map_bytes);
-  int32_t* flags = (int32_t*)((char*)ws + 2 * map_bytes);
+  WsCarver c{(char*)ws};
+  const auto [buf0, buf1, flags, nflags] = einx_detect_carve(c, p);
   const float* cur = score;
   const int nIt = p->radius > 0 ? p->nms_iters : 0;
   if (nIt > 0) {
-    if (!flags_zeroed && hipMemsetAsync(flags, 0, (size_t)p->B * nIt * sizeof(int32_t), s) != hipSuccess) {
+    if (!flags_zeroed && hipMemsetAsync(flags, 0, (size_t)nflags * sizeof(int32_t), s) != hipSuccess) {
       einx_set_error("einx_detect: memset failed");
       return EINX_ERR_LAUNCH;
     }

@@ -33,6 +33,26 @@ void einx_set_error(const char* fmt, ...);
     }                                                                         \
   } while (0)
 
+// Workspaces are the caller's.  An op lists the regions of its workspace once, in one carve function that walks a WsCarver: from
+// a null base the walk only sizes (every pointer it hands out is null and `bytes` ends as the total), from the caller's pointer it
+// hands the regions out, so a *_ws_bytes query and its call cannot disagree.  Every region starts on a multiple of 256 bytes from
+// the base: the library's one rounding rule.  Host code; nothing on the device depends on it.
+struct WsCarver {
+  char* base;
+  size_t bytes = 0;
+  static size_t round_up(size_t n) { return (n + 255) & ~(size_t)255; }
+  // for a base that the caller need not align: the walk starts at the next multiple of 256, and the op's carve ends in slack(256)
+  static WsCarver aligned_up(void* ws) { return WsCarver{(char*)round_up((size_t)ws)}; }
+  template <typename T>
+  T* take(size_t count) {
+    T* p = (T*)here();
+    bytes += round_up(count * sizeof(T));
+    return p;
+  }
+  char* here() const { return base ? base + bytes : nullptr; }  // where the next region starts: the end of the last one
+  void slack(size_t n) { bytes += round_up(n); }                // bytes that belong to the size and to no region
+};
+
 // RAII timing scope around one kernel launch (or a group of launches) on `stream`; a no-op unless
 // einx_profile_enable(1) was called.  Usage: `EinxProfScope prof("lg_gemm", stream);` before the launch.
 class EinxProfScope {
@@ -135,7 +155,13 @@ __device__ __forceinline__ void einx_watch_tensor(const EinxWatch& w, int t, int
 // less per network on the latency-bound chain of a single-pair forward)
 int einx_score_map_zero(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int H, int W, int h0, int w0, int dilate,
                         int border, float* prob, float* score, int32_t* zero_ptr, int zero_n, float* crop, void* stream);
-int32_t* einx_detect_flags(const einx_detect_params* p, void* ws, int* n);
+// einx_detect's workspace (detect.hip); einx_extract nests it in its own and has the score kernel zero `flags`
+struct EinxDetectWs {
+  float *buf0, *buf1;  // [B,Hp,Wp] each: the NMS passes ping-pong between them
+  int32_t* flags;      // [B,nms_iters] pass flags
+  int nflags;          // how many of them a detection uses: 0 when radius == 0
+};
+EinxDetectWs einx_detect_carve(WsCarver& c, const einx_detect_params* p);
 // final_map != null: the cropped `nms` output is NOT written here; *final_map receives the buffer that holds the NMS fix-point (the caller
 // crops it: einx_extract, on the sampling launch)
 int einx_detect_prezeroed(const float* score, const einx_detect_params* p, void* ws, float* nms_out, float* positions, int32_t* indices,

@@ -465,12 +465,6 @@ __global__ void events_mask_kernel(const int32_t* cnt_all, int n, const int32_t*
 
 }  // namespace
 
-// workspace: [B][4] fp64 statistics | count image int32 [B,H,W] | min/max int32 [B][2] | device offsets int64 [B+1]
-EINX_EXPORT size_t einx_events_ws_bytes(int B, int H, int W) {
-  if (B <= 0 || H <= 0 || W <= 0) return 0;
-  return (size_t)B * 32 + (size_t)B * H * W * sizeof(int32_t) + (size_t)B * 8 + ((size_t)B + 1) * 8 + 256;
-}
-
 namespace {
 // The caller's offsets array is pageable memory that it may free as soon as the call returns, so it is first copied
 // (synchronously, a few hundred bytes) into a library-owned PINNED staging buffer; the asynchronous host-to-device
@@ -552,17 +546,48 @@ VoxGeom vox_geom(int bins, int H, int W) {
   g.bw = einx_cdiv(W, VOX_BANDS);
   return g;
 }
-size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-}  // namespace
 
 // workspace of einx_voxel_grid: per-slab statistics fp64 [B][nslab][3] | list lengths int32 [B][nslab][16][16] | device offsets
-// int64 [B+1] | event records float4 [N] | cell keys uint32 [N] | event lists uint32 [4 N]   (N = total_events = offsets_host[B])
+// int64 [B+1] | event records float4 [N] | cell keys uint32 [N] | event lists uint32 [4 N]   (N = total_events = offsets_host[B]),
+// and 256 bytes of slack that pay for rounding the caller's base up.  Returns the device offsets.
+int64_t* carve(WsCarver& c, VoxArgs& a, int B, const VoxGeom& g, int64_t N) {
+  a.part = c.take<double>((size_t)B * g.nslab * 3);
+  a.counts = c.take<int32_t>((size_t)B * g.nslab * VOX_BANDS * VOX_SEGS);
+  int64_t* offs = c.take<int64_t>((size_t)B + 1);
+  a.rec = c.take<float4>((size_t)N);
+  a.keys = c.take<uint32_t>((size_t)N);
+  a.lists = c.take<uint32_t>((size_t)N * 4);
+  c.slack(256);
+  return offs;
+}
+
+struct EventsWs {
+  int32_t *cnt, *mm;
+  int64_t* offs;
+};
+// workspace of einx_events_mask: [B][4] fp64 statistics (unused; part of the size) | count image int32 [B,H,W] | min/max int32
+// [B][2] | device offsets int64 [B+1], and 256 bytes of slack
+EventsWs carve(WsCarver& c, int B, int H, int W) {
+  c.take<double>((size_t)B * 4);
+  const EventsWs w{c.take<int32_t>((size_t)B * H * W), c.take<int32_t>((size_t)B * 2), c.take<int64_t>((size_t)B + 1)};
+  c.slack(256);
+  return w;
+}
+}  // namespace
+
+EINX_EXPORT size_t einx_events_ws_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  WsCarver c{nullptr};
+  carve(c, B, H, W);
+  return c.bytes;
+}
+
 EINX_EXPORT size_t einx_voxel_ws_bytes(int B, int bins, int H, int W, int64_t total_events) {
   if (B <= 0 || bins <= 0 || H <= 0 || W <= 0 || total_events < 0) return 0;
-  const VoxGeom g = vox_geom(bins, H, W);
-  return al256((size_t)B * g.nslab * 3 * sizeof(double)) + al256((size_t)B * g.nslab * VOX_BANDS * VOX_SEGS * sizeof(int32_t)) +
-         al256(((size_t)B + 1) * sizeof(int64_t)) + al256((size_t)total_events * sizeof(float4)) +
-         al256((size_t)total_events * sizeof(uint32_t)) + al256((size_t)total_events * 4 * sizeof(uint32_t)) + 256;
+  WsCarver c{nullptr};
+  VoxArgs a;
+  carve(c, a, B, vox_geom(bins, H, W), total_events);
+  return c.bytes;
 }
 
 EINX_EXPORT int einx_voxel_grid(const float* x, const float* y, const double* t, const float* p, const int64_t* offsets_host, int B,
@@ -578,24 +603,13 @@ EINX_EXPORT int einx_voxel_grid(const float* x, const float* y, const double* t,
   const int64_t N = offsets_host[B];
   EINX_CHECK_ARG(N >= 0 && N < ((int64_t)1 << 31), "bad event count");
   EINX_CHECK_ARG(ws_bytes >= einx_voxel_ws_bytes(B, bins, H, W, N), "workspace smaller than einx_voxel_ws_bytes");
-  char* wp = (char*)(((size_t)ws + 255) & ~(size_t)255);
+  WsCarver c = WsCarver::aligned_up(ws);
   VoxArgs a;
-  a.part = (double*)wp;
-  wp += al256((size_t)B * g.nslab * 3 * sizeof(double));
-  a.counts = (int32_t*)wp;
-  const size_t counts_bytes = (size_t)B * g.nslab * VOX_BANDS * VOX_SEGS * sizeof(int32_t);
-  wp += al256(counts_bytes);
-  int64_t* offs = (int64_t*)wp;
-  wp += al256(((size_t)B + 1) * sizeof(int64_t));
-  a.rec = (float4*)wp;
-  wp += al256((size_t)N * sizeof(float4));
-  a.keys = (uint32_t*)wp;
-  wp += al256((size_t)N * sizeof(uint32_t));
-  a.lists = (uint32_t*)wp;
+  int64_t* offs = carve(c, a, B, g, N);
   const long long mx = stage_offsets(offsets_host, B, offs, s);
   EINX_CHECK_ARG(mx != -1, "offsets must be non-decreasing");
   const bool lds_hist = g.nslab * VOX_BANDS <= VOX_PREP_BINS;  // else: counted with global atomics into zeroed counters
-  if (mx == -2 || (!lds_hist && hipMemsetAsync(a.counts, 0, counts_bytes, s) != hipSuccess)) {
+  if (mx == -2 || (!lds_hist && hipMemsetAsync(a.counts, 0, (char*)offs - (char*)a.counts, s) != hipSuccess)) {
     einx_set_error("einx_voxel_grid: memset / copy failed");
     return EINX_ERR_LAUNCH;
   }
@@ -636,9 +650,8 @@ EINX_EXPORT int einx_events_mask(const float* x, const float* y, const int64_t* 
   EINX_CHECK_ARG(offsets_host[B] == 0 || (x && y), "null event arrays");  // (no event at all: all-false masks)
   hipStream_t s = (hipStream_t)stream;
   const int n = H * W;
-  int32_t* cnt = (int32_t*)((char*)ws + (size_t)B * 32);
-  int32_t* mm = (int32_t*)((char*)ws + (size_t)B * 32 + (size_t)B * n * sizeof(int32_t));
-  int64_t* offs = (int64_t*)(((size_t)((char*)ws + (size_t)B * 32 + (size_t)B * n * sizeof(int32_t) + (size_t)B * 8) + 7) & ~(size_t)7);
+  WsCarver c{(char*)ws};
+  const auto [cnt, mm, offs] = carve(c, B, H, W);
   const long long mx = stage_offsets(offsets_host, B, offs, s);
   EINX_CHECK_ARG(mx != -1, "offsets must be non-decreasing");
   if (mx == -2 || hipMemsetAsync(cnt, 0, (size_t)B * n * sizeof(int32_t), s) != hipSuccess) {

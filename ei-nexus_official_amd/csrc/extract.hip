@@ -32,8 +32,6 @@ struct einx_extractor {
 
 namespace {
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Plan {
   int Hp, Wp, h0, w0;       // padded size, top/left pad
   int hc, wc;               // head resolution
@@ -198,16 +196,38 @@ EINX_EXPORT int einx_extract_shapes(const einx_extractor* e, int H, int W, einx_
 // is B x nms_iters words of the workspace)
 static inline int nms_budget(int nms_iters) { return nms_iters > 0 ? nms_iters : 8; }
 
+namespace {
+struct ExtractWs {
+  float* buf[2];       // the backbone's ping-pong activations
+  float *head, *head2; // scratch of the heads' hidden layers; head2 == head where the size holds one
+  void* det_ws;        // the detector's workspace, nested: `det` is its carve
+  EinxDetectWs det;
+};
+
+// einx_extract's workspace; einx_extract_ws_bytes walks it from a null base.  The second head scratch is a region whenever
+// fork_heads() says so, which depends only on the arguments that size the workspace: whether a call then runs the descriptor
+// branch beside the detector branch (and uses it) is decided at run time, and moves no region.
+ExtractWs carve(WsCarver& c, const einx_extractor* e, const Plan& pl, const einx_detect_params* dp, int B) {
+  ExtractWs w;
+  w.buf[0] = c.take<float>(pl.buf_elems[0] * B);
+  w.buf[1] = c.take<float>(pl.buf_elems[1] * B);
+  w.head = c.take<float>(pl.head_elems * B);
+  w.head2 = fork_heads(e, pl, B) ? c.take<float>(pl.head_elems * B) : w.head;
+  w.det_ws = c.here();
+  w.det = einx_detect_carve(c, dp);
+  c.slack(256);
+  return w;
+}
+}  // namespace
+
 EINX_EXPORT size_t einx_extract_ws_bytes(const einx_extractor* e, int B, int H, int W, int cap, int nms_iters) {
   Plan pl;
   if (!e || B <= 0 || !make_plan(e, H, W, &pl)) return 0;
   einx_detect_params p;
   detect_params(e, pl, B, H, W, cap > 0 ? cap : 1, nms_budget(nms_iters), &p);
-  size_t bytes = 0;
-  bytes += align256(pl.buf_elems[0] * B * sizeof(float)) + align256(pl.buf_elems[1] * B * sizeof(float));
-  bytes += align256(pl.head_elems * B * sizeof(float)) * (fork_heads(e, pl, B) ? 2 : 1);
-  bytes += align256(einx_detect_ws_bytes(&p));
-  return bytes + 256;
+  WsCarver c{nullptr};
+  carve(c, e, pl, &p, B);
+  return c.bytes;
 }
 
 EINX_EXPORT int einx_extract(const einx_extractor* e, float* in, const uint8_t* mask, int B, int H, int W, int nms_iters, void* ws,
@@ -228,26 +248,17 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   EINX_CHECK_ARG(make_plan(e, H, W, &pl), "image size does not fit the network's pooling / cell size");
   EINX_CHECK_ARG(e->d.cell == 1 || (o->coarse && o->raw_cl), "cell-8 networks need the coarse / raw_cl outputs");
   EINX_CHECK_ARG(ws_bytes >= einx_extract_ws_bytes(e, B, H, W, o->cap, nms_iters), "workspace smaller than einx_extract_ws_bytes for these arguments");
-  char* p = (char*)ws;
-  float* buf[2];
-  buf[0] = (float*)p;
-  p += align256(pl.buf_elems[0] * B * sizeof(float));
-  buf[1] = (float*)p;
-  p += align256(pl.buf_elems[1] * B * sizeof(float));
-  float* head = (float*)p;
-  p += align256(pl.head_elems * B * sizeof(float));
+  einx_detect_params dp;
+  detect_params(e, pl, B, H, W, o->cap, nms_budget(nms_iters), &dp);
+  WsCarver c{(char*)ws};
+  const ExtractWs wk = carve(c, e, pl, &dp, B);
   // (while einx_profile_enable(1) records per-launch times the branches stay in line: its numbers are kernels ALONE on the chip)
   bool fork = fork_heads(e, pl, B) && !einx_profile_active();
   {  // a fork nested inside a caller's own fork crashes hipStreamEndCapture (ROCm 7.2): under capture the branches stay in line
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (fork && hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) fork = false;
   }
-  float* head2 = head;  // the descriptor head's own scratch when the two branches run concurrently
-  if (fork) {
-    head2 = (float*)p;
-    p += align256(pl.head_elems * B * sizeof(float));
-  }
-  void* det_ws = p;
+  float* const head2 = fork ? wk.head2 : wk.head;  // the descriptor head's own scratch when the two branches run concurrently
   int rc;
   if (e->d.input_div != 0.0f && e->d.input_div != 1.0f) {  // SuperPointv1: `image /= 255.0` in place on the caller's tensor
     rc = einx_div_inplace(in, (size_t)B * e->backbone.front().cin * H * W, e->d.input_div, stream);
@@ -260,7 +271,7 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   int first = 0;
   // the first two layers of a 1-channel network as one launch (large launches only: einx_conv_first_two_fused_ok)
   if (nb >= 2 && 1 == einx_conv_first_two_fused_ok(&e->backbone[0], &e->backbone[1], B, pl.Hp, pl.Wp)) {
-    float* out = (2 < nb) ? buf[1] : o->feats;
+    float* out = (2 < nb) ? wk.buf[1] : o->feats;
     if ((rc = einx_conv_first_two_fused(in, B, H, W, pl.h0, pl.w0, pl.Hp, pl.Wp, &e->backbone[0], &e->backbone[1], out, stream))) return rc;
     if (e->backbone[1].pool) {
       h /= 2;
@@ -271,7 +282,7 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   }
   for (int i = first; i < nb; ++i) {
     const einx_conv_desc& c = e->backbone[i];
-    float* out = (i + 1 < nb) ? buf[i & 1] : o->feats;
+    float* out = (i + 1 < nb) ? wk.buf[i & 1] : o->feats;
     if (i == 0) rc = einx_conv_block(cur, B, H, W, pl.h0, pl.w0, pl.Hp, pl.Wp, &c, out, stream);
     else rc = einx_conv_block(cur, B, h, w, 0, 0, h, w, &c, out, stream);
     if (rc) return rc;
@@ -296,11 +307,11 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   // single images: the two heads' first layers as one launch into `head` (det channels first); each head's second layer then reads
   // its slice (one image: a channel slice is contiguous)
   const bool merged = e->has_merged && B == 1;
-  if (merged && (rc = einx_conv_block(o->feats, B, h, w, 0, 0, h, w, &e->merged, head, stream))) return rc;
-  const float* desc_in = head + (size_t)e->det.front().cout * h * w;
+  if (merged && (rc = einx_conv_block(o->feats, B, h, w, 0, 0, h, w, &e->merged, wk.head, stream))) return rc;
+  const float* desc_in = wk.head + (size_t)e->det.front().cout * h * w;
   auto det_branch = [&](void* st) -> int {
-    if (merged) return einx_conv_block(head, B, h, w, 0, 0, h, w, &e->det[1], o->logits, st);
-    return run_head(e->det, head, o->logits, st);
+    if (merged) return einx_conv_block(wk.head, B, h, w, 0, 0, h, w, &e->det[1], o->logits, st);
+    return run_head(e->det, wk.head, o->logits, st);
   };
   // descriptor branch: head convs + the dense by-product that depends on `raw` only
   auto desc_branch = [&](void* st) -> int {
@@ -335,16 +346,12 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
     if ((rc = det_branch(stream))) return rc;
     if ((rc = desc_branch(stream))) return rc;
   }
-  einx_detect_params dp;
-  detect_params(e, pl, B, H, W, o->cap, nms_budget(nms_iters), &dp);
   // the score kernel also zeroes the detection's NMS pass flags (no memset launch) when it has a thread per flag word
-  int nflags = 0;
-  int32_t* flags = einx_detect_flags(&dp, det_ws, &nflags);
   const int C_det = e->det.back().cout;
   const long score_threads = (long)(C_det == 65 ? einx_cdiv(B * h * w, 32) : einx_cdiv(B * h * w, 256)) * 256;
-  const bool zero_in_score = nflags > 0 && nflags <= score_threads;
+  const bool zero_in_score = wk.det.nflags > 0 && wk.det.nflags <= score_threads;
   rc = einx_score_map_zero(o->logits, B, C_det, h, w, mask, H, W, pl.h0, pl.w0, e->d.dilate_mask, e->d.border, o->prob, o->score,
-                           zero_in_score ? flags : nullptr, zero_in_score ? nflags : 0, o->score_crop, stream);
+                           zero_in_score ? wk.det.flags : nullptr, zero_in_score ? wk.det.nflags : 0, o->score_crop, stream);
   if (rc) {
     if (sd) (void)hipStreamWaitEvent((hipStream_t)stream, sd->join, 0);
     return rc;
@@ -352,7 +359,7 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   // the cropped `nms` output is written by extra workgroups of the sampling launch below (one launch less): the detection only
   // reports which buffer holds the NMS fix-point
   const float* nms_map = nullptr;
-  rc = einx_detect_prezeroed(o->score, &dp, det_ws, o->nms, o->positions, o->indices, o->counts, o->thr, o->not_converged, zero_in_score ? 1 : 0,
+  rc = einx_detect_prezeroed(o->score, &dp, wk.det_ws, o->nms, o->positions, o->indices, o->counts, o->thr, o->not_converged, zero_in_score ? 1 : 0,
                              o->nms ? &nms_map : nullptr, stream);
   if (sd && hipStreamWaitEvent((hipStream_t)stream, sd->join, 0) != hipSuccess && !rc) {  // join before the sampler reads `raw`
     einx_set_error("einx_extract: join failed");

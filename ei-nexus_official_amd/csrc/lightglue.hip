@@ -905,8 +905,6 @@ __global__ void lg_normalize_kpts_kernel(const float* kpts, int cols, size_t tot
   for (int c = 2; c < out_cols; ++c) out[t * out_cols + c] = 0.0f;
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Side {
   const float* kpts;
   const float* desc;
@@ -915,49 +913,34 @@ struct Side {
   float *x, *enc, *q, *k, *v, *ctx, *msg, *h, *cert, *dust;
 };
 
-// d: descriptor_dim, dh: head dim -- buffers [tokens, d] (x, q, k, v, ctx, msg), [tokens, 2 dh] (enc), [tokens, 2 d] (h)
-size_t side_bytes(int B, int cap, int d, int dh) {
-  const size_t tok = (size_t)B * cap;
-  return al(tok * d * 4) + al(tok * 2 * dh * 4) + 3 * al(tok * d * 4) + 2 * al(tok * d * 4) + al(tok * 2 * d * 4) + 2 * al(tok * 4);
-}
-
-char* carve_side(Side& s, char* p, int B, int cap, int d, int dh) {
-  const size_t tok = (size_t)B * cap;
-  auto take = [&](size_t bytes) { float* r = (float*)p; p += al(bytes); return r; };
-  s.x = take(tok * d * 4);
-  s.enc = take(tok * 2 * dh * 4);
-  s.q = take(tok * d * 4);
-  s.k = take(tok * d * 4);
-  s.v = take(tok * d * 4);
-  s.ctx = take(tok * d * 4);
-  s.msg = take(tok * d * 4);
-  s.h = take(tok * 2 * d * 4);
-  s.cert = take(tok * 4);
-  s.dust = take(tok * 4);
-  return p;
-}
-
-// Both sides stacked: every buffer is [2B, cap, width], side 0 = entries 0..B-1, side 1 = entries B..2B-1.  LightGlue applies
-// the same weights to both sides, so every per-side launch becomes one launch over 2B entries (cross attention reads
-// the partner entry's keys / values); s0 / s1 stay views of the halves.  Never larger than two separate sides.
-char* carve_stacked(Side& s0, Side& s1, char* p, int B, int cap, int d, int dh) {
-  const size_t tok = (size_t)B * cap;
-  auto take = [&](size_t width, float*& a0, float*& a1) {
-    a0 = (float*)p;
-    a1 = a0 + tok * width;
-    p += al(2 * tok * width * 4);
-  };
-  take(d, s0.x, s1.x);
-  take(2 * dh, s0.enc, s1.enc);
-  take(d, s0.q, s1.q);
-  take(d, s0.k, s1.k);
-  take(d, s0.v, s1.v);
-  take(d, s0.ctx, s1.ctx);
-  take(d, s0.msg, s1.msg);
-  take(2 * d, s0.h, s1.h);
-  take(1, s0.cert, s1.cert);
-  take(1, s0.dust, s1.dust);
-  return p;
+// einx_lightglue's workspace (einx_lg_ws_bytes_heads walks it from a null base); d: descriptor_dim, dh: head dim.  Per side the
+// buffers [tokens, d] (x, q, k, v, ctx, msg), [tokens, 2 dh] (enc), [tokens, 2 d] (h), [tokens] (cert, dust); then the stacked
+// counts, the assignment stage's MNN workspace (match_tiles.h) and 1024 bytes of slack.  Stacked (equal capacities): every buffer
+// is ONE array [2B, cap, width], side 0 = entries 0..B-1, side 1 = entries B..2B-1.  LightGlue applies the same weights to both
+// sides, so every per-side launch becomes one launch over 2B entries (cross attention reaches the partner entry B entries on);
+// s0 / s1 stay views of the halves.  The array lies in the two regions that its halves would take apart, side 1 directly behind
+// side 0's last element: rounding each half up never gives less than the whole needs, so the size does not depend on `stacked`.
+void carve(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, bool stacked, int B, int cap0, int cap1, int d, int dh) {
+  const struct {
+    float* Side::*buf;
+    size_t width;  // floats per token
+  } bufs[] = {{&Side::x, (size_t)d},   {&Side::enc, (size_t)2 * dh}, {&Side::q, (size_t)d},     {&Side::k, (size_t)d}, {&Side::v, (size_t)d},
+              {&Side::ctx, (size_t)d}, {&Side::msg, (size_t)d},      {&Side::h, (size_t)2 * d}, {&Side::cert, 1},      {&Side::dust, 1}};
+  if (stacked) {
+    for (const auto& b : bufs) {
+      const size_t n = (size_t)B * cap0 * b.width;
+      float* both = c.take<float>(n);
+      c.take<float>(n);
+      s0.*b.buf = both;
+      s1.*b.buf = both ? both + n : nullptr;
+    }
+  } else {
+    for (const auto& b : bufs) s0.*b.buf = c.take<float>((size_t)B * cap0 * b.width);
+    for (const auto& b : bufs) s1.*b.buf = c.take<float>((size_t)B * cap1 * b.width);
+  }
+  cnt2 = c.take<int32_t>((size_t)2 * B);  // the counts of both sides as [2B] (stacked only)
+  einx_match::carve(c, a, B, cap0, cap1);
+  c.slack(1024);
 }
 
 __global__ void lg_stack_counts_kernel(const int32_t* n, const int32_t* m, int B, int32_t* out) {
@@ -1180,7 +1163,12 @@ EINX_EXPORT size_t einx_lg_ws_bytes_heads(int B, int cap0, int cap1, int d, int 
   Dims dm;
   if (B <= 0 || cap0 <= 0 || cap1 <= 0 || !dims_of(d, heads, dm)) return 0;
   (void)input_dim;
-  return side_bytes(B, cap0, d, dm.dh) + side_bytes(B, cap1, d, dm.dh) + einx_mnn_ws_bytes(B, cap0, cap1) + al((size_t)2 * B * 4) + 1024;
+  Side s0, s1;
+  int32_t* cnt2;
+  MnnArgs a;
+  WsCarver c{nullptr};
+  carve(c, s0, s1, cnt2, a, cap0 == cap1, B, cap0, cap1, d, dm.dh);
+  return c.bytes;
 }
 
 EINX_EXPORT size_t einx_lg_ws_bytes(int B, int cap0, int cap1, int d, int input_dim) {  // 64-wide heads (the LightGlue default)
@@ -1213,23 +1201,19 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
   s1.desc = desc1;
   s1.cnt = m;
   s1.cap = cap1;
-  char* p = (char*)ws;
   // equal capacities (every shipped configuration): the two sides are stacked and every layer runs ONCE over 2B entries --
   // half the launches, and at small batch twice the workgroups per launch (a single pair: 8.0 -> see profiles/r03_notes.md)
   const bool stacked = cap0 == cap1;
+  int32_t* cnt2;
+  MnnArgs a;
+  WsCarver c{(char*)ws};
+  carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, D, dm.dh);
   Side sb{};
   if (stacked) {
-    p = carve_stacked(s0, s1, p, B, cap0, D, dm.dh);
-    int32_t* cnt2 = (int32_t*)p;
-    p += al((size_t)2 * B * 4);
     hipLaunchKernelGGL(lg_stack_counts_kernel, dim3((unsigned)einx_cdiv(2 * B, 256)), dim3(256), 0, st, n, m, B, cnt2);
     sb = s0;
     sb.cnt = cnt2;
-  } else {
-    p = carve_side(s0, p, B, cap0, D, dm.dh);
-    p = carve_side(s1, p, B, cap1, D, dm.dh);
   }
-  void* mnn_ws = p;
   Side* sides[2] = {&s0, &s1};
   Side* run[2] = {stacked ? &sb : &s0, &s1};  // what the shared-weight stages iterate over
   const int nrun = stacked ? 1 : 2, Br = stacked ? 2 * B : B;
@@ -1331,7 +1315,6 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
       LG_CHECK(0);
     }
   }
-  MnnArgs a;
   a.d0 = s0.q;
   a.d1 = s1.q;
   a.n = n;
@@ -1339,27 +1322,12 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
   a.cap0 = cap0;
   a.cap1 = cap1;
   a.D = D;
-  a.nc64 = einx_cdiv(cap1, 64);
-  a.nr64 = einx_cdiv(cap0, WROWS);
-  char* q = (char*)mnn_ws;
-  a.rowkey = (unsigned long long*)q;
-  q += al((size_t)B * cap0 * 8);
-  a.colkey = (unsigned long long*)q;
-  q += al((size_t)B * cap1 * 8);
-  a.rowstat = (float*)q;
-  q += al((size_t)B * cap0 * a.nc64 * 8);
-  a.colstat = (float*)q;
-  q += al((size_t)B * cap1 * a.nr64 * 8);
-  a.rowlse = (float*)q;
-  q += al((size_t)B * cap0 * 8);
-  a.collse = (float*)q;
   a.la = la;
   a.cert0 = s0.cert;
   a.cert1 = s1.cert;
   a.dust0 = s0.dust;
   a.dust1 = s1.dust;
-  const size_t keybytes = al((size_t)B * cap0 * 8) + al((size_t)B * cap1 * 8);
-  if (hipMemsetAsync(mnn_ws, 0, keybytes, st) != hipSuccess) {
+  if (hipMemsetAsync(a.rowkey, 0, (char*)a.rowstat - (char*)a.rowkey, st) != hipSuccess) {  // rowkey | colkey
     einx_set_error("einx_lightglue: memset failed");
     return EINX_ERR_LAUNCH;
   }

@@ -638,7 +638,23 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(const float* s0, cons
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// The matcher's workspace: fills a's workspace pointers and the chunk counts that shape them.  einx_mnn_ws_bytes is this walk
+// from a null base; mnn_impl and einx_lightglue's assignment stage (whose workspace nests this one) walk it from theirs.  The
+// order is relied on: rowkey | colkey are zeroed by one memset that ends where rowstat begins, row2 | col2 by one that ends where
+// the walk does.
+void carve(WsCarver& c, MnnArgs& a, int B, int cap0, int cap1) {
+  const size_t n0 = (size_t)B * cap0, n1 = (size_t)B * cap1;
+  a.nc64 = einx_cdiv(cap1, 64);
+  a.nr64 = einx_cdiv(cap0, WROWS);
+  a.rowkey = c.take<unsigned long long>(n0);
+  a.colkey = c.take<unsigned long long>(n1);
+  a.rowstat = c.take<float>(n0 * a.nc64 * 2);
+  a.colstat = c.take<float>(n1 * a.nr64 * 2);
+  a.rowlse = c.take<float>(n0 * 2);
+  a.collse = c.take<float>(n1 * 2);
+  a.row2 = c.take<unsigned>(n0);  // second-neighbour keys (einx_mnn_thresh)
+  a.col2 = c.take<unsigned>(n1);
+}
 
 
 }  // namespace

@@ -276,15 +276,27 @@ __global__ __launch_bounds__(256) void metric_finalize_kernel(const MetArgs a) {
   }
 }
 
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+// einx_pair_metrics' workspace, and 256 bytes of slack.  icnt is zeroed by a memset that ends where near0 begins.
+void carve(WsCarver& c, MetArgs& a, const einx_metric_params* p) {
+  const size_t n0 = (size_t)p->B * p->cap0, n1 = (size_t)p->B * p->cap1;
+  a.tw0 = c.take<float>(n0 * 2);
+  a.p1 = c.take<float>(n1 * 2);
+  a.keep0 = c.take<uint8_t>(n0);
+  a.keep1 = c.take<uint8_t>(n1);
+  a.icnt = c.take<int32_t>((size_t)p->B * ICNT);
+  a.near0 = c.take<float>(n0 * 3);
+  a.near1 = c.take<float>(n1 * 3);
+  c.slack(256);
+}
 
 }  // namespace
 
 EINX_EXPORT size_t einx_metrics_ws_bytes(const einx_metric_params* p) {
   if (!p || p->B <= 0) return 0;
-  const size_t B = p->B;
-  return al(B * p->cap0 * 8) + al(B * p->cap1 * 8) + al(B * p->cap0) + al(B * p->cap1) + al(B * ICNT * 4) + al(B * p->cap0 * 12) +
-         al(B * p->cap1 * 12) + 256;
+  WsCarver c{nullptr};
+  MetArgs a;
+  carve(c, a, p);
+  return c.bytes;
 }
 
 EINX_EXPORT int einx_pair_metrics(const einx_metric_params* p, const float* kpts0, const float* kpts1, const float* desc0, const float* desc1,
@@ -308,22 +320,10 @@ EINX_EXPORT int einx_pair_metrics(const einx_metric_params* p, const float* kpts
   a.nmatch = nmatch;
   a.p = *p;
   a.out = out;
-  char* q = (char*)ws;
   const size_t B = p->B;
-  a.tw0 = (float*)q;
-  q += al(B * p->cap0 * 8);
-  a.p1 = (float*)q;
-  q += al(B * p->cap1 * 8);
-  a.keep0 = (uint8_t*)q;
-  q += al(B * p->cap0);
-  a.keep1 = (uint8_t*)q;
-  q += al(B * p->cap1);
-  a.icnt = (int32_t*)q;
-  q += al(B * ICNT * 4);
-  a.near0 = (float*)q;
-  q += al(B * p->cap0 * 12);
-  a.near1 = (float*)q;
-  if (hipMemsetAsync(a.icnt, 0, al(B * ICNT * 4), s) != hipSuccess) {
+  WsCarver c{(char*)ws};
+  carve(c, a, p);
+  if (hipMemsetAsync(a.icnt, 0, (char*)a.near0 - (char*)a.icnt, s) != hipSuccess) {
     einx_set_error("einx_pair_metrics: memset failed");
     return EINX_ERR_LAUNCH;
   }

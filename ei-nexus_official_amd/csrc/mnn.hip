@@ -16,13 +16,10 @@ using namespace einx_gemm;
 
 EINX_EXPORT size_t einx_mnn_ws_bytes(int B, int cap0, int cap1) {
   if (B <= 0 || cap0 <= 0 || cap1 <= 0) return 0;
-  const size_t nc64 = (size_t)einx_cdiv(cap1, 64), nr64 = (size_t)einx_cdiv(cap0, WROWS);
-  size_t bytes = 0;
-  bytes += align256((size_t)B * cap0 * 8) + align256((size_t)B * cap1 * 8);
-  bytes += align256((size_t)B * cap0 * nc64 * 8) + align256((size_t)B * cap1 * nr64 * 8);
-  bytes += align256((size_t)B * cap0 * 8) + align256((size_t)B * cap1 * 8);
-  bytes += align256((size_t)B * cap0 * 4) + align256((size_t)B * cap1 * 4);  // second-neighbour keys (einx_mnn_thresh)
-  return bytes;
+  WsCarver c{nullptr};
+  MnnArgs a;
+  carve(c, a, B, cap0, cap1);
+  return c.bytes;
 }
 
 EINX_EXPORT int einx_mnn(const float* desc0, const int32_t* n, int cap0, const float* desc1, const int32_t* m, int cap1, int B, int D,
@@ -78,33 +75,16 @@ int mnn_impl(const float* desc0, const int32_t* n, int cap0, const float* desc1,
   a.cap0 = cap0;
   a.cap1 = cap1;
   a.D = D;
-  a.nc64 = einx_cdiv(cap1, 64);
-  a.nr64 = einx_cdiv(cap0, WROWS);
-  char* p = (char*)ws;
-  a.rowkey = (unsigned long long*)p;
-  p += align256((size_t)B * cap0 * 8);
-  a.colkey = (unsigned long long*)p;
-  p += align256((size_t)B * cap1 * 8);
-  a.rowstat = (float*)p;
-  p += align256((size_t)B * cap0 * a.nc64 * 8);
-  a.colstat = (float*)p;
-  p += align256((size_t)B * cap1 * a.nr64 * 8);
-  a.rowlse = (float*)p;
-  p += align256((size_t)B * cap0 * 8);
-  a.collse = (float*)p;
-  p += align256((size_t)B * cap1 * 8);
-  a.row2 = (unsigned*)p;
-  p += align256((size_t)B * cap0 * 4);
-  a.col2 = (unsigned*)p;
+  WsCarver c{(char*)ws};
+  carve(c, a, B, cap0, cap1);
   a.la = la;
   a.cert0 = a.cert1 = a.dust0 = a.dust1 = nullptr;
-  const size_t keybytes = align256((size_t)B * cap0 * 8) + align256((size_t)B * cap1 * 8);
-  if (hipMemsetAsync(ws, 0, keybytes, s) != hipSuccess) {
+  if (hipMemsetAsync(a.rowkey, 0, (char*)a.rowstat - (char*)a.rowkey, s) != hipSuccess) {  // rowkey | colkey
     einx_set_error("einx_mnn: memset failed");
     return EINX_ERR_LAUNCH;
   }
   const bool thresh = use_ratio || use_dist;
-  if (use_ratio && hipMemsetAsync(a.row2, 0, align256((size_t)B * cap0 * 4) + align256((size_t)B * cap1 * 4), s) != hipSuccess) {
+  if (use_ratio && hipMemsetAsync(a.row2, 0, c.here() - (char*)a.row2, s) != hipSuccess) {  // row2 | col2
     einx_set_error("einx_mnn: memset failed");
     return EINX_ERR_LAUNCH;
   }

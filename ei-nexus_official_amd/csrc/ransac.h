@@ -1,7 +1,7 @@
 // The RANSAC skeleton shared by the estimators (pose.hip: DESIGN.md 8b, homography.hip: 8c): the counter-based generator and its
-// distinct-index draws, the workspace carver, the selection scan with OpenCV's shrinking iteration bound and the state it keeps
-// between rounds, the host's round schedule, and the cooperative Gauss-Jordan elimination.  An estimator adds its minimal solver,
-// its error function, its inlier count and its epilogue.
+// distinct-index draws, the selection scan with OpenCV's shrinking iteration bound and the state it keeps between rounds, the
+// host's round schedule, and the cooperative Gauss-Jordan elimination.  An estimator adds its minimal solver, its error function,
+// its inlier count, its epilogue and the carve of its workspace (WsCarver: einx_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,19 +38,6 @@ __device__ __forceinline__ bool ransac_draw(unsigned long long seed, int it, int
   }
   return true;
 }
-
-// Walks a workspace region by region, each aligned to 256 bytes.  From a null base it only sizes (every pointer it hands out is
-// null and `bytes` ends as the total), so an estimator lists its regions once, in one function that serves *_ws_bytes and the call.
-struct WsCarver {
-  char* base;
-  size_t bytes = 0;
-  template <typename T>
-  T* take(size_t count) {
-    T* p = base ? (T*)(base + bytes) : nullptr;
-    bytes += (count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
 
 // RANSACUpdateNumIters for a model of M points, with (1 - ep)^M as M - 1 products
 template <int M>

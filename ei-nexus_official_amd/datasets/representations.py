@@ -125,7 +125,7 @@ def events_to_voxel_grid_batch(events_list, input_size, normalize=True, device="
     x, y, t, p, offs = packed if packed is not None else _pack(events_list, device)
     L = N.lib()
     grid = torch.empty((B, bins, H, W), dtype=torch.float32, device=device)
-    ws = torch.empty(L.einx_voxel_ws_bytes(B, bins, H, W, int(offs[-1])), dtype=torch.uint8, device=device)
+    ws = N._workspace(L.einx_voxel_ws_bytes(B, bins, H, W, int(offs[-1])), device)
     check(L.einx_voxel_grid(N._ptr(x), N._ptr(y), N._ptr(t), N._ptr(p), offs.ctypes.data_as(ctypes.c_void_p), B, bins, H, W, int(normalize),
                             N._ptr(grid), N._ptr(ws), ws.numel(), N._stream(grid)), "einx_voxel_grid")
     return grid
@@ -144,7 +144,7 @@ def events_mask_batch(events_list, resolution, device="cuda", packed=None):
     x, y, _, _, offs = packed if packed is not None else _pack(events_list, device)
     L = N.lib()
     mask = torch.empty((B, 1, H, W), dtype=torch.uint8, device=device)
-    ws = torch.empty(L.einx_events_ws_bytes(B, H, W), dtype=torch.uint8, device=device)
+    ws = N._workspace(L.einx_events_ws_bytes(B, H, W), device)
     check(L.einx_events_mask(N._ptr(x), N._ptr(y), offs.ctypes.data_as(ctypes.c_void_p), B, H, W, N._ptr(ws), N._ptr(mask), N._stream(mask)),
           "einx_events_mask")
     return mask.view(torch.bool)
