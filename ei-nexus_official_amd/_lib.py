@@ -142,6 +142,15 @@ SIGNATURES = {
     "einx_voxel_grid": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
     "einx_events_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_time_surface_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_int64]),
+    "einx_event_stack_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_int64]),
+    "einx_distance_map_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_int64]),
+    "einx_time_surface": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    "einx_event_stack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
+    "einx_distance_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
     "einx_events_pack": (c_int, [ctypes.POINTER(EventArrays), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "einx_metrics_ws_bytes": (c_size_t, [ctypes.POINTER(MetricParams)]),
     "einx_pair_metrics": (c_int, [ctypes.POINTER(MetricParams)] + [c_void_p] * 13),

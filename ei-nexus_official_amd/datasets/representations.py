@@ -1,6 +1,7 @@
 """Event representations on the GPU, same names and argument meaning as the
-reference's datasets/representations.py:67-124 (`events_to_voxel_grid`) and the events mask built in
-datasets/visualize.py:23-50 + test_events-image_same-time.py:137.  Events arrive as the reference's
+reference's datasets/representations.py (`events_to_voxel_grid` :67-124, `events_to_time_surface` :26-63,
+`events_to_event_stack` :178-212, `events_to_distance_map` :216-248; DESIGN.md 8d for the last three) and the events
+mask built in datasets/visualize.py:23-50 + test_events-image_same-time.py:137.  Events arrive as the reference's
 dict of numpy arrays {"x","y","t","p"}; the result stays on the device, ready for EIM.forward."""
 import ctypes
 
@@ -150,23 +151,94 @@ def events_mask_batch(events_list, resolution, device="cuda", packed=None):
     return mask.view(torch.bool)
 
 
-def events_representation_batch(events_list, input_size, normalize=True, device="cuda", stage=None, on_stage_stream=False):
-    """voxel grids [B,bins,H,W] and events masks [B,1,H,W] of B samples from ONE host-side packing and upload of the raw
+def _rep_batch(op, events_list, input_size, device, packed):
+    """one of the three ops of csrc/event_reps.hip on B samples -> [B,bins,H,W] fp32"""
+    bins, H, W = (int(v) for v in input_size)
+    B = len(events_list)
+    x, y, t, p, offs = packed if packed is not None else _pack(events_list, device)
+    L = N.lib()
+    out = torch.empty((B, bins, H, W), dtype=torch.float32, device=device)
+    nbytes = getattr(L, f"einx_{op}_ws_bytes")(B, bins, H, W, int(offs[-1]))
+    if nbytes == 0:
+        raise ValueError(f"einx_{op}: unsupported shape B={B}, input_size={(bins, H, W)}")
+    ws = N._workspace(nbytes, device)
+    check(getattr(L, f"einx_{op}")(N._ptr(x), N._ptr(y), N._ptr(t), N._ptr(p), offs.ctypes.data_as(ctypes.c_void_p), B, bins, H, W,
+                                   N._ptr(out), N._ptr(ws), ws.numel(), N._stream(out)), f"einx_{op}")
+    return out
+
+
+def events_to_time_surface_batch(events_list, input_size, device="cuda", packed=None):
+    """list of B event dicts -> time surfaces [B,bins,H,W] (fp32, on `device`); packed: as events_to_voxel_grid_batch"""
+    return _rep_batch("time_surface", events_list, input_size, device, packed)
+
+
+def events_to_event_stack_batch(events_list, input_size, device="cuda", packed=None):
+    """list of B event dicts -> event stacks [B,bins,H,W] (fp32, on `device`)"""
+    return _rep_batch("event_stack", events_list, input_size, device, packed)
+
+
+def events_to_distance_map_batch(events_list, input_size, device="cuda", packed=None):
+    """list of B event dicts -> event distance maps [B,bins,H,W] (fp32, on `device`)"""
+    return _rep_batch("distance_map", events_list, input_size, device, packed)
+
+
+def events_to_time_surface(events, input_size, device="cuda"):
+    """Drop-in for datasets/representations.py:26-63 (one sample): returns [bins,H,W]; the `events` dict is not modified.
+    Events outside the image are dropped where numpy would wrap a negative index or raise."""
+    return events_to_time_surface_batch([events], input_size, device)[0]
+
+
+def events_to_event_stack(events, input_size, device="cuda"):
+    """Drop-in for datasets/representations.py:178-212 (one sample): returns [bins,H,W]; the `events` dict is not modified."""
+    return events_to_event_stack_batch([events], input_size, device)[0]
+
+
+def events_to_distance_map(events, input_size, device="cuda"):
+    """Drop-in for datasets/representations.py:216-248 (one sample): returns [bins,H,W]; the `events` dict is not modified.
+    The 3x3 chamfer distance in 16.16 fixed point as DESIGN.md 8d writes it down, not bit parity with cv2.distanceTransform."""
+    return events_to_distance_map_batch([events], input_size, device)[0]
+
+
+# the reference's `representation_type` strings (datasets/MVSEC.py:706-718, datasets/EC.py:236-248) -> batch functions
+REPRESENTATIONS = {
+    "VoxelGrid": events_to_voxel_grid_batch,
+    "TimeSurface": events_to_time_surface_batch,
+    "EventStack": events_to_event_stack_batch,
+    "EventDistanceMap": events_to_distance_map_batch,
+}
+
+
+def build_representation(representation_type):
+    """the batch function (events_list, input_size, device=..., packed=...) of a `representation_type` string"""
+    try:
+        return REPRESENTATIONS[representation_type]
+    except (KeyError, TypeError):
+        raise ValueError(f"Unsupported representation type '{representation_type}'.") from None
+
+
+def events_representation_batch(events_list, input_size, normalize=True, device="cuda", stage=None, on_stage_stream=False,
+                                representation_type="VoxelGrid"):
+    """representations [B,bins,H,W] and events masks [B,1,H,W] of B samples from ONE host-side packing and upload of the raw
     event arrays (what test_events-image_same-time.py:130-140 builds per sample with two passes over the events).
+    representation_type: one of REPRESENTATIONS; `normalize` applies to the voxel grid only.
     stage: an EventStage -- the upload goes through its page-locked arrays without blocking the host.
     on_stage_stream: the two representation kernels are enqueued on the stage's stream behind the copies as well (an evaluation
     loop: they then run beside the previous batch's forward); the current stream waits for them before it goes on."""
     bins, H, W = (int(v) for v in input_size)
+    build = build_representation(representation_type)
+    if build is events_to_voxel_grid_batch:
+        represent = lambda packed: build(events_list, input_size, normalize, device, packed=packed)  # noqa: E731
+    else:
+        represent = lambda packed: build(events_list, input_size, device, packed=packed)  # noqa: E731
     if stage is not None and on_stage_stream:
         packed = _pack(events_list, device, stage, defer_join=True)
         cur = torch.cuda.current_stream(stage.device)
         with torch.cuda.stream(stage.copy_stream):
-            grid = events_to_voxel_grid_batch(events_list, input_size, normalize, device, packed=packed)
+            grid = represent(packed)
             mask = events_mask_batch(events_list, (W, H), device, packed=packed)
         for t in (grid, mask):
             t.record_stream(cur)  # allocated on the stage's stream, consumed on the caller's
         stage.join()
         return grid, mask
     packed = _pack(events_list, device, stage)
-    return (events_to_voxel_grid_batch(events_list, input_size, normalize, device, packed=packed),
-            events_mask_batch(events_list, (W, H), device, packed=packed))
+    return represent(packed), events_mask_batch(events_list, (W, H), device, packed=packed)

@@ -15,13 +15,15 @@ import numpy as np
 import torch
 
 from .core.metrics._native_metrics import batch_homography, batch_metrics, batch_relative_pose, metric_names
-from .datasets.representations import EventStage, events_representation_batch
+from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
 class SameTimeEvaluator:
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), he_thresh=None, he_ransac_thresh=3.0,
-                 he_conf=0.995):
-        """model: EIM (eval mode); bins: voxel-grid channels; resolution: (W, H) like MVSECDataset.RESOLUTION.
+                 he_conf=0.995, representation_type="VoxelGrid"):
+        """model: EIM (eval mode); bins: the event network's in_channels; resolution: (W, H) like MVSECDataset.RESOLUTION.
+        representation_type: the datasets' switch (MVSEC.py:706-718): "VoxelGrid", "TimeSurface", "EventStack" or
+        "EventDistanceMap" -- what `step` and `run` build from the raw events on the device.
         he_thresh: HomographyEstimation's correctness thresholds (the script's [3, 5, 10]); None (default): no homography
         estimation, nothing is launched for it and result() has no HE key.  With thresholds, every batch whose `homography` is
         given also runs the RANSAC homography of its matches on the device (csrc/homography.hip; the script's
@@ -33,6 +35,8 @@ class SameTimeEvaluator:
         self._he_shapes = {}
         self.model = model
         self.bins = int(bins)
+        build_representation(representation_type)  # an unknown name raises here, not in the first batch
+        self.representation_type = representation_type
         self.resolution = tuple(int(v) for v in resolution)
         self.mma_thr, self.vdd_thr = tuple(mma_thr), tuple(vdd_thr)
         self.names = metric_names(self.mma_thr, self.vdd_thr)
@@ -59,7 +63,8 @@ class SameTimeEvaluator:
             # the image network does not depend on the events: it is enqueued FIRST and the host packs / uploads the raw events
             # (38 MB, ~2.5 ms) under its ~4 ms of device work; the event network follows (round 6: 11.7 -> see profiles/r06_notes.md)
             im = self.model.enqueue_image(images, None)
-            events_rep, events_mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage)
+            events_rep, events_mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage,
+                                                                  representation_type=self.representation_type)
             self.last_inputs = (events_rep, events_mask)  # what the extractors saw (deterministic since round 4: bit-equal run to run)
             ef, imf, matches = self.model._finish(self.model._enqueue(events_rep, images, events_mask, image_feats=im))
         return self._account(ef, imf, matches, homography, pose)
@@ -136,7 +141,8 @@ class SameTimeEvaluator:
                 # convolutions (0.3 ms of memory- / latency-bound kernels per batch leave the main stream's chain).  (Every
                 # in-flight slot on a stream of its own, so that batch i's tail could overlap batch i + 1's head, measured the
                 # same: 8.89 vs 8.84 ms per batch, profiles/r06_notes.md.)
-                rep, mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage, on_stage_stream=True)
+                rep, mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage, on_stage_stream=True,
+                                                        representation_type=self.representation_type)
                 self.last_inputs = (rep, mask)  # of the batch enqueued last (results lag by up to depth - 1 batches)
                 pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose))
             k += 1
@@ -247,8 +253,8 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
     """
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
-                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995):
-        super().__init__(model, bins, resolution, mma_thr, vdd_thr, he_thresh, he_ransac_thresh, he_conf)
+                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid"):
+        super().__init__(model, bins, resolution, mma_thr, vdd_thr, he_thresh, he_ransac_thresh, he_conf, representation_type)
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
         self._pose_rows = []

@@ -352,6 +352,35 @@ int einx_voxel_grid(const float* x, const float* y, const double* t, const float
 int einx_events_mask(const float* x, const float* y, const int64_t* offsets_host, int B, int H, int W, void* ws, uint8_t* mask,
                      void* stream);
 
+/* The other three values of the reference's `representation_type` (datasets/MVSEC.py:706-718, datasets/EC.py:236-248), DESIGN.md 8d.
+ * Same packed inputs as einx_voxel_grid; out: [B,bins,H,W] fp32.  Common rules: tn = (t - t[first]) / ((t[last] - t[first]) + 1e-8)
+ * in float64 per sample (representations.py:8-22); event k is in bin i iff tn >= i * dt && tn <= i * dt + dt (dt = 1.0 / nb, float64,
+ * both sides inclusive: for non-decreasing t the reference's two searchsorted calls; for unsorted t this per-event predicate IS
+ * the contract); xi = (int)x, yi = (int)y and an event outside the image is dropped (numpy would wrap a negative index or raise).
+ * A sample without events gives zeros (distance map: 8192.0).  Integer atomics only: two calls give the same bits.  The calls
+ * enqueue on `stream`, keep no library-owned state (the offsets travel as kernel arguments) and can be captured.
+ * offsets_host[0] must be 0; ws_bytes >= einx_*_ws_bytes(B, bins, H, W, offsets_host[B]) is checked (EINX_ERR_ARG); the size
+ * queries return 0 on a shape the op does not take. */
+size_t einx_time_surface_ws_bytes(int B, int bins, int H, int W, int64_t total_events);
+size_t einx_event_stack_ws_bytes(int B, int bins, int H, int W, int64_t total_events);
+size_t einx_distance_map_ws_bytes(int B, int bins, int H, int W, int64_t total_events);
+/* events_to_time_surface (datasets/representations.py:26-63): nb = bins / 2 (bins >= 2), channel c = 2 i + (int)p, where numpy's
+ * rule wraps -bins <= c < 0 once (p = -1) and any other c outside [0, bins) is dropped; a cell holds (float)tn of the
+ * highest-indexed event that hits it (numpy's "last one wins"), 0 where none does. */
+int einx_time_surface(const float* x, const float* y, const double* t, const float* p, const int64_t* offsets_host, int B, int bins, int H,
+                      int W, float* out, void* ws, size_t ws_bytes, void* stream);
+/* events_to_event_stack (datasets/representations.py:178-212): nb = bins, cell[i, yi, xi] += 2 (int)p - 1, summed in int32 and
+ * converted once: the reference's sequential float32 sum whenever every partial sum stays within +-2^24. */
+int einx_event_stack(const float* x, const float* y, const double* t, const float* p, const int64_t* offsets_host, int B, int bins, int H,
+                     int W, float* out, void* ws, size_t ws_bytes, void* stream);
+/* events_to_distance_map (datasets/representations.py:216-248): nb = bins; per bin the 3x3-mask chamfer distance of every pixel
+ * to the pixels hit by an event of the bin, in 16.16 fixed point with HV = 62587 (0.955), DIAG = 89738 (1.3693):
+ * d = min over set pixels of HV (max(|dx|,|dy|) - min(|dx|,|dy|)) + DIAG min(|dx|,|dy|), out = (float)d / 65536; a bin without a
+ * pixel gives 8192.0 everywhere.  The written algorithm, not bit parity with cv2.distanceTransform(..., DIST_L2, 3).
+ * W <= 1024, H <= 4096. */
+int einx_distance_map(const float* x, const float* y, const double* t, const float* p, const int64_t* offsets_host, int B, int bins, int H,
+                      int W, float* out, void* ws, size_t ws_bytes, void* stream);
+
 /* Host-side helper (no kernel, no device access): concatenates the B per-sample event arrays of a batch into the flat
  * x / y / p (fp32) and t (fp64) HOST arrays einx_voxel_grid / einx_events_mask read after an upload, converting element types
  * (C casts: the rounding of numpy's astype), and writes offsets[B + 1].  `threads` host threads share the copy (page-locked
