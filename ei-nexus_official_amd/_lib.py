@@ -62,6 +62,11 @@ class HomographyParams(ctypes.Structure):
                [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("he_thr", c_float * 4), ("seed", ctypes.c_uint64)]
 
 
+class GtMatchesParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap0", "cap1", "cols0", "cols1", "kp_yx", "H0", "W0", "H1", "W1",
+                                                                            "homography")] + [("pos_sq", c_float), ("neg_sq", c_float)]
+
+
 class EventArrays(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("y", c_void_p), ("t", c_void_p), ("p", c_void_p), ("x_type", ctypes.c_int32), ("y_type", ctypes.c_int32),
                 ("t_type", ctypes.c_int32), ("p_type", ctypes.c_int32), ("n", ctypes.c_int64)]
@@ -160,6 +165,12 @@ SIGNATURES = {
     "einx_homography_ws_bytes": (c_size_t, [ctypes.POINTER(HomographyParams)]),
     "einx_homography": (c_int, [ctypes.POINTER(HomographyParams)] + [c_void_p] * 11),
     "einx_homography_dlt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_gt_matches_ws_bytes": (c_size_t, [ctypes.POINTER(GtMatchesParams)]),
+    "einx_gt_project": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 23),
+    "einx_gt_warp": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 8),
+    "einx_gt_label": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 17),
+    "einx_gt_matches": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 30),
+    "einx_match_pr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "einx_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "einx_lg_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "einx_lg_ws_bytes_heads": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import HomographyParams, MetricParams, PoseParams, check
+from ..._lib import GtMatchesParams, HomographyParams, MetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -193,3 +193,184 @@ def homography_dlt(x1, x2):
     ok = torch.empty((n,), dtype=torch.int32, device=x1.device)
     check(N.lib().einx_homography_dlt(N._ptr(x1), N._ptr(x2), n, npts, N._ptr(H), N._ptr(ok), N._stream(x1)), "einx_homography_dlt")
     return H, ok
+
+
+# ---- ground-truth matches and matcher precision / recall (csrc/gt_matches.hip) ------------------------------------
+MATCH_PR_NAMES = ("match_recall", "match_precision", "accuracy", "average_precision")
+
+
+def _counts(c, B, cap, dev):
+    if c is None:
+        return torch.full((B,), cap, dtype=torch.int32, device=dev)
+    N._dev_check(c, dt=torch.int32)
+    return c
+
+
+def _gt_params(kp0, kp1, ordering, pos_th, neg_th, homography=False, size0=(0, 0), size1=(0, 0)):
+    p = GtMatchesParams()
+    p.struct_size = ctypes.sizeof(GtMatchesParams)
+    p.B, p.cap0, p.cols0 = kp0.shape
+    p.cap1, p.cols1 = kp1.shape[1], kp1.shape[2]
+    p.kp_yx = int(ordering == "yx")
+    p.H0, p.W0, p.H1, p.W1 = int(size0[0]), int(size0[1]), int(size1[0]), int(size1[1])
+    p.homography = int(homography)
+    p.pos_sq, p.neg_sq = float(pos_th ** 2), float(neg_th ** 2)
+    if kp1.shape[0] != p.B:
+        raise ValueError("einx: kp0 and kp1 differ in batch size")
+    return p
+
+
+def _f32c(t, dev, shape):
+    return t.to(dev, torch.float32).reshape(shape).contiguous()
+
+
+def _gt_stage_a_outputs(B, cap0, cap1, dev, pose_form=True):
+    o = {"proj_0to1": torch.empty((B, cap0, 2), dtype=torch.float32, device=dev),
+         "proj_1to0": torch.empty((B, cap1, 2), dtype=torch.float32, device=dev)}
+    if pose_form:
+        for side, cap in ((0, cap0), (1, cap1)):
+            o[f"depth_keypoints{side}"] = torch.empty((B, cap), dtype=torch.float32, device=dev)
+            o[f"valid{side}"] = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+            o[f"visible{side}"] = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    return o
+
+
+def _gt_label_outputs(B, cap0, cap1, dev):
+    return {"matches0": torch.empty((B, cap0), dtype=torch.int64, device=dev), "matches1": torch.empty((B, cap1), dtype=torch.int64, device=dev),
+            "matching_scores0": torch.empty((B, cap0), dtype=torch.float32, device=dev),
+            "matching_scores1": torch.empty((B, cap1), dtype=torch.float32, device=dev),
+            "pos0": torch.empty((B, cap0), dtype=torch.int32, device=dev)}
+
+
+def _pose_inputs(B, dev, depth0, depth1, K0, K1, T_0to1, T_1to0, precomputed):
+    a = {"K0": _f32c(K0, dev, (B, 9)), "K1": _f32c(K1, dev, (B, 9)), "T01": _f32c(T_0to1, dev, (B, 16)),
+         "T10": None if T_1to0 is None else _f32c(T_1to0, dev, (B, 16)), "d0": None, "d1": None, "pre": (None,) * 4, "size0": (0, 0), "size1": (0, 0)}
+    if precomputed is not None:
+        d0, v0, d1, v1 = precomputed
+        a["pre"] = (d0.to(dev, torch.float32).contiguous(), d1.to(dev, torch.float32).contiguous(), v0.to(dev, torch.uint8).contiguous(),
+                    v1.to(dev, torch.uint8).contiguous())
+    else:
+        a["d0"], a["d1"] = (d.to(dev, torch.float32).reshape(B, d.shape[-2], d.shape[-1]).contiguous() for d in (depth0, depth1))
+        a["size0"], a["size1"] = a["d0"].shape[1:], a["d1"].shape[1:]
+    return a
+
+
+def _bools(o):
+    for k in ("valid0", "valid1", "visible0", "visible1"):
+        if k in o:
+            o[k] = o[k].bool()
+    return o
+
+
+@on_input_device
+def gt_project(kp0, kp1, n, m, depth0, depth1, K0, K1, T_0to1, T_1to0=None, ordering="yx", precomputed=None):
+    """stage A, pose form: kp [B,cap,cols>=2] float32, n / m int32 [B] or None (= cap), depth [B,H,W], K [B,3,3], T [B,4,4]
+    (T_1to0 None: inverted in the kernel), precomputed = (d0, valid0, d1, valid1) [B,cap] instead of the depth maps.
+    Returns proj_0to1 / proj_1to0 [B,cap,2] (x, y), depth_keypoints*, valid*, visible* (bool)."""
+    B, dev = kp0.shape[0], kp0.device
+    N._dev_check(kp0, kp1)
+    n, m = _counts(n, B, kp0.shape[1], dev), _counts(m, B, kp1.shape[1], dev)
+    a = _pose_inputs(B, dev, depth0, depth1, K0, K1, T_0to1, T_1to0, precomputed)
+    p = _gt_params(kp0, kp1, ordering, 0, 0, False, a["size0"], a["size1"])
+    o = _gt_stage_a_outputs(B, p.cap0, p.cap1, dev)
+    P = N._ptr
+    check(N.lib().einx_gt_project(ctypes.byref(p), P(kp0), P(kp1), P(n), P(m), P(a["d0"]), P(a["d1"]), P(a["K0"]), P(a["K1"]), P(a["T01"]),
+                                  P(a["T10"]), *[P(t) for t in a["pre"]], P(o["depth_keypoints0"]), P(o["depth_keypoints1"]), P(o["valid0"]),
+                                  P(o["valid1"]), P(o["proj_0to1"]), P(o["proj_1to0"]), P(o["visible0"]), P(o["visible1"]), N._stream(kp0)),
+          "einx_gt_project")
+    return _bools(o)
+
+
+@on_input_device
+def gt_warp(kp0, kp1, n, m, homography, ordering="xy"):
+    """stage A, homography form: H [B,3,3] (or [3,3]) -> proj_0to1 = H kp0, proj_1to0 = H^-1 kp1, [B,cap,2] (x, y)"""
+    B, dev = kp0.shape[0], kp0.device
+    N._dev_check(kp0, kp1)
+    n, m = _counts(n, B, kp0.shape[1], dev), _counts(m, B, kp1.shape[1], dev)
+    H = _f32c(homography.expand(B, 3, 3) if homography.dim() == 2 else homography, dev, (B, 9))
+    p = _gt_params(kp0, kp1, ordering, 0, 0, True)
+    o = _gt_stage_a_outputs(B, p.cap0, p.cap1, dev, pose_form=False)
+    check(N.lib().einx_gt_warp(ctypes.byref(p), N._ptr(kp0), N._ptr(kp1), N._ptr(n), N._ptr(m), N._ptr(H), N._ptr(o["proj_0to1"]),
+                               N._ptr(o["proj_1to0"]), N._stream(kp0)), "einx_gt_warp")
+    return o
+
+
+@on_input_device
+def gt_label(kp0, kp1, n, m, proj_0to1, proj_1to0, visible0=None, visible1=None, valid0=None, valid1=None, pos_th=3, neg_th=5, ordering="yx"):
+    """stage B from given projections [B,cap,2] (x, y) and visibility / validity [B,cap] (bool or uint8; None: all true, the
+    homography form) -> matches0 / matches1 int64, matching_scores0 / 1 float32, pos0 int32"""
+    B, dev = kp0.shape[0], kp0.device
+    N._dev_check(kp0, kp1, proj_0to1, proj_1to0)
+    n, m = _counts(n, B, kp0.shape[1], dev), _counts(m, B, kp1.shape[1], dev)
+    u8 = lambda t: None if t is None else t.to(dev, torch.uint8).contiguous()  # noqa: E731
+    vis0, vis1, val0, val1 = u8(visible0), u8(visible1), u8(valid0), u8(valid1)
+    p = _gt_params(kp0, kp1, ordering, pos_th, neg_th, visible0 is None)
+    L = N.lib()
+    ws = N._workspace(L.einx_gt_matches_ws_bytes(ctypes.byref(p)), dev)
+    o = _gt_label_outputs(B, p.cap0, p.cap1, dev)
+    P = N._ptr
+    check(L.einx_gt_label(ctypes.byref(p), P(kp0), P(kp1), P(n), P(m), P(proj_0to1), P(proj_1to0), P(vis0), P(vis1), P(val0), P(val1), P(ws),
+                          P(o["matches0"]), P(o["matches1"]), P(o["matching_scores0"]), P(o["matching_scores1"]), P(o["pos0"]), N._stream(kp0)),
+          "einx_gt_label")
+    return o
+
+
+@on_input_device
+def gt_matches(kp0, kp1, n=None, m=None, depth0=None, depth1=None, K0=None, K1=None, T_0to1=None, T_1to0=None, homography=None, pos_th=3,
+               neg_th=5, ordering="yx", precomputed=None):
+    """stages A + B in one call (einx_gt_matches), no host sync: the pose form (depth maps or `precomputed` depths, K, T) or, with
+    `homography`, the homography form.  kp [B,cap,cols>=2], n / m int32 [B] or None (= cap).  Returns every tensor of gt_project /
+    gt_warp and gt_label in one dict."""
+    B, dev = kp0.shape[0], kp0.device
+    kp0, kp1 = kp0.float().contiguous(), kp1.float().contiguous()
+    N._dev_check(kp0, kp1)
+    n, m = _counts(n, B, kp0.shape[1], dev), _counts(m, B, kp1.shape[1], dev)
+    hom = homography is not None
+    if hom:
+        a = {"K0": None, "K1": None, "T01": None, "T10": None, "d0": None, "d1": None, "pre": (None,) * 4, "size0": (0, 0), "size1": (0, 0)}
+        H = _f32c(homography.expand(B, 3, 3) if homography.dim() == 2 else homography, dev, (B, 9))
+    else:
+        a = _pose_inputs(B, dev, depth0, depth1, K0, K1, T_0to1, T_1to0, precomputed)
+        H = None
+    p = _gt_params(kp0, kp1, ordering, pos_th, neg_th, hom, a["size0"], a["size1"])
+    L = N.lib()
+    ws = N._workspace(L.einx_gt_matches_ws_bytes(ctypes.byref(p)), dev)
+    o = _gt_stage_a_outputs(B, p.cap0, p.cap1, dev, pose_form=not hom)
+    o.update(_gt_label_outputs(B, p.cap0, p.cap1, dev))
+    P = N._ptr
+    check(L.einx_gt_matches(ctypes.byref(p), P(kp0), P(kp1), P(n), P(m), P(a["d0"]), P(a["d1"]), P(a["K0"]), P(a["K1"]), P(a["T01"]), P(a["T10"]),
+                            *[P(t) for t in a["pre"]], P(H), P(ws), P(o.get("depth_keypoints0")), P(o.get("depth_keypoints1")), P(o.get("valid0")),
+                            P(o.get("valid1")), P(o["proj_0to1"]), P(o["proj_1to0"]), P(o.get("visible0")), P(o.get("visible1")), P(o["matches0"]),
+                            P(o["matches1"]), P(o["matching_scores0"]), P(o["matching_scores1"]), P(o["pos0"]), N._stream(kp0)), "einx_gt_matches")
+    return _bools(o)
+
+
+@on_input_device
+def batch_gt_matches(ev_batched, im_batched, depth0, depth1, K0, K1, T_0to1, T_1to0=None, pos_th=3, neg_th=5):
+    """gt_matches of the keypoints of an EIM.forward_batched result (BatchedFeats x2: positions [B,cap,3] + counts), no host sync"""
+    return gt_matches(ev_batched.det.positions, im_batched.det.positions, ev_batched.det.counts, im_batched.det.counts, depth0, depth1, K0, K1,
+                      T_0to1, T_1to0, pos_th=pos_th, neg_th=neg_th, ordering=ev_batched.ordering)
+
+
+@on_input_device
+def match_pr(mr, gt_m0, n=None, scores0=None):
+    """matcher_metrics per pair over its first n[b] rows (n None: every row).  `mr`: a MatchResult (its matches0 / scores0 are
+    taken) or the matches0 tensor [B,cap] int64 with `scores0` [B,cap] float32 beside it; gt_m0 [B,cap] int64.
+    Returns [B,4] float64 = MATCH_PR_NAMES (NaN for a pair without rows)."""
+    if isinstance(mr, N.MatchResult):
+        mr, scores0 = mr.matches0, mr.scores0
+    if scores0 is None:
+        raise ValueError("einx: match_pr needs a MatchResult, or matches0 with scores0=")
+    B, cap = mr.shape
+    dev = mr.device
+    if cap == 0:
+        return torch.full((B, 4), float("nan"), dtype=torch.float64, device=dev)
+    matches0, gt_m0 = mr.to(torch.int64).contiguous(), gt_m0.to(dev, torch.int64).contiguous()
+    scores0 = scores0.to(dev, torch.float32).contiguous()
+    if gt_m0.shape != matches0.shape or scores0.shape != matches0.shape:
+        raise ValueError("einx: matches0, scores0 and gt_m0 must have one shape [B,cap]")
+    n = _counts(n, B, cap, dev)
+    out = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    check(N.lib().einx_match_pr(N._ptr(matches0), N._ptr(scores0), N._ptr(gt_m0), N._ptr(n), B, cap, N._ptr(out), N._stream(matches0)),
+          "einx_match_pr")
+    return out

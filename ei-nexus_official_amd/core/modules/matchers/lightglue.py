@@ -3,8 +3,9 @@
 Drop-in for LightGlue (reference core/modules/matchers/lightglue.py:421-716), inference path:
 same `conf` handling (merged over `default_conf`), same parameter tree (`posenc.Wr`,
 `transformers.{i}.self_attn|cross_attn.*`, `log_assignment.{i}.*`, `token_confidence.{i}.*`,
-optional `input_proj`) and the same output dict.  Training-only members (loss, NLLLoss,
-matcher_metrics, token-confidence loss; :17-133, :190-203, :751-800) are out of scope.
+optional `input_proj`) and the same output dict.  `matcher_metrics` (:17-63) runs on the device
+(csrc/gt_matches.hip).  Training-only members (loss, NLLLoss, token-confidence
+loss; :66-133, :190-203, :751-800) are out of scope.
 Early stopping / point pruning are commented out in the reference (:606-652) and absent here.
 """
 import ctypes
@@ -16,6 +17,19 @@ from ...._native import on_input_device
 from .... import _lib
 from .... import _native as N
 from ._batched import from_feats, materialize_matches, stacked_outputs
+
+
+@torch.no_grad()
+def matcher_metrics(pred, data, prefix="", prefix_gt=None):
+    """match_recall, match_precision, accuracy and average_precision of pred[f"{prefix}matches0"] (ranked by
+    pred[f"{prefix}matching_scores0"]) against data[f"gt_{prefix_gt}matches0"], one value per pair: the reference's keys in and out
+    (lightglue.py:17-63), computed by einx_match_pr.  average_precision is the closed form precision * (recall - r_first) of the
+    reference's expression, the highest score's row taken at the lowest index on a tie."""
+    from ...metrics._native_metrics import MATCH_PR_NAMES, match_pr
+    if prefix_gt is None:
+        prefix_gt = prefix
+    rows = match_pr(pred[f"{prefix}matches0"], data[f"gt_{prefix_gt}matches0"], scores0=pred[f"{prefix}matching_scores0"]).float()
+    return {f"{prefix}{name}": rows[:, i] for i, name in enumerate(MATCH_PR_NAMES)}
 
 
 class _Conf(dict):

@@ -10,11 +10,15 @@
 
                --(homography.hip, evaluators built with he_thresh, steps given a homography)--> RANSAC homography, refit, LM
                   polish, mean corner error per pair --> HE means and AUC@t (per-pair rows all-gathered across ranks)
+
+               --(gt_matches.hip, DifferentTimeEvaluator with poses and depth maps)--> ground-truth matches of the keypoints,
+                  match_recall / match_precision / accuracy / average_precision per pair --> means (all-reduced across ranks)
 """
 import numpy as np
 import torch
 
-from .core.metrics._native_metrics import batch_homography, batch_metrics, batch_relative_pose, metric_names
+from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, batch_homography, batch_metrics, batch_relative_pose, match_pr,
+                                            metric_names)
 from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
@@ -51,7 +55,7 @@ class SameTimeEvaluator:
         (scaled in place by SuperPoint exactly like the reference).  Returns the per-pair metric rows [B,K] (device)."""
         return self._step(events_list, images, homography, None)
 
-    def _step(self, events_list, images, homography, pose):
+    def _step(self, events_list, images, homography, pose, depth=None):
         W, H = self.resolution
         dev = images.device
         if not hasattr(self, "_stages"):
@@ -67,7 +71,7 @@ class SameTimeEvaluator:
                                                                   representation_type=self.representation_type)
             self.last_inputs = (events_rep, events_mask)  # what the extractors saw (deterministic since round 4: bit-equal run to run)
             ef, imf, matches = self.model._finish(self.model._enqueue(events_rep, images, events_mask, image_feats=im))
-        return self._account(ef, imf, matches, homography, pose)
+        return self._account(ef, imf, matches, homography, pose, **self._depth_argument(pose, depth))
 
     def _account(self, ef, imf, matches, homography, pose=None):
         rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, homography, self.mma_thr, self.vdd_thr)
@@ -110,7 +114,7 @@ class SameTimeEvaluator:
     @torch.no_grad()
     def run(self, batches, depth=2):
         """The evaluation LOOP (test_events-image_same-time.py:130-194 iterates a DataLoader): `batches` yields
-        (events_list, images[, homography[, pose]]) like the arguments of `step`; one `step` result per batch comes back, in order.
+        (events_list, images[, homography[, pose[, depth]]]) like the arguments of `step`; one `step` result per batch comes back, in order.
         Up to `depth` batches are in flight: batch i + 1's events are concatenated into page-locked memory, uploaded with
         non-blocking copies and its kernels enqueued (EIM.forward_stream's mechanism) BEFORE the host waits for batch i's
         counts, so packing and the PCIe transfer hide under the device's work instead of adding to it.  Same kernels, same
@@ -124,13 +128,15 @@ class SameTimeEvaluator:
         k = 0
 
         def finish(entry):
-            p, hom, pose = entry
-            return self._account(*self.model._finish(p), hom, pose)
+            p, hom, pose, depth_maps = entry
+            return self._account(*self.model._finish(p), hom, pose, **self._depth_argument(pose, depth_maps))
 
         for item in batches:
             events_list, images = item[0], item[1]
             homography = item[2] if len(item) > 2 else None
             pose = item[3] if len(item) > 3 else None
+            depth_maps = item[4] if len(item) > 4 else None
+            self._depth_argument(pose, depth_maps)  # raises before anything is enqueued
             slot = k % depth
             dev = images.device
             with torch.cuda.device(dev):
@@ -144,12 +150,19 @@ class SameTimeEvaluator:
                 rep, mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage, on_stage_stream=True,
                                                         representation_type=self.representation_type)
                 self.last_inputs = (rep, mask)  # of the batch enqueued last (results lag by up to depth - 1 batches)
-                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose))
+                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose, depth_maps))
             k += 1
             if len(pending) >= depth:
                 yield finish(pending.popleft())
         while pending:
             yield finish(pending.popleft())
+
+    def _depth_argument(self, pose, depth):
+        """what `_account` is given for the depth maps of a batch: nothing here -- the same-time evaluation has no use for them,
+        so an item that carries some is an error, not something to drop silently; DifferentTimeEvaluator passes them on"""
+        if depth is not None:
+            raise ValueError(f"einx: {type(self).__name__} takes no depth maps (DifferentTimeEvaluator does, together with pose=)")
+        return {}
 
     def result(self):
         """Mean of every metric over the pairs seen so far; sums are all-reduced when a process group is up."""
@@ -244,9 +257,15 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
       [B,4,4] of the pair on the device, the RANSAC relative pose of every pair runs on the device as well (csrc/pose.hip, what
       RelativePoseEstimation.update_one computes, :251-257), with no host synchronisation; the returned rows are unchanged.
       `run()` items may carry the same tuple as a 4th element.
+    * `step(..., pose=(K0, K1, T_0to1), depth=(depth0, depth1))`: with the depth maps [B,H,W] of the two views as well, the
+      ground-truth matches of the batch's keypoints (events = view 0, image = view 1; csrc/gt_matches.hip, DESIGN.md 8e: what
+      val_matcher.py:66-97 computes with gt_matches_from_pose_depth) and the matcher's match_recall / match_precision / accuracy /
+      average_precision against them (matcher_metrics) run on the device too, with no host synchronisation; the returned rows
+      are unchanged, `last_gt` keeps the batch's label tensors.  `depth` without `pose` raises.  `run()` items may carry `depth`
+      as a 5th element.
     * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
       RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
-      all-gathered before the AUC.
+      all-gathered before the AUC.  Once depth was given: the four matcher_metrics means over the pairs that have keypoints.
     * `pose_inputs(matches, b)`: what the reference feeds RelativePoseEstimation.update_one for pair b
       (`matches["matched_kpts0"][b]`, `matches["matched_kpts1"][b]`, :251-257), plus the (x, y) views of
       test_events-image_different_time.py:217-224 (`[..., :2]`, flipped when the extractor's ordering is "yx").
@@ -258,13 +277,30 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
         self._pose_rows = []
+        self._pr_rows = []
+        self._pr_sums = self._pr_counts = None
+        self.gt_pos_th, self.gt_neg_th = 3, 5  # gt_matches_from_pose_depth's defaults, as val_matcher.py calls it
+        self.last_gt = None
 
     @torch.no_grad()
-    def step(self, events_list, images, homography=None, pose=None):
-        return self._step(events_list, images, homography, pose)
+    def step(self, events_list, images, homography=None, pose=None, depth=None):
+        self._depth_argument(pose, depth)
+        return self._step(events_list, images, homography, pose, depth)
 
-    def _account(self, ef, imf, matches, homography, pose=None):
+    def _depth_argument(self, pose, depth):
+        if depth is not None and pose is None:
+            raise ValueError("einx: depth=(depth0, depth1) needs pose=(K0, K1, T_0to1): ground-truth matches come from depth AND motion")
+        return {} if depth is None else {"depth": depth}
+
+    def _account(self, ef, imf, matches, homography, pose=None, depth=None):
         out = super()._account(ef, imf, matches, homography)
+        if depth is not None:
+            K0, K1, T = pose
+            mr = self.model._last_match
+            self.last_gt = batch_gt_matches(ef._batched, imf._batched, depth[0], depth[1], K0, K1, T, None, self.gt_pos_th, self.gt_neg_th)
+            self._pr_rows.append(match_pr(mr, self.last_gt["matches0"], ef._batched.det.counts))
+            if len(self._pr_rows) >= 64:
+                self._fold_pr()
         if pose is not None:
             K0, K1, T = pose
             _, _, _, _, prow = batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
@@ -272,9 +308,35 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
             self._pose_rows.append(prow)
         return out
 
+    def _fold_pr(self):
+        """NaN-aware sums and counts of the [B,4] matcher_metrics rows (a pair without keypoints has NaN rows)"""
+        if not self._pr_rows:
+            return
+        rows = torch.cat(self._pr_rows, 0)
+        self._pr_rows = []
+        ok = ~torch.isnan(rows)
+        s, c = torch.nan_to_num(rows).sum(0), ok.sum(0).double()
+        self._pr_sums = s if self._pr_sums is None else self._pr_sums + s
+        self._pr_counts = c if self._pr_counts is None else self._pr_counts + c
+
     def result(self):
         out = super().result()
         out.update(_gathered_summary(self._pose_rows, 4, rpe_summary, self.pose_thresh))
+        self._fold_pr()
+        grouped = torch.distributed.is_available() and torch.distributed.is_initialized()
+        if self._pr_sums is not None or grouped:
+            # under a process group EVERY rank reduces, with zeros if it was given no depth: a rank that skipped the collective
+            # would leave the others waiting in it (as _gathered_summary does for the pose rows)
+            if self._pr_sums is None:
+                dev = self.sums.device if self.sums is not None else "cpu"
+                s, c = torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(4, dtype=torch.float64, device=dev)
+            else:
+                s, c = self._pr_sums.clone(), self._pr_counts.clone()
+            if grouped:
+                torch.distributed.all_reduce(s)
+                torch.distributed.all_reduce(c)
+            if float(c.max()) > 0:  # some rank labelled a pair that has keypoints
+                out.update(zip(MATCH_PR_NAMES, (s / c.clamp_min(1)).tolist()))
         return out
 
     def pose_inputs(self, matches, b=0):

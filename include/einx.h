@@ -602,6 +602,53 @@ int einx_homography(const einx_homography_params* p, const float* mk0, const flo
  * stores); H_out [n,9] float64 gets the normalised DLT of each problem (H[2,2] = 1), ok [n] int32 is 0 where it has none. */
 int einx_homography_dlt(const double* x1, const double* x2, int n_problems, int n_points, double* H_out, int32_t* ok, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ground-truth matches and the matcher's precision / recall (csrc/gt_matches.hip)
+ *   gt_matches_from_pose_depth / gt_matches_from_homography   core/geometry/gt_generation.py:15-224
+ *   sample_depth, project (ccth=None)                         core/geometry/depth.py:9-60
+ *   matcher_metrics                                           core/modules/matchers/lightglue.py:17-63
+ * Per side: keypoints kp [B,cap,cols>=2] float32 + int32 counts n / m [B] (the PairBatch layout), depth [B,H,W] float32 with its
+ * own H, W, K [B,3,3] and T [B,4,4] float32.  T_1to0 may be NULL: the kernel then uses (R^T, -R^T t) of T_0to1.  With the four
+ * dk*_in / vk*_in arrays (depths [B,cap] float32 and their validity uint8 per keypoint) the depth maps are not read (may be NULL).
+ * Stage A (einx_gt_project, or einx_gt_warp with H [B,9] float32 for the homography form) writes dk [B,cap] sampled depths,
+ * valid / vis [B,cap] uint8 and proj [B,cap,2] (x, y) projections into the other view (NaN where the depth is NaN); rows at or
+ * beyond a pair's count get zeros.  Stage B (einx_gt_label, from given projections; vis* / valid* NULL = every point visible /
+ * valid, the homography form) writes matches [B,cap] int64 (index, -1 unmatched, -2 ignore; -2 at or beyond the count, -1
+ * everywhere below it when the pair has n == 0 or m == 0), scores [B,cap] float32 = (matches > -1), and pos0 [B,cap0] int32 (the
+ * mutual positive of row i or -1: the dense `assignment` is its scatter; may be NULL).  No N x M intermediate, no atomics: bit-exact
+ * given stage A's outputs, and two runs give the same bits.  einx_gt_matches = stage A (einx_gt_warp when p->homography) + B.
+ * einx_match_pr: matcher_metrics per pair over its first n[b] rows, out [B,4] float64 = match_recall, match_precision, accuracy,
+ * average_precision (NaN for n[b] == 0); matches0 / gt_matches0 [B,cap0] int64, scores0 [B,cap0] float32.
+ * Nothing synchronises or allocates; every call can be captured.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_gt_matches_params {
+  size_t struct_size;     /* sizeof(einx_gt_matches_params) (checked) */
+  int32_t B, cap0, cap1;
+  int32_t cols0, cols1;   /* row width of kp0 / kp1 (>= 2) */
+  int32_t kp_yx;          /* 1: keypoints are (y,x,..) */
+  int32_t H0, W0, H1, W1; /* sizes of depth0 / depth1 (unused with precomputed depths and by the homography form) */
+  int32_t homography;     /* einx_gt_matches: 0 pose form, 1 homography form */
+  float pos_sq, neg_sq;   /* pos_th^2, neg_th^2 rounded to float32 (what torch compares a float32 tensor with) */
+} einx_gt_matches_params;
+size_t einx_gt_matches_ws_bytes(const einx_gt_matches_params* p); /* workspace of einx_gt_label / einx_gt_matches; 0 on a bad shape */
+int einx_gt_project(const einx_gt_matches_params* p, const float* kp0, const float* kp1, const int32_t* n, const int32_t* m,
+                    const float* depth0, const float* depth1, const float* K0, const float* K1, const float* T_0to1, const float* T_1to0,
+                    const float* dk0_in, const float* dk1_in, const uint8_t* vk0_in, const uint8_t* vk1_in, float* dk0, float* dk1,
+                    uint8_t* valid0, uint8_t* valid1, float* proj01, float* proj10, uint8_t* vis0, uint8_t* vis1, void* stream);
+int einx_gt_warp(const einx_gt_matches_params* p, const float* kp0, const float* kp1, const int32_t* n, const int32_t* m, const float* H,
+                 float* proj01, float* proj10, void* stream);
+int einx_gt_label(const einx_gt_matches_params* p, const float* kp0, const float* kp1, const int32_t* n, const int32_t* m,
+                  const float* proj01, const float* proj10, const uint8_t* vis0, const uint8_t* vis1, const uint8_t* valid0,
+                  const uint8_t* valid1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, int32_t* pos0,
+                  void* stream);
+int einx_gt_matches(const einx_gt_matches_params* p, const float* kp0, const float* kp1, const int32_t* n, const int32_t* m,
+                    const float* depth0, const float* depth1, const float* K0, const float* K1, const float* T_0to1, const float* T_1to0,
+                    const float* dk0_in, const float* dk1_in, const uint8_t* vk0_in, const uint8_t* vk1_in, const float* H, void* ws,
+                    float* dk0, float* dk1, uint8_t* valid0, uint8_t* valid1, float* proj01, float* proj10, uint8_t* vis0, uint8_t* vis1,
+                    int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, int32_t* pos0, void* stream);
+int einx_match_pr(const int64_t* matches0, const float* scores0, const int64_t* gt_matches0, const int32_t* n, int B, int cap0, double* out,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
