@@ -25,6 +25,7 @@ from . import _native as native  # noqa: E402
 from . import configs, shard, synth  # noqa: E402
 from .configs import AttrDict, default_config  # noqa: E402
 from .core.modules import EIM, ImageImageMatcher, build_model  # noqa: E402
+from .core.loss import build_losses  # noqa: E402
 from .core.modules.Extractors import EventKeypointsExtractor, ImageKeypointsExtractor  # noqa: E402
 from .core.modules.Matchers import Matcher  # noqa: E402
 from .core.modules.matchers.MNN import NearestNeighborMatcher  # noqa: E402
@@ -49,5 +50,5 @@ def install_as_core():
     return _core
 
 
-__all__ = ["install_as_core", "SameTimeEvaluator", "DifferentTimeEvaluator", "EIM", "ImageImageMatcher", "build_model", "EventKeypointsExtractor", "ImageKeypointsExtractor", "Matcher",
+__all__ = ["install_as_core", "SameTimeEvaluator", "DifferentTimeEvaluator", "EIM", "ImageImageMatcher", "build_model", "build_losses", "EventKeypointsExtractor", "ImageKeypointsExtractor", "Matcher",
            "NearestNeighborMatcher", "LightGlue", "default_config", "AttrDict", "native"]

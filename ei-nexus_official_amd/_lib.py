@@ -171,6 +171,11 @@ SIGNATURES = {
     "einx_gt_label": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 17),
     "einx_gt_matches": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 30),
     "einx_match_pr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "einx_desc_loss_ws_bytes": (c_size_t, [c_int] * 11),
+    "einx_desc_loss": (c_int, [c_void_p, c_float, c_void_p, c_float] + [c_int] * 11 + [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "einx_map_loss_ws_bytes": (c_size_t, [c_int, c_int]),
+    "einx_map_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "einx_logits_loss": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "einx_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "einx_lg_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "einx_lg_ws_bytes_heads": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -520,3 +520,80 @@ class ParamWatch:
             check(lib().einx_params_hash(_ptr(self.table), self.n, _ptr(self.scratch), _ptr(self.ref), _ptr(self.stale), _stream(self.table)),
                   "einx_params_hash")
         return self.stale
+
+
+# ------------------------------------------------------------------------------ losses (forward values; csrc/loss.hip)
+DESC_LOSS_MODES = {"mae": 0, "mse": 1, "cos": 2}
+MAP_LOSS_MODES = {"sq": 0, "abs": 1, "bce": 2, "cos": 3}
+
+
+def _loss_mask(mask, numel):
+    """-> (the tensor the kernel reads, or None; its einx.h mask type).  bool / uint8: non-zero is 1; anything else: float32 weights."""
+    if mask is None:
+        return None, 0
+    if mask.device.type != "cuda":
+        raise RuntimeError(f"einx: the mask must live on a HIP device, got {mask.device}")
+    if mask.numel() != numel:
+        raise ValueError(f"einx: mask of {mask.numel()} elements where {numel} are expected")
+    if mask.dtype == torch.bool:
+        return mask.contiguous().view(U8), 1
+    if mask.dtype == U8:
+        return mask.contiguous(), 1
+    return mask.to(F32).contiguous(), 2
+
+
+def desc_loss(raw_a, scale_a, raw_b, scale_b, padded_size, pads, cell, mask=None, mode="mae"):
+    """(sum, count) per image [B,2] float64 of DescriptorsLoss over the `normalized_descriptors` of two raw maps [B,D,hc,wc]
+    without building the dense maps (einx_desc_loss).  mask: [B,H,W] (any shape with B*H*W elements) or None."""
+    _dev_check(raw_a, raw_b)
+    if raw_a.shape != raw_b.shape:
+        raise ValueError(f"einx: raw maps of different shapes {tuple(raw_a.shape)} / {tuple(raw_b.shape)}")
+    B, D, hc, wc = raw_a.shape
+    Hp, Wp = int(padded_size[0]), int(padded_size[1])
+    w0, w1, h0, h1 = pads
+    H, W = Hp - h0 - h1, Wp - w0 - w1
+    m, mt = _loss_mask(mask, B * H * W)
+    out = torch.empty((B, 2), dtype=torch.float64, device=raw_a.device)
+    L = lib()
+    nws = int(L.einx_desc_loss_ws_bytes(B, D, hc, wc, Hp, Wp, h0, w0, H, W, int(cell)))
+    ws = _workspace(nws, raw_a.device)
+    check(L.einx_desc_loss(_ptr(raw_a), float(scale_a), _ptr(raw_b), float(scale_b), B, D, hc, wc, Hp, Wp, h0, w0, H, W, int(cell), _ptr(m), mt,
+                           DESC_LOSS_MODES[mode], _ptr(out), _ptr(ws), nws, _stream(raw_a)), "einx_desc_loss")
+    return out
+
+
+def map_loss(x, y, mask=None, mode="sq"):
+    """(sum, count) per image [B,2] float64 of a masked pair reduction over two float32 tensors [B,C,...] (einx_map_loss).
+    mask: B*P elements (broadcast over the channels) or B*C*P (one weight per element), or None."""
+    _dev_check(x, y)
+    if x.shape != y.shape:
+        raise ValueError(f"einx: tensors of different shapes {tuple(x.shape)} / {tuple(y.shape)}")
+    B, C = int(x.shape[0]), (int(x.shape[1]) if x.dim() > 2 else 1)
+    P = int(x.numel() // (B * C))
+    full = mask is not None and C > 1 and mask.numel() == B * C * P
+    m, mt = _loss_mask(mask, B * C * P if full else B * P)
+    out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    L = lib()
+    nws = int(L.einx_map_loss_ws_bytes(B, P))
+    ws = _workspace(nws, x.device)
+    check(L.einx_map_loss(_ptr(x), _ptr(y), B, C, P, _ptr(m), mt, int(full), MAP_LOSS_MODES[mode], _ptr(out), _ptr(ws), nws, _stream(x)),
+          "einx_map_loss")
+    return out
+
+
+def logits_loss(x, y, cell, crop=None, mask=None):
+    """(sum, count) per image [B,2] float64 of LogitsLoss over [B,cell^2+1,hc,wc] logits (einx_logits_loss).
+    crop: (h0, w0, H, W) of the un-padded window in the pixel-shuffled map, None: the whole map; mask: B*H*W elements or None."""
+    _dev_check(x, y)
+    if x.shape != y.shape:
+        raise ValueError(f"einx: tensors of different shapes {tuple(x.shape)} / {tuple(y.shape)}")
+    B, C, hc, wc = x.shape
+    h0, w0, H, W = (0, 0, cell * hc, cell * wc) if crop is None else (int(v) for v in crop)
+    m, mt = _loss_mask(mask, B * H * W)
+    out = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+    L = lib()
+    nws = int(L.einx_map_loss_ws_bytes(B, hc * wc))
+    ws = _workspace(nws, x.device)
+    check(L.einx_logits_loss(_ptr(x), _ptr(y), B, C, int(cell), hc, wc, h0, w0, H, W, _ptr(m), mt, _ptr(out), _ptr(ws), nws, _stream(x)),
+          "einx_logits_loss")
+    return out

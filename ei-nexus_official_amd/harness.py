@@ -22,9 +22,12 @@ from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, bat
 from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
+LOSS_NAMES = ("extractor_keypoints_loss", "extractor_descriptor_loss", "loss")  # val_extractor.py:167-172 (VAL_ prefix added there)
+
+
 class SameTimeEvaluator:
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), he_thresh=None, he_ransac_thresh=3.0,
-                 he_conf=0.995, representation_type="VoxelGrid"):
+                 he_conf=0.995, representation_type="VoxelGrid", losses=None):
         """model: EIM (eval mode); bins: the event network's in_channels; resolution: (W, H) like MVSECDataset.RESOLUTION.
         representation_type: the datasets' switch (MVSEC.py:706-718): "VoxelGrid", "TimeSurface", "EventStack" or
         "EventDistanceMap" -- what `step` and `run` build from the raw events on the device.
@@ -32,7 +35,17 @@ class SameTimeEvaluator:
         estimation, nothing is launched for it and result() has no HE key.  With thresholds, every batch whose `homography` is
         given also runs the RANSAC homography of its matches on the device (csrc/homography.hip; the script's
         HE.update_one, test_events-image_same-time.py:189-194) with no host synchronisation, and result() adds HE@t_ratio,
-        HE_errors, HE_inliers and HE@t_auc (:269-277)."""
+        HE_errors, HE_inliers and HE@t_auc (:269-277).
+        losses: the dict of core.loss.build_losses (any mapping with `keypoints_loss` / `descriptors_loss`), None (default):
+        nothing is launched for it and result() is unchanged.  With losses, every batch also enqueues the two extractor losses of
+        the reference's stage-1 validation loop (val_extractor.py:154-163: keypoints_loss(events_feats, image_feats, events_mask,
+        padder), descriptors_loss(events_feats, image_feats, events_mask)) on the device (csrc/loss.hip) with no
+        host synchronisation, one value per pair as that loop forms them at its batch size of 1, and result() adds
+        extractor_keypoints_loss, extractor_descriptor_loss and loss (their per-pair sum): each the mean over the pairs where it is
+        finite (:183-186)."""
+        self.losses = losses
+        self._loss_rows = []
+        self._loss_sums = self._loss_counts = None
         self.he_thresh = None if he_thresh is None else tuple(he_thresh)
         self.he_ransac_thresh, self.he_conf = float(he_ransac_thresh), float(he_conf)
         self._he_rows = []
@@ -71,7 +84,38 @@ class SameTimeEvaluator:
                                                                   representation_type=self.representation_type)
             self.last_inputs = (events_rep, events_mask)  # what the extractors saw (deterministic since round 4: bit-equal run to run)
             ef, imf, matches = self.model._finish(self.model._enqueue(events_rep, images, events_mask, image_feats=im))
-        return self._account(ef, imf, matches, homography, pose, **self._depth_argument(pose, depth))
+        out = self._account(ef, imf, matches, homography, pose, **self._depth_argument(pose, depth))
+        self._account_losses(ef, imf, events_mask)
+        return out
+
+    def _account_losses(self, ef, imf, events_mask):
+        """[B,3] float64 rows (keypoints loss, descriptors loss, their sum) of the batch's pairs, kept on the device; an entry of
+        `losses` that is missing or has no per-pair form (core.loss.Pass) gives NaN, which the means skip"""
+        if self.losses is None:
+            return
+        from .core.modules.utils.util import Padder
+        bf = ef._batched
+        padder = Padder(tuple(bf.image_size), bf.cell)
+        cols = []
+        for key in ("keypoints_loss", "descriptors_loss"):
+            pair_values = getattr(self.losses.get(key), "pair_values", None)
+            if pair_values is None:
+                cols.append(torch.full((bf.B,), float("nan"), dtype=torch.float64, device=bf.raw.device))
+            else:
+                cols.append(pair_values(ef, imf, events_mask, padder))
+        self._loss_rows.append(torch.stack([cols[0], cols[1], cols[0] + cols[1]], 1))
+        if len(self._loss_rows) >= 64:
+            self._fold_losses()
+
+    def _fold_losses(self):
+        if not self._loss_rows:
+            return
+        rows = torch.cat(self._loss_rows, 0)
+        self._loss_rows = []
+        ok = torch.isfinite(rows)
+        s, c = torch.where(ok, rows, torch.zeros_like(rows)).sum(0), ok.sum(0).double()
+        self._loss_sums = s if self._loss_sums is None else self._loss_sums + s
+        self._loss_counts = c if self._loss_counts is None else self._loss_counts + c
 
     def _account(self, ef, imf, matches, homography, pose=None):
         rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, homography, self.mma_thr, self.vdd_thr)
@@ -128,8 +172,11 @@ class SameTimeEvaluator:
         k = 0
 
         def finish(entry):
-            p, hom, pose, depth_maps = entry
-            return self._account(*self.model._finish(p), hom, pose, **self._depth_argument(pose, depth_maps))
+            p, hom, pose, depth_maps, mask = entry
+            ef, imf, matches = self.model._finish(p)
+            out = self._account(ef, imf, matches, hom, pose, **self._depth_argument(pose, depth_maps))
+            self._account_losses(ef, imf, mask)
+            return out
 
         for item in batches:
             events_list, images = item[0], item[1]
@@ -150,7 +197,7 @@ class SameTimeEvaluator:
                 rep, mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage, on_stage_stream=True,
                                                         representation_type=self.representation_type)
                 self.last_inputs = (rep, mask)  # of the batch enqueued last (results lag by up to depth - 1 batches)
-                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose, depth_maps))
+                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose, depth_maps, mask))
             k += 1
             if len(pending) >= depth:
                 yield finish(pending.popleft())
@@ -174,6 +221,16 @@ class SameTimeEvaluator:
         out = dict(zip(self.names, mean))
         if self.he_thresh is not None:
             out.update(_gathered_summary(self._he_rows, len(self.he_thresh) + 2, he_summary, self.he_thresh))
+        if self.losses is not None:
+            self._fold_losses()
+            if self._loss_sums is None:  # no batch yet: zeros, so that every rank of a process group still takes part below
+                ls, lc = torch.zeros(3, dtype=torch.float64, device=s.device), torch.zeros(3, dtype=torch.float64, device=s.device)
+            else:
+                ls, lc = self._loss_sums.clone(), self._loss_counts.clone()
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                torch.distributed.all_reduce(ls)
+                torch.distributed.all_reduce(lc)
+            out.update(zip(LOSS_NAMES, (ls / lc).tolist()))  # no finite value for a key: NaN, as the mean of nothing
         return out
 
 
@@ -272,7 +329,10 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
     """
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
-                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid"):
+                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None):
+        if losses is not None:
+            raise ValueError("einx: DifferentTimeEvaluator takes no losses: its two views are not aligned pixel by pixel, which is what "
+                             "the extractor losses compare (SameTimeEvaluator does)")
         super().__init__(model, bins, resolution, mma_thr, vdd_thr, he_thresh, he_ransac_thresh, he_conf, representation_type)
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)

@@ -649,6 +649,44 @@ int einx_gt_matches(const einx_gt_matches_params* p, const float* kp0, const flo
 int einx_match_pr(const int64_t* matches0, const float* scores0, const int64_t* gt_matches0, const int32_t* n, int B, int cap0, double* out,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Forward values of the extractor losses (csrc/loss.hip): validation under no_grad, no autograd.
+ *   ScoreLoss, LogitsLoss, DescriptorsLoss (mse / mae / cosine_similarity), FeatureLoss      core/loss/extractor_loss.py:6-383
+ * Every call writes out [B,2] float64 = one (sum, count) pair per image: the reference's (pooled) loss value is
+ * weight * sum_b(sum) / sum_b(count), a per-pair value weight * sum_b / count_b (count 0 gives NaN, as the reference's 0 / 0).
+ * Every term is added in float64; partial sums go through the caller's workspace and are added in a fixed order: no atomics,
+ * bit-identical run to run.  Nothing synchronises or allocates; every call can be captured.  ws: aligned to 256 bytes.
+ * Masks: mask_type EINX_MASK_NONE (mask NULL, every weight 1), EINX_MASK_U8 (non-zero = 1) or EINX_MASK_F32 (weights).
+ *
+ * einx_desc_loss: DescriptorsLoss on `normalized_descriptors` of two extractor outputs WITHOUT materialising the [B,D,H,W] maps.
+ *   raw_a / raw_b [B,D,hc,wc] with their descriptor_scale_factor; Hp, Wp, h0, w0, H, W as einx_upsample_normalize; cell 8
+ *   (bilinear upsample + normalise, cropped) or 1 (hc == Hp, wc == Wp: normalise, cropped); mask [B,H,W].  The elements a (of
+ *   side a) and b formed in registers equal, bit for bit, what einx_upsample_normalize / einx_normalize_map would have stored.
+ *   MAE: sum = sum w |a - b|, MSE: sum = sum w (a - b)^2 (difference and square rounded to float32, as torch does), count =
+ *   D * sum w.  COS: sum = sum_pixels w dot / (max(|a|, 1e-8) max(|b|, 1e-8)) in float64, count = sum w (H * W without a mask);
+ *   the module returns 1 - sum / count.  Geometries that einx_upsample_normalize gives to its band kernel (W > 384, wc > 63,
+ *   unusual scales) materialise both maps in the workspace and reduce them with einx_map_loss's kernel: same result contract.
+ * einx_map_loss: x, y [B,C,P] float32 (contiguous); mask [B,P] (broadcast over C; count = C * sum w) or, with mask_full, [B,C,P]
+ *   (count = sum w).  SQ / ABS as above; BCE: x = probability, target t = (y > 0), term -(t max(log x, -100) +
+ *   (1 - t) max(log(1 - x), -100)) with the logarithms in float64; COS: cosine over C per position ([B,P] mask only).
+ * einx_logits_loss: LogitsLoss.  x, y [B,C,hc,wc], channels 0 .. cell^2 - 1 only; element (c, yc, xc) is pixel
+ *   (cell yc + c / cell, cell xc + c % cell) (pixel_shuffle), kept inside the crop window [h0, h0 + H) x [w0, w0 + W)
+ *   (Padder.unpad) and weighted by mask [B,H,W] at its cropped position; count = elements in the window, masked or not (the
+ *   reference's mean).  Workspace: einx_map_loss_ws_bytes(B, hc * wc).
+ * ---------------------------------------------------------------------------------------- */
+enum { EINX_MASK_NONE = 0, EINX_MASK_U8 = 1, EINX_MASK_F32 = 2 };
+enum { EINX_LOSS_MAE = 0, EINX_LOSS_MSE = 1, EINX_LOSS_COS = 2 };
+enum { EINX_MAP_SQ = 0, EINX_MAP_ABS = 1, EINX_MAP_BCE = 2, EINX_MAP_COS = 3 };
+size_t einx_desc_loss_ws_bytes(int B, int D, int hc, int wc, int Hp, int Wp, int h0, int w0, int H, int W, int cell); /* 0 on a bad shape */
+int einx_desc_loss(const float* raw_a, float scale_a, const float* raw_b, float scale_b, int B, int D, int hc, int wc, int Hp, int Wp,
+                   int h0, int w0, int H, int W, int cell, const void* mask, int mask_type, int mode, double* out, void* ws,
+                   size_t ws_bytes, void* stream);
+size_t einx_map_loss_ws_bytes(int B, int P);
+int einx_map_loss(const float* x, const float* y, int B, int C, int P, const void* mask, int mask_type, int mask_full, int mode,
+                  double* out, void* ws, size_t ws_bytes, void* stream);
+int einx_logits_loss(const float* x, const float* y, int B, int C, int cell, int hc, int wc, int h0, int w0, int H, int W,
+                     const void* mask, int mask_type, double* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
