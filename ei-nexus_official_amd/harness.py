@@ -13,7 +13,17 @@
 
                --(gt_matches.hip, DifferentTimeEvaluator with poses and depth maps)--> ground-truth matches of the keypoints,
                   match_recall / match_precision / accuracy / average_precision per pair --> means (all-reduced across ranks)
+
+               --(loss.hip, SameTimeEvaluator with losses)--> the two extractor losses per pair --> means (all-reduced across ranks)
+
+Every batch is a `_Batch`, whichever entry point it came through: `step` and `run` differ only in how they enqueue it
+(`_enqueue_batch`), and finish it the same way (`_finish_batch`: the model's host side, `_account`, `_account_losses`).  What
+ends as a mean (metrics, losses, precision / recall) goes through one `_RunningMean` each; what ends as an AUC keeps its rows
+(`_he_rows`, `_pose_rows`, `_gathered_summary`).
 """
+from collections import deque
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
@@ -23,6 +33,65 @@ from .datasets.representations import EventStage, build_representation, events_r
 
 
 LOSS_NAMES = ("extractor_keypoints_loss", "extractor_descriptor_loss", "loss")  # val_extractor.py:167-172 (VAL_ prefix added there)
+
+
+def _grouped():
+    """a process group is up: `result()` takes part in its collectives"""
+    return torch.distributed.is_available() and torch.distributed.is_initialized()
+
+
+class _Batch(NamedTuple):
+    """the arguments of `step`, and an item of `run` (a plain tuple of the first 2 to 5 of them, in this order)"""
+    events_list: list
+    images: torch.Tensor
+    homography: Optional[torch.Tensor] = None
+    pose: Optional[tuple] = None
+    depth: Optional[tuple] = None
+
+
+class _RunningMean:
+    """Column means of per-pair float64 rows [B,width] that stay on the device.  `add` only keeps the batch's rows: they are
+    folded into sums and counts lazily, 64 batches at a time (concatenated, summed, added to the running sums) -- eight small
+    reductions per batch on the forward's stream were a third of what the evaluation loop cost on top of the forward
+    (profiles/r06_notes.md 3).  An entry is skipped when it is NaN, or with `finite_only` when it is not finite; an infinity that
+    is not skipped counts as nan_to_num's largest float."""
+
+    def __init__(self, width, finite_only=False):
+        self.width, self.finite_only = width, finite_only
+        self.pending, self.sums, self.counts = [], None, None
+
+    def add(self, rows):
+        self.pending.append(rows)
+        if len(self.pending) >= 64:
+            self.fold()
+
+    def fold(self):
+        if not self.pending:
+            return
+        rows = torch.cat(self.pending, 0)
+        self.pending = []
+        ok = torch.isfinite(rows) if self.finite_only else ~torch.isnan(rows)
+        s, c = torch.where(ok, torch.nan_to_num(rows), 0.0).sum(0), ok.sum(0).double()
+        self.sums = s if self.sums is None else self.sums + s
+        self.counts = c if self.counts is None else self.counts + c
+
+    def reduced(self, device):
+        """(sums, counts) over every rank.  Nothing added here: zeros on `device`, so that this rank still takes part -- a rank
+        that skipped the collective would leave the others waiting in it."""
+        self.fold()
+        if self.sums is None:
+            s, c = (torch.zeros(self.width, dtype=torch.float64, device=device) for _ in range(2))
+        else:
+            s, c = self.sums.clone(), self.counts.clone()
+        if _grouped():
+            torch.distributed.all_reduce(s)
+            torch.distributed.all_reduce(c)
+        return s, c
+
+    @staticmethod
+    def means(sums, counts, empty_is_nan=False):
+        """a column in which nothing was counted gives 0.0, or with `empty_is_nan` NaN, as the mean of nothing"""
+        return (sums / (counts if empty_is_nan else counts.clamp_min(1))).tolist()
 
 
 class SameTimeEvaluator:
@@ -44,8 +113,7 @@ class SameTimeEvaluator:
         extractor_keypoints_loss, extractor_descriptor_loss and loss (their per-pair sum): each the mean over the pairs where it is
         finite (:183-186)."""
         self.losses = losses
-        self._loss_rows = []
-        self._loss_sums = self._loss_counts = None
+        self._loss_mean = _RunningMean(len(LOSS_NAMES), finite_only=True)
         self.he_thresh = None if he_thresh is None else tuple(he_thresh)
         self.he_ransac_thresh, self.he_conf = float(he_ransac_thresh), float(he_conf)
         self._he_rows = []
@@ -57,34 +125,55 @@ class SameTimeEvaluator:
         self.resolution = tuple(int(v) for v in resolution)
         self.mma_thr, self.vdd_thr = tuple(mma_thr), tuple(vdd_thr)
         self.names = metric_names(self.mma_thr, self.vdd_thr)
-        self._sums = None
-        self._counts = None
-        self._rows = []
+        self._metric_mean = _RunningMean(len(self.names))
+        self._stages = {}  # (slot, on its own stream, device) -> EventStage
         self.pairs = 0
 
     @torch.no_grad()
     def step(self, events_list, images, homography=None):
         """events_list: B dicts {"x","y","t","p"} of numpy arrays; images: [B,1,H,W] float (0..255) on the device
         (scaled in place by SuperPoint exactly like the reference).  Returns the per-pair metric rows [B,K] (device)."""
-        return self._step(events_list, images, homography, None)
+        return self._step(_Batch(events_list, images, homography))
 
-    def _step(self, events_list, images, homography, pose, depth=None):
+    def _step(self, batch):
+        self._validate(batch)
+        return self._finish_batch(batch, *self._enqueue_batch(batch, 0, on_stage_stream=False))  # synchronous: its stage is free again
+
+    def _validate(self, batch):
+        """the same-time evaluation has no use for depth maps, so a batch that carries some is an error, not something to drop
+        silently"""
+        if batch.depth is not None:
+            raise ValueError(f"einx: {type(self).__name__} takes no depth maps (DifferentTimeEvaluator does, together with pose=)")
+
+    def _enqueue_batch(self, batch, slot, on_stage_stream):
+        """Device side of one batch, nothing waits: raw events -> representation -> both networks and the matcher.  Returns what
+        `_finish_batch` takes after the batch.
+        on_stage_stream=False (`step`): the image network does not depend on the events, so it is enqueued FIRST and the host packs /
+        uploads the raw events (38 MB, ~2.5 ms) under its ~4 ms of device work; the event network follows (round 6: 11.7 -> see
+        profiles/r06_notes.md).
+        on_stage_stream=True (`run`): upload AND representation kernels of batch i + 1 on the stage's own stream: they run beside
+        batch i's convolutions (0.3 ms of memory- / latency-bound kernels per batch leave the main stream's chain).  (Every
+        in-flight slot on a stream of its own, so that batch i's tail could overlap batch i + 1's head, measured the same: 8.89
+        vs 8.84 ms per batch, profiles/r06_notes.md.)"""
         W, H = self.resolution
-        dev = images.device
-        if not hasattr(self, "_stages"):
-            self._stages = {}
+        dev = batch.images.device
         with torch.cuda.device(dev):
-            stage = self._stages.get(("step", dev))
-            if stage is None:  # page-locked upload path (the call is synchronous: the stage is free again when it returns)
-                stage = self._stages[("step", dev)] = EventStage(dev)
-            # the image network does not depend on the events: it is enqueued FIRST and the host packs / uploads the raw events
-            # (38 MB, ~2.5 ms) under its ~4 ms of device work; the event network follows (round 6: 11.7 -> see profiles/r06_notes.md)
-            im = self.model.enqueue_image(images, None)
-            events_rep, events_mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage,
-                                                                  representation_type=self.representation_type)
-            self.last_inputs = (events_rep, events_mask)  # what the extractors saw (deterministic since round 4: bit-equal run to run)
-            ef, imf, matches = self.model._finish(self.model._enqueue(events_rep, images, events_mask, image_feats=im))
-        out = self._account(ef, imf, matches, homography, pose, **self._depth_argument(pose, depth))
+            stage = self._stages.get((slot, on_stage_stream, dev))
+            if stage is None:  # page-locked upload path
+                stage = self._stages[(slot, on_stage_stream, dev)] = EventStage(dev)
+            im = None if on_stage_stream else self.model.enqueue_image(batch.images, None)
+            rep, mask = events_representation_batch(batch.events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage,
+                                                    on_stage_stream=on_stage_stream, representation_type=self.representation_type)
+            # what the extractors saw (deterministic since round 4: bit-equal run to run); in `run`: of the batch enqueued last
+            # (results lag by up to depth - 1 batches)
+            self.last_inputs = (rep, mask)
+            return self.model._enqueue(rep, batch.images, mask, slot=slot, image_feats=im), mask
+
+    def _finish_batch(self, batch, pending, events_mask):
+        """Host side of one batch: wait for the model's counts, then enqueue everything that is evaluated on its result"""
+        with torch.cuda.device(batch.images.device):
+            ef, imf, matches = self.model._finish(pending)
+        out = self._account(ef, imf, matches, batch)
         self._account_losses(ef, imf, events_mask)
         return out
 
@@ -103,57 +192,32 @@ class SameTimeEvaluator:
                 cols.append(torch.full((bf.B,), float("nan"), dtype=torch.float64, device=bf.raw.device))
             else:
                 cols.append(pair_values(ef, imf, events_mask, padder))
-        self._loss_rows.append(torch.stack([cols[0], cols[1], cols[0] + cols[1]], 1))
-        if len(self._loss_rows) >= 64:
-            self._fold_losses()
+        self._loss_mean.add(torch.stack([cols[0], cols[1], cols[0] + cols[1]], 1))
 
-    def _fold_losses(self):
-        if not self._loss_rows:
-            return
-        rows = torch.cat(self._loss_rows, 0)
-        self._loss_rows = []
-        ok = torch.isfinite(rows)
-        s, c = torch.where(ok, rows, torch.zeros_like(rows)).sum(0), ok.sum(0).double()
-        self._loss_sums = s if self._loss_sums is None else self._loss_sums + s
-        self._loss_counts = c if self._loss_counts is None else self._loss_counts + c
-
-    def _account(self, ef, imf, matches, homography, pose=None):
-        rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, homography, self.mma_thr, self.vdd_thr)
-        # the running sums are folded lazily (`_fold`): eight small reductions per batch on the forward's stream were a third of
-        # what the evaluation loop cost on top of the forward (profiles/r06_notes.md 3)
-        self._rows.append(rows)
-        if len(self._rows) >= 64:
-            self._fold()
+    def _account(self, ef, imf, matches, batch):
+        # the matcher's result is read from the model AFTER its _finish, which may have re-run the matcher (NMS retry)
+        rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, batch.homography, self.mma_thr, self.vdd_thr)
+        self._metric_mean.add(rows)
         self.pairs += rows.shape[0]
-        if self.he_thresh is not None and homography is not None:
+        if self.he_thresh is not None and batch.homography is not None:
             mr = self.model._last_match
             key = (tuple(ef._batched.image_size), mr.mk0.shape[0], mr.mk0.device)
             shape = self._he_shapes.get(key)
             if shape is None:  # (H, W) of the forward for every pair, uploaded once
                 shape = self._he_shapes[key] = torch.tensor([key[0]] * key[1], dtype=torch.int32, device=key[2])
-            self._he_rows.append(batch_homography(mr, shape, homography, self.he_ransac_thresh, self.he_conf, ordering=ef._batched.ordering,
+            self._he_rows.append(batch_homography(mr, shape, batch.homography, self.he_ransac_thresh, self.he_conf, ordering=ef._batched.ordering,
                                                   he_thr=self.he_thresh)[3])
         return rows, (ef, imf, matches)
 
-    def _fold(self):
-        if not self._rows:
-            return
-        rows = torch.cat(self._rows, 0) if len(self._rows) > 1 else self._rows[0]
-        self._rows = []
-        ok = ~torch.isnan(rows)
-        z = torch.nan_to_num(rows)
-        self._sums = z.sum(0) if self._sums is None else self._sums + z.sum(0)
-        self._counts = ok.sum(0).double() if self._counts is None else self._counts + ok.sum(0).double()
-
     @property
     def sums(self):
-        self._fold()
-        return self._sums
+        self._metric_mean.fold()
+        return self._metric_mean.sums
 
     @property
     def counts(self):
-        self._fold()
-        return self._counts
+        self._metric_mean.fold()
+        return self._metric_mean.counts
 
     @torch.no_grad()
     def run(self, batches, depth=2):
@@ -163,74 +227,27 @@ class SameTimeEvaluator:
         non-blocking copies and its kernels enqueued (EIM.forward_stream's mechanism) BEFORE the host waits for batch i's
         counts, so packing and the PCIe transfer hide under the device's work instead of adding to it.  Same kernels, same
         results as `step`; every `images` tensor must stay untouched until its result has been yielded."""
-        from collections import deque
-        W, H = self.resolution
         depth = max(int(depth), 1)
         pending = deque()
-        if not hasattr(self, "_stages"):
-            self._stages = {}
-        k = 0
-
-        def finish(entry):
-            p, hom, pose, depth_maps, mask = entry
-            ef, imf, matches = self.model._finish(p)
-            out = self._account(ef, imf, matches, hom, pose, **self._depth_argument(pose, depth_maps))
-            self._account_losses(ef, imf, mask)
-            return out
-
-        for item in batches:
-            events_list, images = item[0], item[1]
-            homography = item[2] if len(item) > 2 else None
-            pose = item[3] if len(item) > 3 else None
-            depth_maps = item[4] if len(item) > 4 else None
-            self._depth_argument(pose, depth_maps)  # raises before anything is enqueued
-            slot = k % depth
-            dev = images.device
-            with torch.cuda.device(dev):
-                stage = self._stages.get((slot, dev))
-                if stage is None:
-                    stage = self._stages[(slot, dev)] = EventStage(dev)
-                # upload AND representation kernels of batch i + 1 on the stage's own stream: they run beside batch i's
-                # convolutions (0.3 ms of memory- / latency-bound kernels per batch leave the main stream's chain).  (Every
-                # in-flight slot on a stream of its own, so that batch i's tail could overlap batch i + 1's head, measured the
-                # same: 8.89 vs 8.84 ms per batch, profiles/r06_notes.md.)
-                rep, mask = events_representation_batch(events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage, on_stage_stream=True,
-                                                        representation_type=self.representation_type)
-                self.last_inputs = (rep, mask)  # of the batch enqueued last (results lag by up to depth - 1 batches)
-                pending.append((self.model._enqueue(rep, images, mask, slot=slot), homography, pose, depth_maps, mask))
-            k += 1
+        for k, item in enumerate(batches):
+            batch = _Batch(*item)
+            self._validate(batch)  # raises before anything of the batch is enqueued
+            pending.append((batch, *self._enqueue_batch(batch, k % depth, on_stage_stream=True)))
             if len(pending) >= depth:
-                yield finish(pending.popleft())
+                yield self._finish_batch(*pending.popleft())
         while pending:
-            yield finish(pending.popleft())
-
-    def _depth_argument(self, pose, depth):
-        """what `_account` is given for the depth maps of a batch: nothing here -- the same-time evaluation has no use for them,
-        so an item that carries some is an error, not something to drop silently; DifferentTimeEvaluator passes them on"""
-        if depth is not None:
-            raise ValueError(f"einx: {type(self).__name__} takes no depth maps (DifferentTimeEvaluator does, together with pose=)")
-        return {}
+            yield self._finish_batch(*pending.popleft())
 
     def result(self):
         """Mean of every metric over the pairs seen so far; sums are all-reduced when a process group is up."""
-        s, c = self.sums.clone(), self.counts.clone()
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            torch.distributed.all_reduce(s)
-            torch.distributed.all_reduce(c)
-        mean = (s / c.clamp_min(1)).tolist()
-        out = dict(zip(self.names, mean))
+        if self.sums is None:
+            raise RuntimeError("einx: result() before the first batch")
+        dev = self.sums.device
+        out = dict(zip(self.names, _RunningMean.means(*self._metric_mean.reduced(dev))))
         if self.he_thresh is not None:
             out.update(_gathered_summary(self._he_rows, len(self.he_thresh) + 2, he_summary, self.he_thresh))
-        if self.losses is not None:
-            self._fold_losses()
-            if self._loss_sums is None:  # no batch yet: zeros, so that every rank of a process group still takes part below
-                ls, lc = torch.zeros(3, dtype=torch.float64, device=s.device), torch.zeros(3, dtype=torch.float64, device=s.device)
-            else:
-                ls, lc = self._loss_sums.clone(), self._loss_counts.clone()
-            if torch.distributed.is_available() and torch.distributed.is_initialized():
-                torch.distributed.all_reduce(ls)
-                torch.distributed.all_reduce(lc)
-            out.update(zip(LOSS_NAMES, (ls / lc).tolist()))  # no finite value for a key: NaN, as the mean of nothing
+        if self.losses is not None:  # no finite value for a key: NaN
+            out.update(zip(LOSS_NAMES, _RunningMean.means(*self._loss_mean.reduced(dev), empty_is_nan=True)))
         return out
 
 
@@ -238,7 +255,7 @@ def gather_rows(rows):
     """[P,K] per-pair rows of this rank (pose rows: K = 4, homography rows: K = thresholds + 2; the same K on every rank) -> the
     rows of every rank (concatenated in rank order).  An AUC cannot be all-reduced from sums: the rows are all-gathered, padded
     to the largest count (on the CPU under gloo)."""
-    if not (torch.distributed.is_available() and torch.distributed.is_initialized()):
+    if not _grouped():
         return rows
     world = torch.distributed.get_world_size()
     dev = rows.device if torch.distributed.get_backend() == "nccl" else torch.device("cpu")
@@ -333,70 +350,42 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         if losses is not None:
             raise ValueError("einx: DifferentTimeEvaluator takes no losses: its two views are not aligned pixel by pixel, which is what "
                              "the extractor losses compare (SameTimeEvaluator does)")
-        super().__init__(model, bins, resolution, mma_thr, vdd_thr, he_thresh, he_ransac_thresh, he_conf, representation_type)
+        super().__init__(model, bins, resolution=resolution, mma_thr=mma_thr, vdd_thr=vdd_thr, he_thresh=he_thresh,
+                         he_ransac_thresh=he_ransac_thresh, he_conf=he_conf, representation_type=representation_type)
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
         self._pose_rows = []
-        self._pr_rows = []
-        self._pr_sums = self._pr_counts = None
+        self._pr_mean = _RunningMean(len(MATCH_PR_NAMES))  # of the [B,4] matcher_metrics rows (a pair without keypoints has NaN rows)
         self.gt_pos_th, self.gt_neg_th = 3, 5  # gt_matches_from_pose_depth's defaults, as val_matcher.py calls it
         self.last_gt = None
 
     @torch.no_grad()
     def step(self, events_list, images, homography=None, pose=None, depth=None):
-        self._depth_argument(pose, depth)
-        return self._step(events_list, images, homography, pose, depth)
+        return self._step(_Batch(events_list, images, homography, pose, depth))
 
-    def _depth_argument(self, pose, depth):
-        if depth is not None and pose is None:
+    def _validate(self, batch):
+        if batch.depth is not None and batch.pose is None:
             raise ValueError("einx: depth=(depth0, depth1) needs pose=(K0, K1, T_0to1): ground-truth matches come from depth AND motion")
-        return {} if depth is None else {"depth": depth}
 
-    def _account(self, ef, imf, matches, homography, pose=None, depth=None):
-        out = super()._account(ef, imf, matches, homography)
-        if depth is not None:
-            K0, K1, T = pose
-            mr = self.model._last_match
-            self.last_gt = batch_gt_matches(ef._batched, imf._batched, depth[0], depth[1], K0, K1, T, None, self.gt_pos_th, self.gt_neg_th)
-            self._pr_rows.append(match_pr(mr, self.last_gt["matches0"], ef._batched.det.counts))
-            if len(self._pr_rows) >= 64:
-                self._fold_pr()
-        if pose is not None:
-            K0, K1, T = pose
-            _, _, _, _, prow = batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
-                                                   ordering=ef._batched.ordering)
-            self._pose_rows.append(prow)
+    def _account(self, ef, imf, matches, batch):
+        out = super()._account(ef, imf, matches, batch)
+        if batch.depth is not None:
+            K0, K1, T = batch.pose
+            self.last_gt = batch_gt_matches(ef._batched, imf._batched, batch.depth[0], batch.depth[1], K0, K1, T, None, self.gt_pos_th,
+                                            self.gt_neg_th)
+            self._pr_mean.add(match_pr(self.model._last_match, self.last_gt["matches0"], ef._batched.det.counts))
+        if batch.pose is not None:
+            K0, K1, T = batch.pose
+            self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
+                                                       ordering=ef._batched.ordering)[4])
         return out
-
-    def _fold_pr(self):
-        """NaN-aware sums and counts of the [B,4] matcher_metrics rows (a pair without keypoints has NaN rows)"""
-        if not self._pr_rows:
-            return
-        rows = torch.cat(self._pr_rows, 0)
-        self._pr_rows = []
-        ok = ~torch.isnan(rows)
-        s, c = torch.nan_to_num(rows).sum(0), ok.sum(0).double()
-        self._pr_sums = s if self._pr_sums is None else self._pr_sums + s
-        self._pr_counts = c if self._pr_counts is None else self._pr_counts + c
 
     def result(self):
         out = super().result()
         out.update(_gathered_summary(self._pose_rows, 4, rpe_summary, self.pose_thresh))
-        self._fold_pr()
-        grouped = torch.distributed.is_available() and torch.distributed.is_initialized()
-        if self._pr_sums is not None or grouped:
-            # under a process group EVERY rank reduces, with zeros if it was given no depth: a rank that skipped the collective
-            # would leave the others waiting in it (as _gathered_summary does for the pose rows)
-            if self._pr_sums is None:
-                dev = self.sums.device if self.sums is not None else "cpu"
-                s, c = torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(4, dtype=torch.float64, device=dev)
-            else:
-                s, c = self._pr_sums.clone(), self._pr_counts.clone()
-            if grouped:
-                torch.distributed.all_reduce(s)
-                torch.distributed.all_reduce(c)
-            if float(c.max()) > 0:  # some rank labelled a pair that has keypoints
-                out.update(zip(MATCH_PR_NAMES, (s / c.clamp_min(1)).tolist()))
+        s, c = self._pr_mean.reduced(self.sums.device)
+        if float(c.max()) > 0:  # some rank labelled a pair that has keypoints
+            out.update(zip(MATCH_PR_NAMES, _RunningMean.means(s, c)))
         return out
 
     def pose_inputs(self, matches, b=0):

@@ -190,10 +190,13 @@ def test_pose_and_camera_holders():
 def test_same_time_evaluator_refuses_depth():
     """a same-time item that carries depth maps is an error, not something dropped silently; the different-time evaluator wants
     the pose beside them (host logic only: no device is touched)"""
+    H = import_module(pkg.__name__ + ".harness")
     same, diff = object.__new__(pkg.SameTimeEvaluator), object.__new__(pkg.DifferentTimeEvaluator)
-    assert same._depth_argument(None, None) == {} and diff._depth_argument(None, None) == {}
+    batch = lambda pose, depth: H._Batch([], None, None, pose, depth)  # noqa: E731
+    same._validate(batch(None, None))  # accepted: does not raise
+    diff._validate(batch(None, None))
     with pytest.raises(ValueError, match="SameTimeEvaluator takes no depth"):
-        same._depth_argument(("K0", "K1", "T"), ("d0", "d1"))
+        same._validate(batch(("K0", "K1", "T"), ("d0", "d1")))
     with pytest.raises(ValueError, match="pose"):
-        diff._depth_argument(None, ("d0", "d1"))
-    assert diff._depth_argument(("K0", "K1", "T"), ("d0", "d1")) == {"depth": ("d0", "d1")}
+        diff._validate(batch(None, ("d0", "d1")))
+    diff._validate(batch(("K0", "K1", "T"), ("d0", "d1")))

@@ -390,9 +390,9 @@ def test_match_pr_and_matcher_metrics_against_fixture():
 
 
 # ------------------------------------------------------------------------------------------------ the evaluation harness
-def test_different_time_evaluator_with_depth():
-    """two SP+MNN batches of 4 synthetic pairs at 346 x 260 with scene depth and pose: the result() means equal the mean of
-    matcher_metrics(restatement labels) over the same pairs; the returned rows are byte-equal to a run without depth"""
+@pytest.fixture(scope="module")
+def depth_batches():
+    """an SP+MNN model and two batches of 4 synthetic pairs at 346 x 260 with scene depth and pose: (H, W, B, bins, model, batches)"""
     H, Wd, B, bins = 260, 346, 4, 5
     cfg = pkg.default_config("SP_MNN", event_channels=bins)
     model = pkg.EIM(cfg, device=DEV).eval()
@@ -404,6 +404,13 @@ def test_different_time_evaluator_with_depth():
         img = synth.synth_image(90 + k, B, H, Wd)
         sc = R.scene(40 + k, B, 4, 4, (H, Wd), (H, Wd), f0=256.0, f1=256.0, n_corr=0)
         batches.append((evs, img, sc))
+    return H, Wd, B, bins, model, batches
+
+
+def test_different_time_evaluator_with_depth(depth_batches):
+    """the batches of `depth_batches`: the result() means equal the mean of matcher_metrics(restatement labels) over the same pairs;
+    the returned rows are byte-equal to a run without depth"""
+    H, Wd, B, bins, model, batches = depth_batches
     with_depth = pkg.DifferentTimeEvaluator(model, bins=bins, resolution=(Wd, H))
     without = pkg.DifferentTimeEvaluator(model, bins=bins, resolution=(Wd, H))
     assert with_depth.last_gt is None
@@ -445,3 +452,35 @@ def test_different_time_evaluator_with_depth():
     res_run = runner.result()
     for k in ("match_recall", "match_precision", "accuracy", "average_precision"):
         assert res_run[k] == res[k]
+
+
+def test_different_time_evaluator_with_homography_pose_and_depth_at_once(depth_batches):
+    """every feature of the evaluator in one batch -- a per-pair homography with he_thresh, pose and depth: `step` and `run` give
+    the same result() key for key, each key a single-feature evaluator reports has the combined evaluator's value, and the
+    returned rows are byte-equal across all of them (everything is seeded and deterministic)"""
+    H, Wd, B, bins, model, batches = depth_batches
+    hom = _t(np.tile(np.array([[1.01, 0.01, -2.0], [-0.01, 0.99, 1.5], [1e-5, -1e-5, 1.0]], np.float32), (B, 1, 1)))
+    make = lambda **kw: pkg.DifferentTimeEvaluator(model, bins=bins, resolution=(Wd, H), **kw)  # noqa: E731
+    same = lambda a, b: a == b or (a != a and b != b)  # noqa: E731
+    full = [(evs, img, (_t(sc["K0"]), _t(sc["K1"]), _t(sc["T01"])), (_t(sc["depth0"]), _t(sc["depth1"]))) for evs, img, sc in batches]
+    stepped, streamed = make(he_thresh=(3, 5, 10)), make(he_thresh=(3, 5, 10))
+    singles = {"homography": (make(he_thresh=(3, 5, 10)), False, False), "pose": (make(), True, False), "depth": (make(), True, True)}
+    rows = [stepped.step(evs, _t(img), hom, pose=pose, depth=depth)[0] for evs, img, pose, depth in full]
+    rows_run = [r for r, _ in streamed.run([(evs, _t(img), hom, pose, depth) for evs, img, pose, depth in full], depth=2)]
+    assert len(rows_run) == len(rows) == 2
+    for r0, r1 in zip(rows, rows_run):
+        assert _np(r0).tobytes() == _np(r1).tobytes()
+    res, res_run = stepped.result(), streamed.result()
+    assert list(res) == list(res_run)
+    for k in res:
+        assert same(res[k], res_run[k]), (k, res[k], res_run[k])
+    pr, he, rpe = set(M.MATCH_PR_NAMES), {k for k in res if k.startswith("HE")}, {k for k in res if k.startswith("RPE")}
+    assert len(he) == 8 and len(rpe) == 10 and pr <= set(res) and set(res) == set(stepped.names) | he | rpe | pr
+    for name, (ev, with_pose, with_depth) in singles.items():
+        for (evs, img, pose, depth), r0 in zip(full, rows):
+            r1, _ = ev.step(evs, _t(img), hom, pose=pose if with_pose else None, depth=depth if with_depth else None)
+            assert _np(r0).tobytes() == _np(r1).tobytes(), name
+        one = ev.result()
+        assert set(one) == set(stepped.names) | (he if name == "homography" else rpe | pr if with_depth else rpe), name
+        for k in one:
+            assert same(one[k], res[k]), (name, k, one[k], res[k])

@@ -380,7 +380,9 @@ def test_nothing_writes_past_the_workspace_query_and_a_short_workspace_is_refuse
 
 
 # ------------------------------------------------------------------------------------------ the evaluation harness
-def test_same_time_evaluator_reports_the_validation_losses():
+@pytest.fixture(scope="module")
+def loss_batches():
+    """(model, the losses of train_stage1.yaml, two batches of raw events and images at B0 x H0 x W0)"""
     import json
     import os
     from helpers import GOLDEN
@@ -388,13 +390,18 @@ def test_same_time_evaluator_reports_the_validation_losses():
         cfg = json.load(f)["train_stage1.yaml"]
     _, model, _ = _eim_model("SP_MNN", seed=11)
     losses = L.build_losses(pkg.configs.to_attr(cfg))
-    kp, ds = losses["keypoints_loss"], losses["descriptors_loss"]
-    assert (kp.mode, ds.mode, ds.desc_type) == ("mse", "mae", "normalized")
     batches = []
     for k in range(2):
         evs = [synth_raw_events(dict(seed=500 + 10 * k + b, n=300 if (k, b) == (1, 2) else 2500, H=H0, W=W0, bins=5, frac=False, pneg=False))
                for b in range(B0)]
         batches.append((evs, synth.synth_image(70 + k, B0, H0, W0)))
+    return model, losses, batches
+
+
+def test_same_time_evaluator_reports_the_validation_losses(loss_batches):
+    model, losses, batches = loss_batches
+    kp, ds = losses["keypoints_loss"], losses["descriptors_loss"]
+    assert (kp.mode, ds.mode, ds.desc_type) == ("mse", "mae", "normalized")
     with_losses = pkg.SameTimeEvaluator(model, bins=5, resolution=(W0, H0), losses=losses)
     plain = pkg.SameTimeEvaluator(model, bins=5, resolution=(W0, H0))
     per = {n: [] for n in ("extractor_keypoints_loss", "extractor_descriptor_loss", "loss")}
@@ -437,3 +444,24 @@ def test_same_time_evaluator_reports_the_validation_losses():
     assert np.isnan(r3["extractor_keypoints_loss"]) and np.isnan(r3["loss"]) and np.isfinite(r3["extractor_descriptor_loss"])
     with pytest.raises(ValueError, match="takes no losses"):
         pkg.DifferentTimeEvaluator(model, bins=5, resolution=(W0, H0), losses=losses)
+
+
+def test_same_time_evaluator_with_homography_and_losses_step_equals_run(loss_batches):
+    """he_thresh and losses together, a homography per batch: `step` and `run` give the same result() key for key, and the loss keys
+    are those of an evaluator that accounts the losses alone"""
+    model, losses, batches = loss_batches
+    hom = _t(np.tile(np.array([[1.01, 0.01, -2.0], [-0.01, 0.99, 1.5], [1e-5, -1e-5, 1.0]], np.float32), (B0, 1, 1)))
+    make = lambda **kw: pkg.SameTimeEvaluator(model, bins=5, resolution=(W0, H0), **kw)  # noqa: E731
+    stepped, streamed, alone = make(he_thresh=(3, 5, 10), losses=losses), make(he_thresh=(3, 5, 10), losses=losses), make(losses=losses)
+    for evs, img in batches:
+        stepped.step(evs, _t(img.copy()), hom)
+        alone.step(evs, _t(img.copy()))
+    assert len(list(streamed.run([(evs, _t(img.copy()), hom) for evs, img in batches]))) == 2
+    a, b, c = stepped.result(), streamed.result(), alone.result()
+    loss_keys = ("extractor_keypoints_loss", "extractor_descriptor_loss", "loss")
+    assert list(a) == list(b) and set(a) == set(stepped.names) | {k for k in a if k.startswith("HE")} | set(loss_keys) and len(a) == len(stepped.names) + 8 + 3
+    for k in a:
+        assert a[k] == b[k] or (a[k] != a[k] and b[k] != b[k]), (k, a[k], b[k])
+    for k in loss_keys:
+        assert a[k] == c[k] or (a[k] != a[k] and c[k] != c[k]), (k, a[k], c[k])
+    assert np.isfinite(a["loss"])

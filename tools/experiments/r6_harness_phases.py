@@ -60,7 +60,8 @@ for rep_i in range(3):
 print("forward only again: %s ms" % " ".join("%.3f" % t for t in ts))
 # phases of the loop body, by hand (depth 2)
 from collections import deque
-stage = [rep.EventStage(dev), rep.EventStage(dev)]
+no_homography = importlib.import_module("ei-nexus_official_amd.harness")._Batch(events, None)  # what `_account` reads of a batch
+stage =[rep.EventStage(dev), rep.EventStage(dev)]
 acc = {"pack": 0.0, "rep_enqueue": 0.0, "model_enqueue": 0.0, "finish": 0.0, "account": 0.0, "clone": 0.0}
 pending = deque()
 n = 20
@@ -82,12 +83,12 @@ for k in range(n):
     if len(pending) >= 2:
         r = w.model._finish(pending.popleft())
         t5 = time.perf_counter()
-        ev._account(*r, None)
+        ev._account(*r, no_homography)
         t6 = time.perf_counter()
     for key, a, b in (("clone", t0, t1), ("pack", t1, t2), ("rep_enqueue", t2, t3), ("model_enqueue", t3, t4), ("finish", t4, t5), ("account", t5, t6)):
         acc[key] += (b - a) * 1e3
 while pending:
-    ev._account(*w.model._finish(pending.popleft()), None)
+    ev._account(*w.model._finish(pending.popleft()), no_homography)
 torch.cuda.synchronize()
 print("by hand: %.3f ms per batch; host phases (ms per batch):" % ((time.perf_counter() - T0) / n * 1e3), {k: round(v / n, 3) for k, v in acc.items()})
 # device-only: representation + forward + metrics with everything resident
@@ -99,7 +100,7 @@ for _ in range(20):
     mask = rep.events_mask_batch(events, (346, 260), dev, packed=(x, y, t, p_, offs))
     w.img.copy_(w.img_src)
     r = w.model(grid, w.img, mask)
-    ev._account(*r, None)
+    ev._account(*r, no_homography)
 torch.cuda.synchronize()
 print("resident events -> rep + forward + metrics: %.3f ms per batch" % ((time.perf_counter() - t0) / 20 * 1e3))
 print("pack threads", rep.EventStage.pack_threads())
