@@ -182,6 +182,10 @@ SIGNATURES = {
     "einx_lightglue": (c_int, [ctypes.POINTER(LgWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int, c_void_p]),
+    "einx_lg_assign_nll_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "einx_lg_assign_nll": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p,
+                                   c_void_p]),
     "einx_normalize_rows": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "einx_similarity": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "einx_normalize_keypoints": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p]),

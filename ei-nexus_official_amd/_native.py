@@ -432,6 +432,77 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False)
     return r
 
 
+LG_NLL_COLUMNS = ("S_pos", "num_pos", "S_neg0", "num_neg0", "S_neg1", "num_neg1", "row_sum", "n")
+
+
+def lg_assign_nll(head, x0, x1, gt_matches0, gt_matches1, pos0=None, assignment=None, n=None, m=None):
+    """einx_lg_assign_nll: the sums behind LightGlue's assignment NLL and row_norm for ONE MatchAssignment head, [B,8] float64 =
+    LG_NLL_COLUMNS per pair, no host synchronisation.  head: (proj_w [d,d], proj_b [d], match_w [1,d], match_b [1])
+    fp32 tensors, or an _lib.LgWeights (its last head's pointers).  x0 [B,cap0,d] / x1 [B,cap1,d]: plain tensors, or a MatchResult
+    as x0 (its ref0 / ref1, x1 ignored).  gt_matches0 / 1 int64 [B,cap].  The positives: pos0 int32 [B,cap0] (-1 = none) or a
+    dense bool / uint8 `assignment` [B,cap0,cap1] (any strides).  n / m: int32 [B] counts or None (= cap)."""
+    if isinstance(x0, MatchResult):
+        x0, x1 = x0.ref0, x0.ref1
+    if (pos0 is None) == (assignment is None):
+        raise ValueError("einx: lg_assign_nll takes the positives as pos0= or as assignment=, one of the two")
+    _dev_check(x0, x1)
+    B, cap0, d = x0.shape
+    cap1 = x1.shape[1]
+    dev = x0.device
+    if x1.shape[0] != B or x1.shape[2] != d:
+        raise ValueError("einx: x0 and x1 differ in batch size or width")
+    if isinstance(head, _lib.LgWeights):
+        if int(head.d) != d:
+            raise ValueError("einx: descriptors and head differ in width")
+        hp = (head.proj_w, head.proj_b, head.match_w, head.match_b)
+    else:
+        _dev_check(*head)
+        if tuple(head[0].shape) != (d, d) or head[1].numel() != d or head[2].numel() != d or head[3].numel() != 1:
+            raise ValueError("einx: head weights do not fit descriptors of width %d" % d)
+        hp = tuple(_ptr(t) for t in head)
+    gt0, gt1 = gt_matches0.to(dev, I64).contiguous(), gt_matches1.to(dev, I64).contiguous()
+    if tuple(gt0.shape) != (B, cap0) or tuple(gt1.shape) != (B, cap1):
+        raise ValueError("einx: gt_matches0 / gt_matches1 must be [B,cap0] / [B,cap1]")
+    strides = (0, 0, 0)
+    if pos0 is not None:
+        _dev_check(pos0, dt=I32)
+        if tuple(pos0.shape) != (B, cap0):
+            raise ValueError("einx: pos0 must be [B,cap0]")
+    else:
+        if assignment.dtype == torch.bool:
+            assignment = assignment.view(U8)
+        if assignment.dtype != U8 or assignment.device != dev or tuple(assignment.shape) != (B, cap0, cap1):
+            raise ValueError("einx: assignment must be a bool / uint8 [B,cap0,cap1] tensor on the descriptors' device")
+        strides = tuple(int(v) for v in assignment.stride())
+    for c in (n, m):
+        _dev_check(c, dt=I32)
+    n = torch.full((B,), cap0, dtype=I32, device=dev) if n is None else n
+    m = torch.full((B,), cap1, dtype=I32, device=dev) if m is None else m
+    L = lib()
+    nbytes = L.einx_lg_assign_nll_ws_bytes(B, cap0, cap1, d)
+    if not nbytes:
+        raise NotImplementedError("einx: lg_assign_nll needs B, cap0, cap1 > 0 and a descriptor width that is a multiple of 4")
+    ws = _workspace(nbytes, dev)
+    out = torch.empty((B, len(LG_NLL_COLUMNS)), dtype=torch.float64, device=dev)
+    check(L.einx_lg_assign_nll(*hp, d, _ptr(x0), _ptr(n), cap0, _ptr(x1), _ptr(m), cap1, B, _ptr(gt0), _ptr(gt1), _ptr(pos0), _ptr(assignment),
+                               *strides, _ptr(ws), _ptr(out), _stream(x0)), "einx_lg_assign_nll")
+    return out
+
+
+def lg_nll_values(rows, balancing=0.5):
+    """[B,8] rows of lg_assign_nll -> [B,5] float64 = nll, nll_pos, nll_neg, num_matchable, num_unmatchable, and row_norm [B]
+    (NaN in every column for a pair without keypoints on a side, whose row holds n = 0).  Device arithmetic only."""
+    s_pos, n_pos, s_n0, n_n0, s_n1, n_n1, rs, n = rows.unbind(1)
+    num_pos = n_pos.clamp_min(1.0)
+    den = n_n0.clamp_min(1.0) + n_n1.clamp_min(1.0)
+    nll_pos = -s_pos / num_pos
+    nll_neg = -(s_n0 + s_n1) / den
+    nll = balancing * nll_pos + (1 - balancing) * nll_neg
+    vals = torch.stack([nll, nll_pos, nll_neg, num_pos, den / 2.0, rs / n], 1)  # n == 0: 0 / 0 = NaN in row_norm
+    vals = torch.where((n > 0).unsqueeze(1), vals, vals.new_tensor(float("nan")))
+    return vals[:, :5], vals[:, 5]
+
+
 def similarity(desc0, n, desc1, m):
     """[B,cap0,cap1] descriptor similarity (MNN.py:88); zero outside the first n[b] x m[b] block."""
     _dev_check(desc0, desc1)

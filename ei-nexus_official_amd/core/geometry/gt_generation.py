@@ -30,6 +30,31 @@ def _assignment(pos0, M):
     return a[..., :M]
 
 
+class _LazyAssignment(_Lazy):
+    """the lazy `assignment` entry: besides the function that builds the dense matrix it keeps pos0, which is all that the
+    consumers on the device need of it (LightGlue.loss)"""
+    __slots__ = ("pos0",)
+
+    def __init__(self, pos0, M):
+        super().__init__(lambda d: _assignment(pos0, M))
+        self.pos0 = pos0
+
+
+def lazy_pos0(data, key="assignment"):
+    """pos0 [B,N] int32 behind data[key] while that entry is still lazy (the entry stays lazy); None once it is a tensor"""
+    v = dict.get(data, key) if isinstance(data, dict) else None
+    return v.pos0 if isinstance(v, _LazyAssignment) else None
+
+
+def prefixed(gt, prefix="gt_"):
+    """the dict under the keys the matcher's loss reads (val_matcher.py:82 builds {f"gt_{k}": v} through .items(), which
+    resolves the dense entries): the same renaming with the lazy entries kept lazy"""
+    out = FeatsDict()
+    for k in dict.keys(gt):
+        dict.__setitem__(out, prefix + k, dict.__getitem__(gt, k))
+    return out
+
+
 def _sq(a, b):
     """[B,N,M] squared distances of a [B,N,2] to b [B,M,2]: x and y terms squared and added unfused, as stage B does"""
     dx = a[:, :, None, 0] - b[:, None, :, 0]
@@ -112,7 +137,7 @@ def gt_matches_from_pose_depth(kp0, kp1, camera0, camera1, depth0, depth1, T_0to
 
     out = FeatsDict()
     out.update({
-        "assignment": _Lazy(lambda d: _assignment(r["pos0"], M)),
+        "assignment": _LazyAssignment(r["pos0"], M),
         "reward": _Lazy(reward),
         "matches0": r["matches0"], "matches1": r["matches1"],
         "matching_scores0": r["matching_scores0"], "matching_scores1": r["matching_scores1"],
@@ -137,7 +162,7 @@ def gt_matches_from_homography(kp0, kp1, H, pos_th=3, neg_th=6, **kw):
 
     out = FeatsDict()
     out.update({
-        "assignment": _Lazy(lambda d: _assignment(r["pos0"], M)),
+        "assignment": _LazyAssignment(r["pos0"], M),
         "reward": _Lazy(reward),
         "matches0": r["matches0"], "matches1": r["matches1"],
         "matching_scores0": r["matching_scores0"], "matching_scores1": r["matching_scores1"],

@@ -4,8 +4,11 @@ Drop-in for LightGlue (reference core/modules/matchers/lightglue.py:421-716), in
 same `conf` handling (merged over `default_conf`), same parameter tree (`posenc.Wr`,
 `transformers.{i}.self_attn|cross_attn.*`, `log_assignment.{i}.*`, `token_confidence.{i}.*`,
 optional `input_proj`) and the same output dict.  `matcher_metrics` (:17-63) runs on the device
-(csrc/gt_matches.hip).  Training-only members (loss, NLLLoss, token-confidence
-loss; :66-133, :190-203, :751-800) are out of scope.
+(csrc/gt_matches.hip).  `LightGlue.loss` in eval mode (:751-800 with one layer of
+ref_descriptors: one assignment head, one NLL, row_norm, matcher_metrics) runs on the device without
+a dense matrix (einx_lg_assign_nll); `NLLLoss` (:66-133) is the dense restatement in
+torch operators.  Training mode (the layer loop, the token-confidence loss :190-203, autograd) is
+out of scope.
 Early stopping / point pruning are commented out in the reference (:606-652) and absent here.
 """
 import ctypes
@@ -30,6 +33,61 @@ def matcher_metrics(pred, data, prefix="", prefix_gt=None):
         prefix_gt = prefix
     rows = match_pr(pred[f"{prefix}matches0"], data[f"gt_{prefix_gt}matches0"], scores0=pred[f"{prefix}matching_scores0"]).float()
     return {f"{prefix}{name}": rows[:, i] for i, name in enumerate(MATCH_PR_NAMES)}
+
+
+LOSS_KEYS = ("total", "last", "assignment_nll", "nll_pos", "nll_neg", "num_matchable", "num_unmatchable", "row_norm")
+
+
+def nll_size_error(B, n, m):
+    """What the reference's NLLLoss.nll_loss raises on stacked [B,n] / [B,m] labels with n != m: it writes the m column negatives
+    into `weights[:, -1, :n]` (:132), a slice of min(n, m + 1) of the m + 1 columns.  None when that assignment goes through
+    (n == m, or m == 1, which broadcasts)."""
+    t = min(n, m + 1)
+    if t == m or m == 1:
+        return None
+    return RuntimeError(f"The expanded size of the tensor ({t}) must match the existing size ({m}) at non-singleton dimension 1.  "
+                        f"Target sizes: [{B}, {t}].  Tensor sizes: [{B}, {m}]")
+
+
+def weight_loss(log_assignment, weights, gamma=0.0):
+    """lightglue.py:66-85 on dense [B,n+1,m+1] tensors"""
+    n, m = log_assignment.shape[1] - 1, log_assignment.shape[2] - 1
+    loss_sc = log_assignment * weights
+    num_neg0 = weights[:, :n, -1].sum(-1).clamp(min=1.0)
+    num_neg1 = weights[:, -1, :m].sum(-1).clamp(min=1.0)
+    num_pos = weights[:, :n, :m].sum((-1, -2)).clamp(min=1.0)
+    nll_pos = -loss_sc[:, :n, :m].sum((-1, -2)) / num_pos
+    nll_neg = (-loss_sc[:, :n, -1].sum(-1) - loss_sc[:, -1, :m].sum(-1)) / (num_neg0 + num_neg1)
+    return nll_pos, nll_neg, num_pos, (num_neg0 + num_neg1) / 2.0
+
+
+class NLLLoss(nn.Module):
+    """The reference's NLLLoss (:88-133) on DENSE tensors with plain torch operators, on whatever device they live on: the
+    restatement next to the device op, off the hot path like the dense `assignment` and `reward` of the ground-truth dict
+    (LightGlue.loss does not go through it).  Forward values; pred["log_assignment"] [B,n+1,m+1]."""
+    default_conf = {"nll_balancing": 0.5, "gamma_f": 0.0}
+
+    def __init__(self, conf):
+        super().__init__()
+        self.conf = _merge(self.default_conf, conf if conf is not None else {})
+        self.loss_fn = self.nll_loss
+
+    def forward(self, pred, data, weights=None):
+        log_assignment = pred["log_assignment"]
+        if weights is None:
+            weights = self.loss_fn(log_assignment, data)
+        nll_pos, nll_neg, num_pos, num_neg = weight_loss(log_assignment, weights, gamma=self.conf.gamma_f)
+        nll = self.conf.nll_balancing * nll_pos + (1 - self.conf.nll_balancing) * nll_neg
+        return nll, weights, {"assignment_nll": nll, "nll_pos": nll_pos, "nll_neg": nll_neg, "num_matchable": num_pos,
+                              "num_unmatchable": num_neg}
+
+    def nll_loss(self, log_assignment, data):
+        n, m = data["gt_matches0"].size(-1), data["gt_matches1"].size(-1)
+        weights = torch.zeros_like(log_assignment)
+        weights[:, :n, :m] = data["gt_assignment"].to(log_assignment.dtype)
+        weights[:, :n, -1] = (data["gt_matches0"] == -1).to(log_assignment.dtype)
+        weights[:, -1, :n] = (data["gt_matches1"] == -1).to(log_assignment.dtype)  # `:n` as the reference writes it (:132): n == m, or it raises
+        return weights
 
 
 class _Conf(dict):
@@ -111,6 +169,8 @@ class LightGlue(nn.Module):
     def __init__(self, conf):
         super().__init__()
         self.conf = conf = _merge(self.default_conf, conf)
+        conf["loss"] = _merge(self.default_conf["loss"], conf["loss"])
+        self.loss_fn = NLLLoss(conf.loss)
         # widths as the reference derives them (lightglue.py:246-248, 456-461): any num_heads dividing descriptor_dim.  The
         # attention kernel is instantiated for 32-, 64- and 128-wide heads (256 = 4 x 64, every EI-Nexus YAML, runs its own
         # instantiation); other widths run the next larger one on zero-padded heads.  What is left out: head widths that are
@@ -309,3 +369,43 @@ class LightGlue(nn.Module):
         out["prune0"] = torch.ones_like(r.scores0) * L
         out["prune1"] = torch.ones_like(r.scores1) * L
         return out
+
+    @torch.no_grad()
+    @on_input_device
+    def loss(self, pred, data):
+        """The reference's `loss` (:751-800) as its validation loop calls it, after model.eval(): `pred` holds the
+        forward's ref_descriptors0/1 [B,1,n,d] (and matches0 / matching_scores0 for the metrics), `data` gt_matches0 [B,n],
+        gt_matches1 [B,m] and gt_assignment [B,n,m].  Returns (losses, metrics): losses = LOSS_KEYS, each float32 [B] on the
+        device; metrics = matcher_metrics(pred, data).  Everything is enqueued; nothing is read back.  The NLL and row_norm come
+        from einx_lg_assign_nll on the last head's weights: no log_assignment is recomputed and pred["log_assignment"] is not read.
+        A gt_assignment that is still a lazy entry of gt_generation's dict is handed over as pos0 and stays lazy; a tensor is
+        read as the dense 0/1 matrix it is.  The reference's failures are mirrored: stacked labels with n != m raise its
+        RuntimeError, more than one layer of ref_descriptors raises KeyError('confidence'); m == 1 < n (a silent broadcast there)
+        and training mode raise NotImplementedError."""
+        from ....core.geometry.gt_generation import lazy_pos0
+        if self.training:
+            raise NotImplementedError("einx LightGlue.loss: training mode (layerwise totals, the token-confidence loss and a backward "
+                                      "pass) is out of scope, see DESIGN.md 8; call it after model.eval()")
+        ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
+        if ref0.shape[1] > 1:
+            raise KeyError("confidence")  # the reference's layer loop adds to a key that only training mode creates (:781)
+        gt0, gt1 = data["gt_matches0"], data["gt_matches1"]
+        B, n, m = ref0.shape[0], gt0.size(-1), gt1.size(-1)
+        err = nll_size_error(B, n, m)
+        if err is not None:
+            raise err
+        if m == 1 and n > 1:
+            raise NotImplementedError("einx LightGlue.loss: with m == 1 < n the reference broadcasts the one column label over its "
+                                      "dustbin row (lightglue.py:132) instead of failing; that value is not reproduced")
+        if ref0.shape[2] != n or ref1.shape[2] != m:
+            raise ValueError("einx LightGlue.loss: ref_descriptors and gt_matches differ in their keypoint counts")
+        pos0 = lazy_pos0(data, "gt_assignment")
+        assignment = None if pos0 is not None else data["gt_assignment"]
+        w = self._pack()[0]
+        rows = N.lg_assign_nll(w, ref0[:, -1].float().contiguous(), ref1[:, -1].float().contiguous(), gt0, gt1, pos0=pos0, assignment=assignment)
+        vals, row_norm = N.lg_nll_values(rows, float(self.conf.loss.nll_balancing))
+        vals, row_norm = vals.float(), row_norm.float()
+        nll = vals[:, 0]
+        losses = {"total": nll, "last": nll.clone(), "assignment_nll": nll, "nll_pos": vals[:, 1], "nll_neg": vals[:, 2],
+                  "num_matchable": vals[:, 3], "num_unmatchable": vals[:, 4], "row_norm": row_norm}
+        return losses, matcher_metrics(pred, data)

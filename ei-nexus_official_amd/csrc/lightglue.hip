@@ -1347,3 +1347,157 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
 #undef LG_CHECK
   return EINX_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Assignment NLL of one MatchAssignment head (lightglue.py:66-133, :751-769): the sums behind NLLLoss and
+// row_norm without a log_assignment matrix.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct NllWs {
+  Side s0, s1;  // q (projected descriptors), cert, dust
+};
+
+// einx_lg_assign_nll's workspace (einx_lg_assign_nll_ws_bytes walks it from a null base): per side the projected descriptors
+// [B,cap,d] and cert / dust [B,cap]; the matcher's workspace (match_tiles.h); the per-chunk partial sums [B,cap0,nc64,3]; slack.
+void carve_nll(WsCarver& c, NllWs& w, MnnArgs& a, int B, int cap0, int cap1, int d) {
+  w.s0.q = c.take<float>((size_t)B * cap0 * d);
+  w.s1.q = c.take<float>((size_t)B * cap1 * d);
+  w.s0.cert = c.take<float>((size_t)B * cap0);
+  w.s0.dust = c.take<float>((size_t)B * cap0);
+  w.s1.cert = c.take<float>((size_t)B * cap1);
+  w.s1.dust = c.take<float>((size_t)B * cap1);
+  einx_match::carve(c, a, B, cap0, cap1);
+  a.nllstat = c.take<float>((size_t)B * cap0 * a.nc64 * 3);
+  c.slack(256);
+}
+
+constexpr int NLL_OUT = 8;  // S_pos, num_pos, S_neg0, num_neg0, S_neg1, num_neg1, sum of the row sums of exp, n
+
+// One workgroup per pair.  A thread adds its rows (i = tid, tid + 256, ...) in ascending order, each row's chunk partials in
+// ascending chunk order, then its columns; the threads' sums meet as in loss.hip: lane l of wave 0 adds the LDS entries l,
+// l + 64, ... in order, then the xor butterfly.  float64 throughout, one fixed order: two calls give the same bits.
+__global__ __launch_bounds__(256) void lg_nll_finish_kernel(const MnnArgs a, const int64_t* gt0, const int64_t* gt1, double* out) {
+  __shared__ double red[7 * 256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = max(0, min(a.n[b], a.cap0)), m = max(0, min(a.m[b], a.cap1));
+  double* o = out + (size_t)b * NLL_OUT;
+  if (n == 0 || m == 0) {  // no assignment to speak of: zeros (uniform over the workgroup)
+    if (tid < NLL_OUT) o[tid] = 0.0;
+    return;
+  }
+  const int chunks = (m + 63) / 64;
+  double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < n; i += 256) {
+    const float* st = a.nllstat + ((size_t)b * a.cap0 + i) * a.nc64 * 3;
+    double e = 0.0, sw = 0.0, cw = 0.0;
+    for (int c = 0; c < chunks; ++c) {
+      e += (double)st[3 * c];
+      sw += (double)st[3 * c + 1];
+      cw += (double)st[3 * c + 2];
+    }
+    const float d0 = a.dust0[(size_t)b * a.cap0 + i];
+    v[0] += sw;
+    v[1] += cw;
+    v[6] += e + exp((double)d0);  // the dustbin column belongs to row_norm (:769)
+    if (gt0[(size_t)b * a.cap0 + i] == -1) {
+      v[2] += (double)d0;
+      v[3] += 1.0;
+    }
+  }
+  for (int j = tid; j < m; j += 256)
+    if (gt1[(size_t)b * a.cap1 + j] == -1) {
+      v[4] += (double)a.dust1[(size_t)b * a.cap1 + j];
+      v[5] += 1.0;
+    }
+#pragma unroll
+  for (int k = 0; k < 7; ++k) red[k * 256 + tid] = v[k];
+  __syncthreads();
+  if (tid < 64) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      double s = 0.0;
+      for (int i = tid; i < 256; i += 64) s += red[k * 256 + i];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+      if (tid == 0) o[k] = s;
+    }
+    if (tid == 0) o[7] = (double)n;
+  }
+}
+
+}  // namespace
+
+EINX_EXPORT size_t einx_lg_assign_nll_ws_bytes(int B, int cap0, int cap1, int d) {
+  if (B <= 0 || cap0 <= 0 || cap1 <= 0 || d <= 0 || d % 4 != 0) return 0;
+  NllWs w;
+  MnnArgs a;
+  WsCarver c{nullptr};
+  carve_nll(c, w, a, B, cap0, cap1, d);
+  return c.bytes;
+}
+
+EINX_EXPORT int einx_lg_assign_nll(const float* proj_w, const float* proj_b, const float* match_w, const float* match_b, int d, const float* x0,
+                                   const int32_t* n, int cap0, const float* x1, const int32_t* m, int cap1, int B, const int64_t* gt_matches0,
+                                   const int64_t* gt_matches1, const int32_t* pos0, const unsigned char* assignment, int64_t as_b, int64_t as_i,
+                                   int64_t as_j, void* ws, double* out, void* stream) {
+  EINX_CHECK_ARG(proj_w && proj_b && match_w && match_b && x0 && n && x1 && m && gt_matches0 && gt_matches1 && ws && out, "null pointer");
+  EINX_CHECK_ARG((pos0 != nullptr) != (assignment != nullptr), "give the positives as pos0 or as a dense assignment, not both");
+  EINX_CHECK_ARG(B > 0 && cap0 > 0 && cap1 > 0 && d > 0 && d % 4 == 0, "bad shape (d must be a multiple of 4)");
+  hipStream_t st = (hipStream_t)stream;
+  NllWs w{};
+  MnnArgs a{};
+  WsCarver c{(char*)ws};
+  carve_nll(c, w, a, B, cap0, cap1, d);
+  w.s0.cnt = n;
+  w.s0.cap = cap0;
+  w.s1.cnt = m;
+  w.s1.cap = cap1;
+  const float* x[2] = {x0, x1};
+  Side* sides[2] = {&w.s0, &w.s1};
+#define NLL_CHECK(expr)                                                       \
+  do {                                                                        \
+    if ((expr) != 0 || hipGetLastError() != hipSuccess) {                     \
+      einx_set_error("einx_lg_assign_nll: kernel launch failed at %s", #expr); \
+      return EINX_ERR_LAUNCH;                                                 \
+    }                                                                         \
+  } while (0)
+  NLL_CHECK(0);
+  for (int sd = 0; sd < 2; ++sd) {  // MatchAssignment (lightglue.py:365-377): final_proj / d^(1/4) and the matchability terms
+    Side& s = *sides[sd];
+    NLL_CHECK(gemm(st, EPI_DIV, s, B, x[sd], d, nullptr, 0, 0x7fffffff, d, proj_w, proj_b, d, s.q, d, sqrtf(sqrtf((float)d))));
+    hipLaunchKernelGGL(lg_matchability_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)B), dim3(256), 0, st, x[sd], s.cnt, s.cap, d, match_w,
+                       match_b, s.cert, s.dust);
+    NLL_CHECK(0);
+  }
+  a.d0 = w.s0.q;
+  a.d1 = w.s1.q;
+  a.n = n;
+  a.m = m;
+  a.cap0 = cap0;
+  a.cap1 = cap1;
+  a.D = d;
+  a.la = nullptr;
+  a.cert0 = w.s0.cert;
+  a.cert1 = w.s1.cert;
+  a.dust0 = w.s0.dust;
+  a.dust1 = w.s1.dust;
+  a.pos0 = pos0;
+  a.assign = assignment;
+  a.as_b = as_b;
+  a.as_i = as_i;
+  a.as_j = as_j;
+  const dim3 grid((unsigned)einx_cdiv(cap1, BN), (unsigned)einx_cdiv(cap0, BM), (unsigned)B);
+  const int mx = cap0 > cap1 ? cap0 : cap1;
+  EINX_PROF("lg_assign_nll (2 tile passes + lse + finish)", st);
+  hipLaunchKernelGGL((mnn_tile_kernel<1, false>), grid, dim3(THREADS), 0, st, a);
+  NLL_CHECK(0);
+  hipLaunchKernelGGL(mnn_lse_kernel, dim3((unsigned)einx_cdiv(mx + 1, 256), (unsigned)B), dim3(256), 0, st, a);
+  NLL_CHECK(0);
+  hipLaunchKernelGGL((mnn_tile_kernel<7, true>), grid, dim3(THREADS), 0, st, a);
+  NLL_CHECK(0);
+  hipLaunchKernelGGL(lg_nll_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, a, gt_matches0, gt_matches1, out);
+  NLL_CHECK(0);
+#undef NLL_CHECK
+  return EINX_OK;
+}

@@ -38,6 +38,12 @@ struct MnnArgs {
   // find_nn thresholds (MNN.py:12-22): second-best similarity per row / column as ordered 32-bit keys (MODE 4)
   unsigned* row2;  // [B,cap0]
   unsigned* col2;  // [B,cap1]
+  // assignment NLL (MODE 7, einx_lg_assign_nll): the positives as pos0 [B,cap0] (the column of row i's positive, -1 = none) or, with
+  // pos0 null, as a dense 0/1 byte matrix read at assign[b * as_b + i * as_i + j * as_j]
+  const int32_t* pos0;
+  const unsigned char* assign;
+  long long as_b, as_i, as_j;
+  float* nllstat;  // [B,cap0,nc64,3]  (sum exp(score), sum w score, sum w) per 64-column chunk
 };
 
 // MODE 0: arg-max keys.  MODE 1: per-chunk softmax statistics.  MODE 2: write log_assignment.
@@ -47,6 +53,9 @@ struct MnnArgs {
 // MODE 3: write the raw similarity tile to a.la as [B,cap0,cap1] (MNN.py:88 `similarity`).
 // MODE 4: second neighbour (topk(2)[1], MNN.py:13-14): per row the maximum over all columns but the arg-max
 //         column found by MODE 0 (an equal value at another index counts, as topk returns it), same per column.
+// MODE 7: (LG only) per row and 64-column chunk sum exp(score), sum w score and sum w over the chunk's valid columns, w the 0/1
+//         ground-truth assignment (a.pos0 or a.assign): the partial sums of the assignment NLL and of row_norm.  Writes no
+//         log_assignment; shaped like MODE 1's row half.
 // LG: values are LightGlue's assignment scores (needs rowlse/collse from MODE 1 + mnn_lse_kernel).
 template <int MODE, bool LG = false>
 __global__ __launch_bounds__(THREADS) void mnn_tile_kernel(const MnnArgs a) {
@@ -324,6 +333,51 @@ __global__ __launch_bounds__(THREADS) void mnn_tile_kernel(const MnnArgs a) {
         for (int nt = 0; nt < NT; ++nt) {
           const int j = j0 + col_of(nt);
           if (j < m) sim[(size_t)i * a.cap1 + j] = f.acc[mt][nt][r];
+        }
+      }
+  }
+  if (MODE == 7) {
+    const int wave = threadIdx.x >> 6;
+    const int cchunk = (j0 >> 6) + (wave & 1);
+    const int ja = j0 + col_of(0), jb = j0 + col_of(1);
+    const bool oka = ja < m, okb = jb < m;
+    const bool dense = a.pos0 == nullptr;  // wave-uniform
+    // the dense form's bytes of the lane's two columns are requested from clamped addresses, like the statistics above
+    const unsigned char* wrow = dense ? a.assign + (long long)b * a.as_b : nullptr;
+    const long long ofa = (long long)min(ja, m - 1) * a.as_j, ofb = (long long)min(jb, m - 1) * a.as_j;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = i0 + row_of(mt, r);
+        const int ic = min(i, n - 1);
+        bool wa, wb;
+        if (dense) {
+          const unsigned char* wr = wrow + (long long)ic * a.as_i;
+          wa = wr[ofa] != 0;
+          wb = wr[ofb] != 0;
+        } else {
+          const int p = a.pos0[(size_t)b * a.cap0 + ic];
+          wa = p == ja;
+          wb = p == jb;
+        }
+        wa = wa && oka;
+        wb = wb && okb;
+        const float va = f.acc[mt][0][r], vb = f.acc[mt][1][r];
+        float e = (oka ? einx_expf(va) : 0.0f) + (okb ? einx_expf(vb) : 0.0f);
+        float sw = (wa ? va : 0.0f) + (wb ? vb : 0.0f);
+        float cw = (wa ? 1.0f : 0.0f) + (wb ? 1.0f : 0.0f);
+#pragma unroll
+        for (int off = 16; off >= 1; off >>= 1) {
+          e += __shfl_xor(e, off, 64);
+          sw += __shfl_xor(sw, off, 64);
+          cw += __shfl_xor(cw, off, 64);
+        }
+        if ((lane & 31) == 0 && i < n && cchunk * 64 < m) {
+          float* o = a.nllstat + (((size_t)b * a.cap0 + i) * a.nc64 + cchunk) * 3;
+          o[0] = e;
+          o[1] = sw;
+          o[2] = cw;
         }
       }
   }

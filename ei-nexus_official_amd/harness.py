@@ -27,6 +27,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
+from . import _native as native
 from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, batch_homography, batch_metrics, batch_relative_pose, match_pr,
                                             metric_names)
 from .datasets.representations import EventStage, build_representation, events_representation_batch
@@ -320,6 +321,16 @@ def rpe_summary(rows, pose_thresh=(5, 10, 20), name="RPE"):
     return _summary(cols, r[:, 2], pose_thresh, name)
 
 
+MATCHER_LOSS_NAMES = ("matcher_loss", "matcher_nll_pos", "matcher_nll_neg", "matcher_row_norm")
+
+
+def matcher_loss_rows(rows, balancing=0.5):
+    """[B,8] rows of einx_lg_assign_nll -> [B,4] float64 = MATCHER_LOSS_NAMES per pair (losses["total"], nll_pos, nll_neg, row_norm
+    of LightGlue.loss in eval mode); NaN rows for a pair without keypoints on a side.  Device arithmetic only."""
+    vals, row_norm = native.lg_nll_values(rows, balancing)
+    return torch.cat([vals[:, :3], row_norm[:, None]], 1)
+
+
 class DifferentTimeEvaluator(SameTimeEvaluator):
     """Call pattern of test_events-image_different_time.py:187-264: the events come from frame i, the image from a LATER
     frame j of the sequence, and the two views are related by a known motion instead of the identity.
@@ -337,6 +348,11 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
       average_precision against them (matcher_metrics) run on the device too, with no host synchronisation; the returned rows
       are unchanged, `last_gt` keeps the batch's label tensors.  `depth` without `pose` raises.  `run()` items may carry `depth`
       as a 5th element.
+    * `matcher_loss=True` (LightGlue matchers; an MNN matcher raises at construction): every batch that carries pose and depth also
+      enqueues the matcher's validation loss (val_matcher.py:84: LightGlue.loss in eval mode; einx_lg_assign_nll) on
+      the forward's last-layer descriptors and the batch's labels, with no host synchronisation; result() adds matcher_loss (the
+      mean of losses["total"]), matcher_nll_pos, matcher_nll_neg and matcher_row_norm over the pairs that have keypoints on both
+      sides.  With the default nothing is launched and result() is unchanged.
     * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
       RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
       all-gathered before the AUC.  Once depth was given: the four matcher_metrics means over the pairs that have keypoints.
@@ -346,7 +362,8 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
     """
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
-                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None):
+                 ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None,
+                 matcher_loss=False):
         if losses is not None:
             raise ValueError("einx: DifferentTimeEvaluator takes no losses: its two views are not aligned pixel by pixel, which is what "
                              "the extractor losses compare (SameTimeEvaluator does)")
@@ -358,6 +375,11 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         self._pr_mean = _RunningMean(len(MATCH_PR_NAMES))  # of the [B,4] matcher_metrics rows (a pair without keypoints has NaN rows)
         self.gt_pos_th, self.gt_neg_th = 3, 5  # gt_matches_from_pose_depth's defaults, as val_matcher.py calls it
         self.last_gt = None
+        self.matcher_loss = bool(matcher_loss)
+        if self.matcher_loss and not hasattr(getattr(model.matcher, "matcher", None), "log_assignment"):
+            raise ValueError("einx: matcher_loss=True needs a LightGlue matcher: the loss is that of its assignment head (an MNN "
+                             "matcher has no parameters and no loss in the validation loop)")
+        self._nll_mean = _RunningMean(len(MATCHER_LOSS_NAMES), finite_only=True)  # of the [B,4] rows of matcher_loss_rows
 
     @torch.no_grad()
     def step(self, events_list, images, homography=None, pose=None, depth=None):
@@ -374,6 +396,11 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
             self.last_gt = batch_gt_matches(ef._batched, imf._batched, batch.depth[0], batch.depth[1], K0, K1, T, None, self.gt_pos_th,
                                             self.gt_neg_th)
             self._pr_mean.add(match_pr(self.model._last_match, self.last_gt["matches0"], ef._batched.det.counts))
+            if self.matcher_loss:  # val_matcher.py:84,100: model.matcher.matcher.loss(matches, gt), VAL_loss = losses["total"].mean()
+                lg = self.model.matcher.matcher
+                rows = native.lg_assign_nll(lg._pack()[0], self.model._last_match, None, self.last_gt["matches0"], self.last_gt["matches1"],
+                                            pos0=self.last_gt["pos0"], n=ef._batched.det.counts, m=imf._batched.det.counts)
+                self._nll_mean.add(matcher_loss_rows(rows, float(lg.conf.loss.nll_balancing)))
         if batch.pose is not None:
             K0, K1, T = batch.pose
             self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
@@ -386,6 +413,10 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         s, c = self._pr_mean.reduced(self.sums.device)
         if float(c.max()) > 0:  # some rank labelled a pair that has keypoints
             out.update(zip(MATCH_PR_NAMES, _RunningMean.means(s, c)))
+        if self.matcher_loss:
+            s, c = self._nll_mean.reduced(self.sums.device)
+            if float(c.max()) > 0:  # some rank had a pair with keypoints on both sides
+                out.update(zip(MATCHER_LOSS_NAMES, _RunningMean.means(s, c)))
         return out
 
     def pose_inputs(self, matches, b=0):

@@ -333,6 +333,24 @@ int einx_lightglue(const einx_lg_weights* w, const float* kpts0, const float* de
                    int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0, float* ref1,
                    int ref_layers, void* stream);
 
+/* Assignment NLL of ONE MatchAssignment head (lightglue.py:66-133 NLLLoss / weight_loss, :751-769 LightGlue.loss in eval mode): the
+ * sums behind nll_pos / nll_neg / row_norm, without a log_assignment matrix or any other B x n x m buffer.
+ * proj_w [d,d], proj_b [d]: the head's final_proj; match_w [d], match_b [1]: its matchability; d a multiple of 4.
+ * x0 [B,cap0,d], x1 [B,cap1,d]: the descriptors the head is applied to (ref_descriptors); n, m: device int32 counts, clamped to
+ * [0, cap].  gt_matches0 [B,cap0], gt_matches1 [B,cap1] int64: -1 selects the dustbin entries (-2 and matches weigh nothing).
+ * The positives come in ONE of two forms (the other NULL): pos0 [B,cap0] int32, the column of row i's positive or -1 (what
+ * einx_gt_label writes), or a dense 0/1 byte matrix read at assignment[b*as_b + i*as_i + j*as_j] (strides in bytes = elements).
+ * The two give the same bits when the matrix is the scatter of pos0.
+ * out [B,8] float64 per pair: S_pos = sum w la[i,j], num_pos = sum w, S_neg0 = sum over gt_matches0 == -1 of la[i,m], num_neg0,
+ * S_neg1 = sum over gt_matches1 == -1 of la[n,j], num_neg1, sum_i sum_{j<=m} exp(la[i,j]) (row_norm x n), n.  A pair with
+ * n == 0 or m == 0 gets eight zeros.  Deterministic (no float atomics, fixed summation order), no host synchronisation, no
+ * allocation: capturable.  ws: einx_lg_assign_nll_ws_bytes(B, cap0, cap1, d) bytes (0 = bad shape). */
+size_t einx_lg_assign_nll_ws_bytes(int B, int cap0, int cap1, int d);
+int einx_lg_assign_nll(const float* proj_w, const float* proj_b, const float* match_w, const float* match_b, int d, const float* x0,
+                       const int32_t* n, int cap0, const float* x1, const int32_t* m, int cap1, int B, const int64_t* gt_matches0,
+                       const int64_t* gt_matches1, const int32_t* pos0, const unsigned char* assignment, int64_t as_b, int64_t as_i,
+                       int64_t as_j, void* ws, double* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Event representation (the step before the path)
  * events of B samples are concatenated; offsets_host[B+1] (HOST array) delimits the samples.
