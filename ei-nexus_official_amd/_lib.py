@@ -85,6 +85,10 @@ class LgWeights(ctypes.Structure):
                 ("layers", ctypes.POINTER(LgLayer))]
 
 
+class LgHead(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("proj_w", "proj_b", "match_w", "match_b", "token_w", "token_b")]
+
+
 # name -> (restype, argtypes); every symbol include/einx.h declares
 SIGNATURES = {
     "einx_version": (c_char_p, []),
@@ -182,6 +186,9 @@ SIGNATURES = {
     "einx_lightglue": (c_int, [ctypes.POINTER(LgWeights), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                c_int, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_int, c_void_p]),
+    "einx_lightglue_early_stop_ws_bytes": (c_size_t, [c_int] * 7),
+    "einx_lightglue_early_stop": (c_int, [ctypes.POINTER(LgWeights), ctypes.POINTER(LgHead), c_size_t, c_float, c_void_p, c_void_p, c_void_p,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float] + [c_void_p] * 10),
     "einx_lg_assign_nll_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "einx_lg_assign_nll": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p,

@@ -321,11 +321,12 @@ def upsample_normalize(raw, padded_size, pads, scale):
 
 # ------------------------------------------------------------------------------ matching
 class MatchResult:
-    __slots__ = ("matches0", "matches1", "scores0", "scores1", "la", "mk0", "mk1", "nmatch", "ref0", "ref1", "mk0_flat", "mk1_flat", "stale")
+    __slots__ = ("matches0", "matches1", "scores0", "scores1", "la", "mk0", "mk1", "nmatch", "ref0", "ref1", "mk0_flat", "mk1_flat", "stale", "stop")
 
     def __init__(self):
         self.mk0_flat = self.mk1_flat = None
         self.stale = None  # device int32 [1]: the matcher's weight watch (LightGlue), read back with the match counts
+        self.stop = None  # device int32 [B]: the layer count each pair ran (LightGlue with early stopping only)
 
 
 def mnn(desc0, n, desc1, m, want_la=True, ratio_thresh=None, distance_thresh=None, gather=None):
@@ -397,16 +398,23 @@ def compact_matches(r):
     return r
 
 
-def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False):
+def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False, early_stop=None):
     """weights: _lib.LgWeights; pb0/pb1: PairBatch (kpts [B,cap,3], desc [B,cap,Din], counts).
-    all_layers: ref0/ref1 are [B,n_layers,cap,d] (training-mode ref_descriptors) instead of [B,cap,d]."""
+    all_layers: ref0/ref1 are [B,n_layers,cap,d] (training-mode ref_descriptors) instead of [B,cap,d].
+    early_stop = (heads, depth_confidence): einx_lightglue_early_stop with the _lib.LgHead array of every layer's heads; r.stop
+    [B] int32 is the number of layers each pair ran."""
     _dev_check(pb0.kpts, pb0.desc, pb1.kpts, pb1.desc)
     _dev_check(pb0.counts, pb1.counts, dt=I32)
     B, cap0, cap1 = pb0.B, pb0.cap, pb1.cap
     L = lib()
     dev = pb0.desc.device
     d = int(weights.d)
-    nbytes = L.einx_lg_ws_bytes_heads(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim))
+    if early_stop is not None:
+        if all_layers:
+            raise ValueError("einx LightGlue: early stopping returns the descriptors the stopping head read, not every layer's")
+        nbytes = L.einx_lightglue_early_stop_ws_bytes(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim), int(weights.n_layers))
+    else:
+        nbytes = L.einx_lg_ws_bytes_heads(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim))
     if not nbytes:
         raise NotImplementedError("einx LightGlue: descriptor_dim must be num_heads x head_dim with head_dim a multiple of 4, at most 256")
     ws = _workspace(nbytes, dev)
@@ -424,6 +432,15 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False)
         r.ref0 = torch.empty((B, cap0, d), dtype=F32, device=dev) if want_ref else None
         r.ref1 = torch.empty((B, cap1, d), dtype=F32, device=dev) if want_ref else None
     (h0, w0), (h1, w1) = pb0.image_size, pb1.image_size
+    if early_stop is not None:
+        heads, depth = early_stop
+        r.stop = torch.empty((B,), dtype=torch.int32, device=dev)
+        check(L.einx_lightglue_early_stop(ctypes.byref(weights), heads, ctypes.sizeof(heads._type_), float(depth), _ptr(pb0.kpts), _ptr(pb0.desc),
+                                          _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc), _ptr(pb1.counts), cap1, B, float(h0), float(w0),
+                                          float(h1), float(w1), _ptr(ws), _ptr(r.matches0), _ptr(r.matches1), _ptr(r.scores0), _ptr(r.scores1),
+                                          _ptr(r.la), _ptr(r.ref0), _ptr(r.ref1), _ptr(r.stop), _stream(pb0.desc)),
+              "einx_lightglue_early_stop")
+        return r
     check(L.einx_lightglue(ctypes.byref(weights), _ptr(pb0.kpts), _ptr(pb0.desc), _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc),
                            _ptr(pb1.counts), cap1, B, float(h0), float(w0), float(h1), float(w1), _ptr(ws), _ptr(r.matches0),
                            _ptr(r.matches1), _ptr(r.scores0), _ptr(r.scores1), _ptr(r.la), _ptr(r.ref0), _ptr(r.ref1),

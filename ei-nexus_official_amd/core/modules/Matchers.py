@@ -60,7 +60,10 @@ class Matcher(nn.Module):
         return N.compact_matches(self.matcher.match_batched(from_batched(bf0), from_batched(bf1)))
 
     def materialize(self, r, n_host, m_host, nmatch_host, prebuilt=None):
-        return materialize_matches(r, n_host, m_host, nmatch_host, self._cols, prebuilt=prebuilt)
+        out = materialize_matches(r, n_host, m_host, nmatch_host, self._cols, prebuilt=prebuilt)
+        if getattr(r, "stop", None) is not None:  # LightGlue with early stopping on: layers run, one int32 scalar per pair
+            out["stop"] = list(r.stop.unbind(0))
+        return out
 
     # ---- un-frozen branch: pad to max_points_num (Matchers.py:67-149) ---------------------------
     def pad_sparse_positions_to_length(self, sparse_positions, length, image_size=None):

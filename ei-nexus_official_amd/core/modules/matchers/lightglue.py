@@ -9,10 +9,12 @@ ref_descriptors: one assignment head, one NLL, row_norm, matcher_metrics) runs o
 a dense matrix (einx_lg_assign_nll); `NLLLoss` (:66-133) is the dense restatement in
 torch operators.  Training mode (the layer loop, the token-confidence loss :190-203, autograd) is
 out of scope.
-Early stopping / point pruning are commented out in the reference (:606-652) and absent here.
+Early stopping / point pruning are commented out in the reference (:606-652).  Early stopping (per-pair adaptive depth) is
+available here as an opt-in, `LightGlue.early_stop`; point pruning is refused.
 """
 import ctypes
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -159,6 +161,12 @@ class TokenConfidence(nn.Module):
 
 
 class LightGlue(nn.Module):
+    """Early stopping.  The reference accepts `depth_confidence` and carries the trained token_confidence / log_assignment heads
+    of every layer, but its forward IGNORES the key: the branch is commented out (:606-636) and the list its helpers read,
+    `confidence_thresholds`, is never created, so every pair runs every layer.  This class does the same by default.  Setting
+    `early_stop = True` (with conf.depth_confidence > 0, in eval mode) runs the branch on the device, per pair
+    (einx_lightglue_early_stop): results then DIFFER from the reference's for every pair that stops, which is
+    why the switch is opt-in rather than driven by the config key alone.  Outputs gain "stop" (layers run per pair)."""
     default_conf = {
         "name": "lightglue", "input_dim": 256, "add_scale_ori": False, "descriptor_dim": 256, "n_layers": 9, "num_heads": 4,
         "flash": False, "mp": False, "depth_confidence": -1, "width_confidence": -1, "filter_threshold": 0.0,
@@ -195,6 +203,9 @@ class LightGlue(nn.Module):
         self.want_log_assignment = True
         self.fold_message_projection = True  # inference-time weight folding (see _pack); False = layer by layer as written
         self.merge_qk_v = True  # CrossBlock.to_qk and to_v as one launch over a merged weight image (same results); False = two launches
+        # what the reference's confidence_threshold reads and never creates (:718-722, 468-470 commented out)
+        self.confidence_thresholds = [self.confidence_threshold(i) for i in range(conf.n_layers)]
+        self.early_stop = False  # opt-in: the reference ignores depth_confidence (see the class docstring)
         self._packed = None
         self._sig = None
         self._sig_tensors = None
@@ -208,6 +219,20 @@ class LightGlue(nn.Module):
     def load_state_dict(self, *a, **k):
         self._packed = self._sig_tensors = None
         return super().load_state_dict(*a, **k)
+
+    def confidence_threshold(self, layer_index):
+        """scaled confidence threshold of a layer (lightglue.py:718-722)"""
+        threshold = 0.8 + 0.1 * np.exp(-4.0 * layer_index / self.conf.n_layers)
+        return float(np.clip(threshold, 0, 1))
+
+    def early_stop_active(self):
+        """whether the next eval-mode forward stops pairs early; depth_confidence is read at every call, like filter_threshold"""
+        if not self.early_stop:
+            return False
+        if float(self.conf.width_confidence) > 0:
+            raise NotImplementedError("einx LightGlue: early_stop with width_confidence > 0 asks for point pruning, which is not "
+                                      "implemented (DESIGN.md 8h)")
+        return not self.training and float(self.conf.depth_confidence) > 0
 
     def refresh(self):
         """Drop the packed / folded weight images.  REQUIRED after edits through `p.data` (an alias with its own version
@@ -282,8 +307,17 @@ class LightGlue(nn.Module):
         w.n_layers, w.heads, w.d, w.input_dim = c.n_layers, c.num_heads, c.descriptor_dim, c.input_dim
         w.filter_threshold = float(c.filter_threshold)
         w.layers = ctypes.cast(layers, ctypes.POINTER(_lib.LgLayer))
+        heads = (_lib.LgHead * c.n_layers)()  # every layer's heads, for early stopping (the same storage, the same watch)
+        for i, (hd, a) in enumerate(zip(heads, self.log_assignment)):
+            hd.proj_w, hd.proj_b = p(a.final_proj.weight), p(a.final_proj.bias)
+            hd.match_w, hd.match_b = p(a.matchability.weight), p(a.matchability.bias)
+            if i < c.n_layers - 1:
+                tok = self.token_confidence[i].token[0]
+                hd.token_w, hd.token_b = p(tok.weight), p(tok.bias)
+            else:
+                hd.token_w, hd.token_b = None, None
         self._watch = N.ParamWatch(self._sig_tensors)  # `.data` edits are seen by content at the next forward (round 4)
-        self._packed = (w, layers, keep)
+        self._packed = (w, layers, keep, heads)
         return self._packed
 
     def _add_scale_ori_error(self, feats0):
@@ -306,7 +340,8 @@ class LightGlue(nn.Module):
         w = self._pack()[0]
         w.filter_threshold = float(self.conf.filter_threshold)  # read at every call like the reference's filter_matches call (lightglue.py:656)
         stale = self._watch.check()
-        r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers)
+        es = (self._pack()[3], float(self.conf.depth_confidence)) if self.early_stop_active() else None
+        r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers, early_stop=es)
         r.stale = stale
         return N.gather_matches(r, pb0.kpts, pb1.kpts, pb0.counts, 2)
 
@@ -355,6 +390,8 @@ class LightGlue(nn.Module):
                 out["ref_descriptors1"] = ref1[:, :, :m[0]]
                 out["prune0"] = torch.ones_like(out["matching_scores0"]) * L
                 out["prune1"] = torch.ones_like(out["matching_scores1"]) * L
+            if r.stop is not None:
+                out["stop"] = r.stop
             return out
         if not (stacked and len(set(n)) == 1 and len(set(m)) == 1):
             raise NotImplementedError("einx LightGlue.forward with B > 1 takes stacked [B,n,*] tensors (as the reference does); "
@@ -368,6 +405,8 @@ class LightGlue(nn.Module):
         out["ref_descriptors1"] = r.ref1 if all_layers else r.ref1[:, None]
         out["prune0"] = torch.ones_like(r.scores0) * L
         out["prune1"] = torch.ones_like(r.scores1) * L
+        if r.stop is not None:
+            out["stop"] = r.stop
         return out
 
     @torch.no_grad()
@@ -381,11 +420,14 @@ class LightGlue(nn.Module):
         A gt_assignment that is still a lazy entry of gt_generation's dict is handed over as pos0 and stays lazy; a tensor is
         read as the dense 0/1 matrix it is.  The reference's failures are mirrored: stacked labels with n != m raise its
         RuntimeError, more than one layer of ref_descriptors raises KeyError('confidence'); m == 1 < n (a silent broadcast there)
-        and training mode raise NotImplementedError."""
+        and training mode raise NotImplementedError.  A `pred` that carries "stop" (early stopping was on) raises ValueError."""
         from ....core.geometry.gt_generation import lazy_pos0
         if self.training:
             raise NotImplementedError("einx LightGlue.loss: training mode (layerwise totals, the token-confidence loss and a backward "
                                       "pass) is out of scope, see DESIGN.md 8; call it after model.eval()")
+        if "stop" in pred:
+            raise ValueError("einx LightGlue.loss: `pred` comes from a forward with early stopping on (it carries \"stop\"): its "
+                             "ref_descriptors are those of each pair's stopping layer, and the loss applies the LAST head (DESIGN.md 8h)")
         ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
         if ref0.shape[1] > 1:
             raise KeyError("confidence")  # the reference's layer loop adds to a key that only training mode creates (:781)

@@ -61,7 +61,8 @@ __global__ void lg_posenc_kernel(const float* kpts, const int32_t* cnt, int cap,
 // ------------------------------------------------------------------------------------------
 // batched Linear: Y[b,i,:] = cat(X[b,i,:], X2[b,i,:]) @ W^T + bias  (+ epilogue)
 // ------------------------------------------------------------------------------------------
-enum { EPI_BIAS = 0, EPI_DIV = 1, EPI_RESID = 2, EPI_ROPE = 3, EPI_ROPE_ANY = 4 };  // ROPE: d = 256, 64-wide heads; ROPE_ANY: g.d / g.dh
+enum { EPI_BIAS = 0, EPI_DIV = 1, EPI_RESID = 2, EPI_ROPE = 3, EPI_ROPE_ANY = 4, EPI_DIV_HEAD = 5 };  // ROPE: d = 256, 64-wide heads; ROPE_ANY: g.d / g.dh
+// EPI_DIV_HEAD: EPI_DIV with every entry's W / bias taken from the head its pair stopped at (early stopping)
 
 struct GemmArgs {
   const float* X;
@@ -78,7 +79,17 @@ struct GemmArgs {
   const float* enc;  // [B,cap,2 dh]: cos(dh) | sin(dh)
   float *Yq, *Yk, *Yv;
   int d, dh;  // read by EPI_ROPE_ANY only (dh even: rotary pairs are adjacent columns)
+  // EPI_DIV_HEAD only: heads[4 h + 0 / 1] = final_proj weight / bias of log_assignment[h] (device table); entry b belongs to pair
+  // b mod pairs, whose head is stop - 1 (the last one, nheads - 1, for stop == 0: an empty pair runs as it always did)
+  const float* const* heads;
+  const int32_t* stop;
+  int pairs, nheads;
 };
+
+__device__ __forceinline__ int head_of(const int32_t* stop, int pairs, int nheads, int b) {
+  const int s = stop[b < pairs ? b : b - pairs];
+  return s > 0 ? s - 1 : nheads - 1;
+}
 
 // Persistent workgroups: the launch holds as many workgroups as the chip runs at once (a multiple
 // of 8) and each walks a list of 128x128 tiles.  Workgroups w and w+8 share an XCD (round-robin
@@ -117,7 +128,7 @@ __global__ __launch_bounds__(THREADS, 2 * THREADS / 256) void lg_gemm_kernel(con
       s.j0 = (tj % tpb) * BN;
       s.Nvalid = rd;
     } else {
-      s.B = g.W;
+      s.B = EPI == EPI_DIV_HEAD ? g.heads[4 * head_of(g.stop, g.pairs, g.nheads, b)] : g.W;
       s.ldb = g.K;
       s.j0 = (L % tilesN) * BN;
       s.Nvalid = g.N;
@@ -197,15 +208,16 @@ __global__ __launch_bounds__(THREADS, 2 * THREADS / 256) void lg_gemm_kernel(con
     // load -> wait -> store round trip per element
     float bj[NT];
     int jj[NT];
+    const float* bias = EPI == EPI_DIV_HEAD ? g.heads[4 * head_of(g.stop, g.pairs, g.nheads, b) + 1] : g.bias;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const int j = j0 + col_of(nt);
       jj[nt] = j < g.N ? j : -1;
-      bj[nt] = j < g.N ? g.bias[j] : 0.0f;
+      bj[nt] = j < g.N ? bias[j] : 0.0f;
     }
     auto finish = [&](float acc, float bias, float old) {
       float v = acc + bias;
-      if (EPI == EPI_DIV) v = v / g.div;
+      if (EPI == EPI_DIV || EPI == EPI_DIV_HEAD) v = v / g.div;
       if (EPI == EPI_RESID) v = old + v;
       return v;
     };
@@ -290,7 +302,7 @@ __global__ __launch_bounds__(256) void lg_gemm_small_kernel(const GemmArgs g) {
     ldb = 3 * g.K;
   } else {
     j0 = tj * SBN;
-    Wb = g.W;
+    Wb = EPI == EPI_DIV_HEAD ? g.heads[4 * head_of(g.stop, g.pairs, g.nheads, b)] : g.W;
     ldb = g.K;
   }
   const float* A1 = g.X + (size_t)b * g.cap * g.ldx;
@@ -374,7 +386,7 @@ __global__ __launch_bounds__(256) void lg_gemm_small_kernel(const GemmArgs g) {
     return;
   }
   float* Y = g.Y + (size_t)b * g.cap * g.ldy;
-  const float bj = g.bias[col];
+  const float bj = (EPI == EPI_DIV_HEAD ? g.heads[4 * head_of(g.stop, g.pairs, g.nheads, b) + 1] : g.bias)[col];
   float old[16];
   if (EPI == EPI_RESID) {
 #pragma unroll
@@ -383,7 +395,7 @@ __global__ __launch_bounds__(256) void lg_gemm_small_kernel(const GemmArgs g) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     float v = acc[r] + bj;
-    if (EPI == EPI_DIV) v = v / g.div;
+    if (EPI == EPI_DIV || EPI == EPI_DIV_HEAD) v = v / g.div;
     if (EPI == EPI_RESID) v = old[r] + v;
     if (rows[r] < n) Y[(size_t)rows[r] * g.ldy + col] = v;
   }
@@ -846,6 +858,113 @@ __global__ __launch_bounds__(256) void lg_matchability_kernel(const float* x, co
   }
 }
 
+// the same with every entry's weights taken from the head its pair stopped at (heads[4 h + 2 / 3], see GemmArgs)
+__global__ __launch_bounds__(256) void lg_matchability_heads_kernel(const float* x, const int32_t* cnt, int cap, int d, const float* const* heads,
+                                                                    const int32_t* stop, int pairs, int nheads, float* cert, float* dust) {
+  const int b = blockIdx.y;
+  const int n = min(cnt[b], cap);
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int lane = threadIdx.x & 63;
+  const int h = head_of(stop, pairs, nheads, b);
+  const float* w = heads[4 * h + 2];
+  const float* row = x + ((size_t)b * cap + i) * d;
+  float s = 0.0f;
+  for (int c = lane; c < d; c += 64) s = fmaf(row[c], w[c], s);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (lane == 0) {
+    const float z = s + heads[4 * h + 3][0];
+    cert[(size_t)b * cap + i] = einx_logsigmoidf(z);
+    dust[(size_t)b * cap + i] = einx_logsigmoidf(-z);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Early stopping: the layers run on PRIVATE active counts; a pair that stops gets both of them zeroed, and every
+// kernel above skips its rows from then on.
+// ------------------------------------------------------------------------------------------
+constexpr int LG_MAX_HEADS = 32;
+struct HeadTable {
+  const float* p[4 * LG_MAX_HEADS];  // per layer: final_proj w, b, matchability w, b
+};
+
+// the heads' pointers into device memory (the kernels pick an entry by stop[b]), the private counts, stop and the decision's counters
+__global__ void lg_es_init_kernel(const HeadTable t, int nheads, const float** heads, const int32_t* n, const int32_t* m, int B, int cap0, int cap1,
+                                  int32_t* cnt2, int32_t* act, int32_t* stop, int32_t* below, int32_t* done) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 4 * nheads) heads[i] = t.p[i];
+  if (i < 2 * B) {
+    const int32_t v = i < B ? n[i] : m[i - B];
+    cnt2[i] = v;
+    act[i] = v;
+  }
+  if (i < B) {
+    stop[i] = (min(n[i], cap0) > 0 && min(m[i], cap1) > 0) ? nheads : 0;
+    below[i] = 0;
+    done[i] = 0;
+  }
+}
+
+struct StopArgs {
+  const float *x0, *x1;  // [B,cap0,d], [B,cap1,d] after the layer
+  int32_t *act0, *act1;  // the active counts, [B] each
+  int cap0, cap1, d, B, layer;
+  const float *w, *bias;  // token_confidence[layer].token[0]
+  float thr, depth;
+  int32_t *below, *done;  // [B], zero between launches
+  int32_t* stop;
+};
+
+// One launch per non-final layer: entry e < B is side 0 of pair e, entry e >= B side 1 of pair e - B; a workgroup takes STOP_ROWS
+// rows (a wave one row at a time: c = sigmoid(x . w + b), compared with the layer's threshold in float32).  The workgroups of a
+// pair add their integer counts into below[pair] and take a ticket; the one that takes the last ticket has every count, applies
+// r = 1 - below / (n + m) > depth_confidence, writes stop and zeroes the pair's active counts, and leaves the counters at zero.
+// Integer sums only: the order in which the workgroups arrive does not matter.  Every workgroup with rows has read the counts
+// before it takes its ticket, so none can meet the zeroed counts of its own launch; those without rows return either way.
+constexpr int STOP_ROWS = 32;
+__global__ __launch_bounds__(256) void lg_stop_kernel(const StopArgs a) {
+  __shared__ int part[4];
+  const int e = blockIdx.y;
+  const bool side = e >= a.B;
+  const int p = side ? e - a.B : e;
+  const int n = min(a.act0[p], a.cap0), m = min(a.act1[p], a.cap1);
+  if (n <= 0 || m <= 0) return;  // stopped earlier, or an empty pair (stop = 0)
+  const int rows = side ? m : n;
+  const int r0 = (int)blockIdx.x * STOP_ROWS;
+  if (r0 >= rows) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* x = side ? a.x1 + (size_t)p * a.cap1 * a.d : a.x0 + (size_t)p * a.cap0 * a.d;
+  const float b0 = a.bias[0];
+  int below = 0;
+  for (int k = 0; k < STOP_ROWS / 4; ++k) {
+    const int i = r0 + wave * (STOP_ROWS / 4) + k;
+    if (i >= rows) break;
+    const float* row = x + (size_t)i * a.d;
+    float s = 0.0f;
+    for (int c = lane; c < a.d; c += 64) s = fmaf(row[c], a.w[c], s);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    below += einx_sigmoidf(s + b0) < a.thr ? 1 : 0;
+  }
+  if (lane == 0) part[wave] = below;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  atomicAdd(&a.below[p], part[0] + part[1] + part[2] + part[3]);
+  __threadfence();
+  const int expected = einx_cdiv(n, STOP_ROWS) + einx_cdiv(m, STOP_ROWS);
+  if (atomicAdd(&a.done[p], 1) != expected - 1) return;
+  __threadfence();
+  const int total = atomicExch(&a.below[p], 0);
+  atomicExch(&a.done[p], 0);
+  const float r = 1.0f - (float)total / (float)(n + m);
+  if (r > a.depth) {
+    a.stop[p] = a.layer + 1;
+    a.act0[p] = 0;
+    a.act1[p] = 0;
+  }
+}
+
 // filter_matches (lightglue.py:402-418) from the packed arg-max keys of the assignment scores
 __global__ void lg_finalize_kernel(const unsigned long long* rowkey, const unsigned long long* colkey, const int32_t* nn, const int32_t* mm,
                                    int cap0, int cap1, float th, int64_t* m0, int64_t* m1, float* s0, float* s1) {
@@ -948,6 +1067,21 @@ __global__ void lg_stack_counts_kernel(const int32_t* n, const int32_t* m, int B
   if (t < 2 * B) out[t] = t < B ? n[t] : m[t - B];
 }
 
+// what early stopping adds behind carve()'s regions (einx_lightglue_early_stop_ws_bytes walks the same function)
+struct EsWs {
+  const float** heads;  // [4 n_layers] device table
+  int32_t *act, *below, *done;  // private active counts [2B]; the decision's counters [B] each
+};
+void carve_es(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, EsWs& e, bool stacked, int B, int cap0, int cap1, int d, int dh,
+              int n_layers) {
+  carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, d, dh);
+  e.heads = c.take<const float*>((size_t)4 * n_layers);
+  e.act = c.take<int32_t>((size_t)2 * B);
+  e.below = c.take<int32_t>((size_t)B);
+  e.done = c.take<int32_t>((size_t)B);
+  c.slack(256);
+}
+
 // persistent launch size: resident workgroups of the tile kernels on this device (a multiple of
 // 8 so that every XCD gets the same number of slots), never more than the tiles there are
 unsigned gemm_grid(int tiles) {
@@ -973,8 +1107,13 @@ bool small_grid(int N, int cap, int B, int K, int Ksplit) {
 }
 
 int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx, const float* X2, int ldx2, int Ksplit, int K, const float* W,
-         const float* bias, int N, float* Y, int ldy, float div = 1.0f) {
+         const float* bias, int N, float* Y, int ldy, float div = 1.0f, const float* const* heads = nullptr, const int32_t* stop = nullptr,
+         int pairs = 0, int nheads = 0) {
   GemmArgs g;
+  g.heads = heads;
+  g.stop = stop;
+  g.pairs = pairs;
+  g.nheads = nheads;
   g.X = X;
   g.X2 = X2;
   g.W = W;
@@ -995,6 +1134,7 @@ int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx,
     EINX_PROF("lg_gemm_small_kernel", st);
     if (epi == EPI_BIAS) hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_BIAS>, sg, dim3(256), 0, st, g);
     else if (epi == EPI_DIV) hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_DIV>, sg, dim3(256), 0, st, g);
+    else if (epi == EPI_DIV_HEAD) hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_DIV_HEAD>, sg, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_RESID>, sg, dim3(256), 0, st, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
@@ -1002,6 +1142,7 @@ int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx,
   EINX_PROF("lg_gemm_kernel", st);
   if (epi == EPI_BIAS) hipLaunchKernelGGL(lg_gemm_kernel<EPI_BIAS>, grid, dim3(THREADS), 0, st, g);
   else if (epi == EPI_DIV) hipLaunchKernelGGL(lg_gemm_kernel<EPI_DIV>, grid, dim3(THREADS), 0, st, g);
+  else if (epi == EPI_DIV_HEAD) hipLaunchKernelGGL(lg_gemm_kernel<EPI_DIV_HEAD>, grid, dim3(THREADS), 0, st, g);
   else hipLaunchKernelGGL(lg_gemm_kernel<EPI_RESID>, grid, dim3(THREADS), 0, st, g);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1175,10 +1316,17 @@ EINX_EXPORT size_t einx_lg_ws_bytes(int B, int cap0, int cap1, int d, int input_
   return d > 0 && d % 64 == 0 ? einx_lg_ws_bytes_heads(B, cap0, cap1, d, d / 64, input_dim) : 0;
 }
 
-EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
-                               const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
-                               float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
-                               float* ref0, float* ref1, int ref_layers, void* stream) {
+namespace {
+// what einx_lightglue_early_stop hands to the shared body (null: einx_lightglue)
+struct EarlyStop {
+  const einx_lg_head* heads;
+  float depth_confidence;
+  int32_t* stop;
+};
+
+int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
+           const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws, int64_t* matches0,
+           int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0, float* ref1, int ref_layers, void* stream) {
   EINX_CHECK_ARG(w && kpts0 && desc0 && n && kpts1 && desc1 && m && ws && matches0 && matches1 && scores0 && scores1, "null pointer");
   Dims dm;
   EINX_CHECK_ARG(dims_of(w->d, w->heads, dm), "descriptor_dim must be num_heads x head_dim with head_dim a multiple of 4, at most 256");
@@ -1206,16 +1354,38 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
   const bool stacked = cap0 == cap1;
   int32_t* cnt2;
   MnnArgs a;
+  EsWs ew{};
   WsCarver c{(char*)ws};
-  carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, D, dm.dh);
-  Side sb{};
-  if (stacked) {
+  if (es) carve_es(c, s0, s1, cnt2, a, ew, stacked, B, cap0, cap1, D, dm.dh, w->n_layers);
+  else carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, D, dm.dh);
+  // r0 / r1: the sides as the LAYERS see them.  Early stopping: on the private active counts (ew.act = n | m, zeroed per pair as
+  // it stops); the input stage, ref_descriptors and the assignment keep the caller's counts.  sa: the stacked view of those.
+  Side sb{}, sa{}, r0 = s0, r1 = s1;
+  if (es) {
+    HeadTable t;
+    for (int i = 0; i < w->n_layers; ++i) {
+      t.p[4 * i + 0] = es->heads[i].proj_w;
+      t.p[4 * i + 1] = es->heads[i].proj_b;
+      t.p[4 * i + 2] = es->heads[i].match_w;
+      t.p[4 * i + 3] = es->heads[i].match_b;
+    }
+    const int items = 4 * w->n_layers > 2 * B ? 4 * w->n_layers : 2 * B;
+    hipLaunchKernelGGL(lg_es_init_kernel, dim3((unsigned)einx_cdiv(items, 256)), dim3(256), 0, st, t, (int)w->n_layers, ew.heads, n, m, B, cap0, cap1,
+                       cnt2, ew.act, es->stop, ew.below, ew.done);
+    r0.cnt = ew.act;
+    r1.cnt = ew.act + B;
+  } else if (stacked) {
     hipLaunchKernelGGL(lg_stack_counts_kernel, dim3((unsigned)einx_cdiv(2 * B, 256)), dim3(256), 0, st, n, m, B, cnt2);
+  }
+  if (stacked) {
+    sa = s0;
+    sa.cnt = cnt2;
     sb = s0;
-    sb.cnt = cnt2;
+    sb.cnt = es ? ew.act : cnt2;
   }
   Side* sides[2] = {&s0, &s1};
-  Side* run[2] = {stacked ? &sb : &s0, &s1};  // what the shared-weight stages iterate over
+  Side* run[2] = {stacked ? &sb : &r0, &r1};  // what the shared-weight stages iterate over
+  Side* asg[2] = {stacked ? &sa : &s0, &s1};  // the assignment's projections: every pair's own rows
   const int nrun = stacked ? 1 : 2, Br = stacked ? 2 * B : B;
   const float sz[2][2] = {{h0, w0}, {h1, w1}};
 #define LG_CHECK(expr)                                                    \
@@ -1271,11 +1441,11 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
       if (merged) LG_CHECK(attn(st, Br, dm, sb.h, sb.cnt, sb.cap, sb.h, sb.h + D, sb.cnt, sb.cap, sb.ctx, B, true));
       else LG_CHECK(attn(st, Br, dm, sb.q, sb.cnt, sb.cap, sb.q, sb.v, sb.cnt, sb.cap, sb.ctx, B));
     } else if (merged) {
-      LG_CHECK(attn(st, B, dm, s0.h, s0.cnt, s0.cap, s1.h, s1.h + D, s1.cnt, s1.cap, s0.ctx, 0, true));
-      LG_CHECK(attn(st, B, dm, s1.h, s1.cnt, s1.cap, s0.h, s0.h + D, s0.cnt, s0.cap, s1.ctx, 0, true));
+      LG_CHECK(attn(st, B, dm, r0.h, r0.cnt, r0.cap, r1.h, r1.h + D, r1.cnt, r1.cap, r0.ctx, 0, true));
+      LG_CHECK(attn(st, B, dm, r1.h, r1.cnt, r1.cap, r0.h, r0.h + D, r0.cnt, r0.cap, r1.ctx, 0, true));
     } else {
-      LG_CHECK(attn(st, B, dm, s0.q, s0.cnt, s0.cap, s1.q, s1.v, s1.cnt, s1.cap, s0.ctx));
-      LG_CHECK(attn(st, B, dm, s1.q, s1.cnt, s1.cap, s0.q, s0.v, s0.cnt, s0.cap, s1.ctx));
+      LG_CHECK(attn(st, B, dm, r0.q, r0.cnt, r0.cap, r1.q, r1.v, r1.cnt, r1.cap, r0.ctx));
+      LG_CHECK(attn(st, B, dm, r1.q, r1.cnt, r1.cap, r0.q, r0.v, r0.cnt, r0.cap, r1.ctx));
     }
     for (int sd = 0; sd < nrun; ++sd) {
       Side& s = *run[sd];
@@ -1296,10 +1466,42 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
         LG_CHECK(0);
       }
     }
+    if (es && li < w->n_layers - 1) {  // the pairs still running decide whether this was their last layer
+      StopArgs sa_;
+      sa_.x0 = s0.x;
+      sa_.x1 = s1.x;
+      sa_.act0 = ew.act;
+      sa_.act1 = ew.act + B;
+      sa_.cap0 = cap0;
+      sa_.cap1 = cap1;
+      sa_.d = D;
+      sa_.B = B;
+      sa_.layer = li;
+      sa_.w = es->heads[li].token_w;
+      sa_.bias = es->heads[li].token_b;
+      const double thr = 0.8 + 0.1 * exp(-4.0 * li / w->n_layers);  // confidence_threshold (lightglue.py:718-722), rounded to float32 once
+      sa_.thr = (float)(thr < 0.0 ? 0.0 : thr > 1.0 ? 1.0 : thr);
+      sa_.depth = es->depth_confidence;
+      sa_.below = ew.below;
+      sa_.done = ew.done;
+      sa_.stop = es->stop;
+      const int mxr = cap0 > cap1 ? cap0 : cap1;
+      EINX_PROF("lg_stop_kernel", st);
+      hipLaunchKernelGGL(lg_stop_kernel, dim3((unsigned)einx_cdiv(mxr, STOP_ROWS), (unsigned)(2 * B)), dim3(256), 0, st, sa_);
+      LG_CHECK(0);
+    }
   }
   // ---- assignment ------------------------------------------------------------------------------
   for (int sd = 0; sd < nrun; ++sd) {
-    Side& s = *run[sd];
+    Side& s = *asg[sd];
+    if (es) {  // route (a): one stage over every pair's own rows, each pair with the head it stopped at (x frozen since then)
+      LG_CHECK(gemm(st, EPI_DIV_HEAD, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, nullptr, nullptr, D, s.q, D, sqrtf(sqrtf((float)D)), ew.heads,
+                    es->stop, B, w->n_layers));
+      hipLaunchKernelGGL(lg_matchability_heads_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)Br), dim3(256), 0, st, s.x, s.cnt, s.cap, D,
+                         ew.heads, es->stop, B, (int)w->n_layers, s.cert, s.dust);
+      LG_CHECK(0);
+      continue;
+    }
     LG_CHECK(gemm(st, EPI_DIV, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, w->proj_w, w->proj_b, D, s.q, D, sqrtf(sqrtf((float)D))));
     hipLaunchKernelGGL(lg_matchability_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)Br), dim3(256), 0, st, s.x, s.cnt, s.cap, D, w->match_w,
                        w->match_b, s.cert, s.dust);
@@ -1346,6 +1548,46 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
   LG_CHECK(0);
 #undef LG_CHECK
   return EINX_OK;
+}
+}  // namespace
+
+EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                               const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
+                               float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
+                               float* ref0, float* ref1, int ref_layers, void* stream) {
+  return lg_run(w, nullptr, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
+                ref1, ref_layers, stream);
+}
+
+EINX_EXPORT size_t einx_lightglue_early_stop_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers) {
+  Dims dm;
+  if (B <= 0 || cap0 <= 0 || cap1 <= 0 || n_layers < 1 || n_layers > LG_MAX_HEADS || !dims_of(d, heads, dm)) return 0;
+  (void)input_dim;
+  Side s0, s1;
+  int32_t* cnt2;
+  MnnArgs a;
+  EsWs e;
+  WsCarver c{nullptr};
+  carve_es(c, s0, s1, cnt2, a, e, cap0 == cap1, B, cap0, cap1, d, dm.dh, n_layers);
+  return c.bytes;
+}
+
+EINX_EXPORT int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                                          const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
+                                          const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
+                                          int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
+                                          float* ref1, int32_t* stop, void* stream) {
+  EINX_CHECK_ARG(w && heads && stop, "null pointer");
+  EINX_CHECK_ARG(head_size == sizeof(einx_lg_head), "head_size does not match this library's einx_lg_head (header / library ABI mismatch)");
+  EINX_CHECK_ARG(w->n_layers >= 1 && w->n_layers <= LG_MAX_HEADS, "early stopping takes 1..32 layers");
+  for (int i = 0; i < w->n_layers; ++i) {
+    const einx_lg_head& h = heads[i];
+    EINX_CHECK_ARG(h.proj_w && h.proj_b && h.match_w && h.match_b, "every layer needs its log_assignment head");
+    EINX_CHECK_ARG(i == w->n_layers - 1 || (h.token_w && h.token_b), "every layer but the last needs its token_confidence head");
+  }
+  const EarlyStop es{heads, depth_confidence, stop};
+  return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
+                1, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -127,6 +127,7 @@ class SameTimeEvaluator:
         self.mma_thr, self.vdd_thr = tuple(mma_thr), tuple(vdd_thr)
         self.names = metric_names(self.mma_thr, self.vdd_thr)
         self._metric_mean = _RunningMean(len(self.names))
+        self._stop_mean = _RunningMean(1)  # layers run per pair, when the matcher stops pairs early (LightGlue.early_stop)
         self._stages = {}  # (slot, on its own stream, device) -> EventStage
         self.pairs = 0
 
@@ -200,6 +201,7 @@ class SameTimeEvaluator:
         rows = batch_metrics(ef._batched, imf._batched, self.model._last_match, batch.homography, self.mma_thr, self.vdd_thr)
         self._metric_mean.add(rows)
         self.pairs += rows.shape[0]
+        self._account_stop(self.model._last_match)
         if self.he_thresh is not None and batch.homography is not None:
             mr = self.model._last_match
             key = (tuple(ef._batched.image_size), mr.mk0.shape[0], mr.mk0.device)
@@ -209,6 +211,11 @@ class SameTimeEvaluator:
             self._he_rows.append(batch_homography(mr, shape, batch.homography, self.he_ransac_thresh, self.he_conf, ordering=ef._batched.ordering,
                                                   he_thr=self.he_thresh)[3])
         return rows, (ef, imf, matches)
+
+    def _account_stop(self, mr):
+        stop = getattr(mr, "stop", None)
+        if stop is not None:
+            self._stop_mean.add(stop.double()[:, None])
 
     @property
     def sums(self):
@@ -249,6 +256,9 @@ class SameTimeEvaluator:
             out.update(_gathered_summary(self._he_rows, len(self.he_thresh) + 2, he_summary, self.he_thresh))
         if self.losses is not None:  # no finite value for a key: NaN
             out.update(zip(LOSS_NAMES, _RunningMean.means(*self._loss_mean.reduced(dev), empty_is_nan=True)))
+        s, c = self._stop_mean.reduced(dev)
+        if float(c.max()) > 0:  # some rank's matcher stopped pairs early: the mean number of layers a pair ran
+            out["matcher_stop_layer"] = _RunningMean.means(s, c)[0]
         return out
 
 
@@ -386,6 +396,9 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         return self._step(_Batch(events_list, images, homography, pose, depth))
 
     def _validate(self, batch):
+        if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.early_stop_active():
+            raise ValueError("einx: matcher_loss=True with early stopping on: the loss applies the LAST assignment head, the forward's "
+                             "descriptors are those of each pair's stopping layer (LightGlue.loss refuses them too, DESIGN.md 8h)")
         if batch.depth is not None and batch.pose is None:
             raise ValueError("einx: depth=(depth0, depth1) needs pose=(K0, K1, T_0to1): ground-truth matches come from depth AND motion")
 

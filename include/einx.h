@@ -333,6 +333,33 @@ int einx_lightglue(const einx_lg_weights* w, const float* kpts0, const float* de
                    int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0, float* ref1,
                    int ref_layers, void* stream);
 
+/* Early stopping: per-pair adaptive depth.  LightGlue trains a token_confidence head per non-final layer and a
+ * log_assignment head per layer so that an easy pair can leave after a few layers; the reference carries them and
+ * `depth_confidence`, but its forward has the branch commented out (lightglue.py:606-636) and always runs every layer.  This
+ * entry point runs the branch.  It is a departure from the reference's results and therefore something the caller opts into;
+ * einx_lightglue is unchanged.
+ * After layer i < n_layers - 1, for every pair still running: c = sigmoid(token_w . x + token_b) of its n + m rows in float32,
+ * below = #{c < thr[i]}, thr[i] = float32(clip(0.8 + 0.1 exp(-4 i / n_layers), 0, 1)); the pair stops iff
+ * 1.0f - float(below) / float(n + m) > depth_confidence.  A pair that stops after layer i has stop = i + 1: its rows are not
+ * touched again, and its assignment comes from heads[i] (final_proj, matchability) applied to them.  A pair that never stops has
+ * stop = n_layers and exactly einx_lightglue's outputs; a pair with n == 0 or m == 0 has stop = 0 and einx_lightglue's outputs.
+ * Pairs are independent of each other.  ref0 / ref1 [B,cap,d] hold the descriptors the head read.
+ * heads: HOST array of n_layers entries (token_* unused in the last); head_size = sizeof(einx_lg_head), checked.  w->proj_* /
+ * w->match_* are not read.  stop: device int32 [B].  n, m are never written: the layers run on copies in the workspace.
+ * One more launch per non-final layer (integer counting, no float atomics: deterministic), no host synchronisation, no
+ * allocation: capturable.  ws: einx_lightglue_early_stop_ws_bytes(...) bytes (0 = unsupported widths, or more than 32 layers). */
+typedef struct einx_lg_head {
+  const float *proj_w, *proj_b;   /* log_assignment[i].final_proj [d,d], [d] */
+  const float *match_w, *match_b; /* log_assignment[i].matchability [1,d], [1] */
+  const float *token_w, *token_b; /* token_confidence[i].token[0] [1,d], [1]; NULL in the last entry */
+} einx_lg_head;
+size_t einx_lightglue_early_stop_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers);
+int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                              const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
+                              const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
+                              int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
+                              float* ref1, int32_t* stop, void* stream);
+
 /* Assignment NLL of ONE MatchAssignment head (lightglue.py:66-133 NLLLoss / weight_loss, :751-769 LightGlue.loss in eval mode): the
  * sums behind nll_pos / nll_neg / row_norm, without a log_assignment matrix or any other B x n x m buffer.
  * proj_w [d,d], proj_b [d]: the head's final_proj; match_w [d], match_b [1]: its matchability; d a multiple of 4.
