@@ -115,6 +115,7 @@ SIGNATURES = {
     "einx_extract_watch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(ExtractOut),
                            ctypes.POINTER(WeightWatch), c_void_p]),
     "einx_conv_last_kernel": (c_char_p, []),
+    "einx_conv_plan": (c_char_p, [c_int] * 11),
     "einx_conv_weight_elems": (c_size_t, [c_int, c_int, c_int]),
     "einx_conv_repack": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "einx_bn_fold": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),

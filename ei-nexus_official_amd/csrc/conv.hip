@@ -1073,10 +1073,11 @@ struct TileCfg {
 };
 
 template <int KS, int TH, int TW, int WM, int WN, int MT, int NT, int CK, bool POOL, bool DENSE3 = false>
-void launch(const ConvArgs& a, int B, hipStream_t s) {
+void launch(const ConvArgs& a, int B, hipStream_t s, bool three_per_cu = false) {
   dim3 grid((unsigned)(a.tilesX * a.tilesY * B), (unsigned)(a.CoutPad / kCoutTile));
   // DENSE3: launches of at least eight rounds of three workgroups per CU take the instantiation that fits three per CU
-  const bool three = DENSE3 && (long)grid.x * grid.y >= 8L * 768;
+  // (ConvPlan::three, decided by conv_plan from the same grid)
+  const bool three = DENSE3 && three_per_cu;
   {
     // name of the instantiation this call launches (einx_conv_last_kernel: measurement provenance)
     static char nm[2][96] = {{0}, {0}};
@@ -1200,18 +1201,251 @@ EINX_EXPORT int einx_conv_first_two_fused(const float* in, int B, int Hs, int Ws
   return EINX_OK;
 }
 
+namespace {
+
+// ---- which instantiation a layer gets.  conv_plan is the ONE selection code: einx_conv_block launches what it returns and
+// einx_conv_plan reports its name without launching.  A new instantiation needs a row here (or a variant of its own below), a
+// case in einx_conv_block and a row in the tests' coverage table (tests/conv_plan_cases.py).
+// every conv_block_kernel instantiation the dispatcher launches: variant, KS, TH, TW, WM, WN, MT, NT, CK, POOL, DENSE3
+// Wave layouts (measured per layer, bench.py --layer-table): 8 waves (2 channel groups x 4 pixel
+// groups, one 32x64 accumulator block each) for the 256-slot tiles -- two waves per SIMD from one
+// workgroup hide each other's LDS/epilogue latency at half the accumulator registers per wave;
+// 4 waves of 1x3 tiles for the 192-slot tiles (6 waves load the 4 SIMDs unevenly: -25 %) and
+// 4 waves for the 1x1 heads.
+#define EINX_CONV_BLOCK_VARIANTS(X)                    \
+  X(CB_1X1_128, 1, 1, 128, 1, 4, 2, 1, 32, false, false) \
+  X(CB_1X1_256, 1, 1, 256, 1, 4, 2, 2, 32, false, false) \
+  X(CB_P_8X32, 3, 8, 32, 2, 4, 1, 2, 8, true, true)      \
+  X(CB_P_12X16, 3, 12, 16, 2, 2, 1, 3, 8, true, false)   \
+  X(CB_P_22X8, 3, 22, 8, 2, 2, 1, 3, 8, true, false)     \
+  X(CB_P_8X16, 3, 8, 16, 2, 2, 1, 2, 8, true, false)     \
+  X(CB_P_4X16, 3, 4, 16, 2, 2, 1, 1, 8, true, false)     \
+  X(CB_8X32_CK2, 3, 8, 32, 2, 4, 1, 2, 2, false, false)  \
+  X(CB_8X32_CK6, 3, 8, 32, 2, 4, 1, 2, 6, false, false)  \
+  X(CB_8X32, 3, 8, 32, 2, 4, 1, 2, 8, false, true)       \
+  X(CB_12X16, 3, 12, 16, 2, 2, 1, 3, 8, false, false)    \
+  X(CB_22X8, 3, 22, 8, 2, 2, 1, 3, 8, false, false)      \
+  X(CB_11X22, 3, 11, 22, 2, 4, 1, 2, 8, false, false)    \
+  X(CB_11X11, 3, 11, 11, 2, 2, 1, 2, 8, false, false)    \
+  X(CB_11X5, 3, 11, 5, 2, 2, 1, 1, 8, false, false)
+
+enum ConvVariant {
+#define X(V, ...) V,
+  EINX_CONV_BLOCK_VARIANTS(X)
+#undef X
+  CB_1X1_128_XTRA,  // conv_block_kernel<1,1,128,...,XTRA>: 64 n + 1 output channels on n channel tiles
+  C16_1X1,          // conv16_1x1_kernel<npw>
+  C16,              // conv16_kernel<pool,8,npw>
+};
+
+struct ConvPlan {
+  int variant;         // ConvVariant
+  int tilesX, tilesY;  // ConvArgs::tilesX / tilesY of the launch
+  int npw;             // N-tiles per wave of the conv16 kernels, 0 otherwise
+  bool three;          // the three-workgroups-per-CU instantiation of a DENSE3 variant
+};
+
+// the fields of einx_conv_desc the selection reads
+struct ConvPlanLayer {
+  int cin, cout, ks, pool;
+};
+
+// the instantiation's name as einx_conv_last_kernel reports it (launch<> composes the same string from its template arguments)
+void conv_plan_name(const ConvPlan& p, bool pool, char* nm, size_t n) {
+  switch (p.variant) {
+#define X(V, KS, TH, TW, WM, WN, MT, NT, CK, POOL, DENSE3)                                                                            \
+  case V:                                                                                                                             \
+    snprintf(nm, n, "conv_block_kernel<%d,%d,%d,%d,%d,%d,%d,%d,%s>%s", KS, TH, TW, WM, WN, MT, NT, CK, POOL ? "true" : "false", \
+             DENSE3 && p.three ? " (3 per CU)" : "");                                                                                 \
+    break;
+    EINX_CONV_BLOCK_VARIANTS(X)
+#undef X
+    case CB_1X1_128_XTRA: snprintf(nm, n, "conv_block_kernel<1,1,128,1,4,2,1,32,false,xtra>"); break;
+    case C16_1X1: snprintf(nm, n, "conv16_1x1_kernel<%d>", p.npw); break;
+    default: snprintf(nm, n, "conv16_kernel<%s,8,%d>", pool ? "true" : "false", p.npw); break;
+  }
+}
+
+// why einx_conv_block does not take this layer and call (nullptr: it does); the one copy of the shape conditions, shared with
+// einx_conv_plan
+const char* conv_shape_refused(const ConvPlanLayer* d, int B, int Hs, int Ws, int h0, int w0, int H, int W) {
+  if (!(d->ks == 1 || d->ks == 3)) return "kernel size must be 1 or 3";
+  if (!(B > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0 && d->cin > 0 && d->cout > 0)) return "bad shape";
+  if (!(!d->pool || (H % 2 == 0 && W % 2 == 0))) return "pooling needs even H and W";
+  if (!(d->ks == 3 || (Hs == H && Ws == W && h0 == 0 && w0 == 0))) return "1x1 layers take no padding fold";
+  if (!(d->ks == 3 || !d->pool)) return "pooled 1x1 not supported";
+  // byte offsets inside one image's [C,H,W] tensor are 32-bit (buffer descriptors per image)
+  if (!((size_t)d->cin * Hs * Ws < (1u << 30) && (size_t)d->cout * H * W < (1u << 30) && (size_t)d->cin * H * W < (1u << 30)))
+    return "image too large (2^30 elements per image and tensor)";
+  return nullptr;
+}
+
+ConvPlan conv_plan(const ConvPlanLayer* d, int B, int Hs, int Ws, int h0, int w0, int H, int W) {
+  ConvPlan p = {0, 0, 0, 0, false};
+  const int CoutPad = einx_cdiv(d->cout, kCoutTile) * kCoutTile;
+  if (d->ks == 1) {
+    // small maps (the 33x44 heads): 128-pixel runs double the workgroup count so that the 256 CUs hold
+    // enough waves to hide the staging latency (768 -> 1536 workgroups for 256 output channels at B=32)
+    const long blocks256 = (long)einx_cdiv(H * W, 256) * B * (CoutPad / kCoutTile);
+    p.tilesY = 1;
+    {  // small grids: one 16x16 accumulator per wave (conv16_1x1_kernel), the widest pixel run that still gives 512 workgroups
+      const long max_wg128 = 512;
+      const long blocks128 = (long)einx_cdiv(H * W, 128) * B * (CoutPad / kCoutTile);
+      if (blocks128 < max_wg128 && d->cin % 32 == 0) {
+        int npw = 1;
+        for (int cand = 4; cand > 1; cand >>= 1)
+          if ((long)einx_cdiv(H * W, 16 * cand) * B * (CoutPad / kCoutTile) >= 512) {
+            npw = cand;
+            break;
+          }
+        p.tilesX = einx_cdiv(H * W, 16 * npw);
+        p.variant = C16_1X1;
+        p.npw = npw;
+        return p;
+      }
+    }
+    const long min256 = 1024;
+    if (blocks256 < min256) {
+      p.tilesX = einx_cdiv(H * W, 128);
+      if (d->cout == CoutPad - kCoutTile + 1 && d->cout > kCoutTile && d->cin % 32 == 0) {
+        // 64 n + 1 output channels (the detector's 65): n channel tiles, the last one also carries channel 64 n (see XTRA)
+        p.variant = CB_1X1_128_XTRA;
+      } else {
+        p.variant = CB_1X1_128;
+      }
+    } else {
+      p.tilesX = einx_cdiv(H * W, 256);
+      p.variant = CB_1X1_256;
+    }
+    return p;
+  }
+  // candidate tile shapes: (8,32) and (11,22) with 256 pixel slots (8 waves), (12,16) and (22,8) with 192
+  // (4 waves), (11,11) with 128 for small maps.  Pooled layers need even tile dims so that every 2x2 window
+  // lives inside one tile.  First choice: the least pixel-slot waste; then the two corrections below.
+  static const TileCfg cfgs[5] = {{8, 32, 256}, {12, 16, 192}, {22, 8, 192}, {11, 22, 256}, {11, 11, 128}};
+  int best = 0;
+  double bw = 1e30;
+  for (int i = 0; i < 4; ++i) {
+    if (d->pool && ((cfgs[i].th & 1) || (cfgs[i].tw & 1))) continue;
+    const double wst = tile_waste(H, W, cfgs[i]);
+    if (wst < bw - 1e-9) {
+      bw = wst;
+      best = i;
+    }
+  }
+  // small maps: when the launch would not even give every CU two workgroups, halve the tile
+  // (11x11, 128 pixel slots) so the 256 CUs are loaded evenly (33x44 map, 128 channels: 384 -> 768)
+  if (!d->pool) {
+    const long blocks = (long)einx_cdiv(H, cfgs[best].th) * einx_cdiv(W, cfgs[best].tw) * B * (CoutPad / kCoutTile);
+    if (blocks < 640 && tile_waste(H, W, cfgs[4]) <= bw * 1.05 + 1e-9) best = 4;
+  }
+  // (rounds 2-4 preferred the 8-wave 11x22 tile over the 4-wave 192-slot tiles at up to 6 % more pixel slots; with the
+  // round-5 kernel the exact 12x16 tiling of the 132x176 maps is 10 % faster: 455 -> 412 us at B=32)
+  {
+    // Small grids (single images: the reference's own call pattern): the launch does not fill the chip, so what counts is the
+    // LATENCY of one workgroup = (waves it puts on a SIMD) x (accumulator tiles per wave) x K-steps x 64 cycles -- the k-ordered
+    // accumulation forbids splitting K -- times the rounds the grid needs on 256 CUs.  Finer tiles with one single-tile wave
+    // per SIMD cut it up to 4x; bit-identical results (same kernel, other template arguments).  Thin first layers stay on the
+    // generic path (they are store-bound).
+    const long blocks_best = (long)einx_cdiv(H, cfgs[best].th) * einx_cdiv(W, cfgs[best].tw) * B * (CoutPad / kCoutTile);
+    // the finest grain: one 16x16 accumulator per wave on the 16x16x4 instruction, when even that leaves SIMDs to spare
+    // (MFMA tiles = pixels / 16 x channels / 16 <= 8192) -- see conv16_kernel
+    {
+      const long max_tiles = 8192;
+      const long t16 = (long)einx_cdiv(H, 2) * einx_cdiv(W, 8) * B * (CoutPad / 16);
+      if (blocks_best < 512 && d->cin % 8 == 0 && Hs == H && Ws == W && h0 == 0 && w0 == 0 && t16 <= max_tiles && (!d->pool || (H % 2 == 0 && W % 2 == 0))) {
+        // pixels per workgroup: the widest tile that still leaves every CU two workgroups (weights are re-streamed per
+        // workgroup; measured at B=1: 132x176 layers 28 -> 24.5 us with two N-tiles per wave, 29 with one or four)
+        const long min_wg = 512;
+        int npw = 1;
+        for (int cand = 4; cand > 1; cand >>= 1)
+          if ((long)einx_cdiv(H, 2) * einx_cdiv(W, 8 * cand) * B * (CoutPad / kCoutTile) >= min_wg) {
+            npw = cand;
+            break;
+          }
+        p.tilesX = einx_cdiv(W, 8 * npw);
+        p.tilesY = einx_cdiv(H, 2);
+        p.variant = C16;
+        p.npw = npw;
+        return p;
+      }
+    }
+    if (blocks_best < 512 && d->cin > 6) {
+      struct Lat {
+        int th, tw, unit;  // unit = waves per SIMD x accumulator tiles per wave
+      };
+      static const Lat pooled[4] = {{8, 32, 4}, {12, 16, 3}, {8, 16, 2}, {4, 16, 1}};
+      static const Lat plain[5] = {{8, 32, 4}, {11, 22, 4}, {12, 16, 3}, {11, 11, 2}, {11, 5, 1}};
+      const Lat* cand = d->pool ? pooled : plain;
+      const int nc = d->pool ? 4 : 5;
+      int pick = -1;
+      double best_est = 1e30;
+      for (int i = 0; i < nc; ++i) {
+        const long blocks = (long)einx_cdiv(H, cand[i].th) * einx_cdiv(W, cand[i].tw) * B * (CoutPad / kCoutTile);
+        const double est = (double)((blocks + 255) / 256) * cand[i].unit;
+        if (est < best_est - 1e-9) {
+          best_est = est;
+          pick = i;
+        }
+      }
+      p.tilesX = einx_cdiv(W, cand[pick].tw);
+      p.tilesY = einx_cdiv(H, cand[pick].th);
+      if (d->pool) {
+        switch (pick) {
+          case 0: p.variant = CB_P_8X32; break;
+          case 1: p.variant = CB_P_12X16; break;
+          case 2: p.variant = CB_P_8X16; break;
+          default: p.variant = CB_P_4X16; break;
+        }
+      } else {
+        switch (pick) {
+          case 0: p.variant = CB_8X32; break;
+          case 1: p.variant = CB_11X22; break;
+          case 2: p.variant = CB_12X16; break;
+          case 3: p.variant = CB_11X11; break;
+          default: p.variant = CB_11X5; break;
+        }
+      }
+      return p;
+    }
+  }
+  p.tilesX = einx_cdiv(W, cfgs[best].tw);
+  p.tilesY = einx_cdiv(H, cfgs[best].th);
+  if (d->pool) {
+    switch (best) {
+      case 0: p.variant = CB_P_8X32; break;
+      case 1: p.variant = CB_P_12X16; break;
+      default: p.variant = CB_P_22X8; break;
+    }
+  } else {
+    switch (best) {
+      case 0:
+        // thin first layers (1 / 5 input channels): stage only the channel pairs that exist
+        if (d->cin <= 2) p.variant = CB_8X32_CK2;
+        else if (d->cin <= 6) p.variant = CB_8X32_CK6;
+        else p.variant = CB_8X32;
+        break;
+      case 1: p.variant = CB_12X16; break;
+      case 2: p.variant = CB_22X8; break;
+      case 3: p.variant = CB_11X22; break;
+      default: p.variant = CB_11X11; break;
+    }
+  }
+  // launches of at least eight rounds of three workgroups per CU take the instantiation that fits three per CU (the two
+  // DENSE3 variants, on this path only: the small-grid picks above never take it)
+  p.three = (p.variant == CB_P_8X32 || p.variant == CB_8X32) && (long)p.tilesX * p.tilesY * B * (CoutPad / kCoutTile) >= 8L * 768;
+  return p;
+}
+
+}  // namespace
+
 EINX_EXPORT int einx_conv_block(const float* in, int B, int Hs, int Ws, int h0, int w0, int H, int W, const einx_conv_desc* d,
                                 float* out, void* stream) {
   EINX_CHECK_ARG(in && out && d && d->w_native, "null pointer");
-  EINX_CHECK_ARG(d->ks == 1 || d->ks == 3, "kernel size must be 1 or 3");
-  EINX_CHECK_ARG(B > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0 && d->cin > 0 && d->cout > 0, "bad shape");
   EINX_CHECK_ARG((d->scale == nullptr) == (d->shift == nullptr), "scale and shift go together");
-  EINX_CHECK_ARG(!d->pool || (H % 2 == 0 && W % 2 == 0), "pooling needs even H and W");
-  EINX_CHECK_ARG(d->ks == 3 || (Hs == H && Ws == W && h0 == 0 && w0 == 0), "1x1 layers take no padding fold");
-  EINX_CHECK_ARG(d->ks == 3 || !d->pool, "pooled 1x1 not supported");
-  // byte offsets inside one image's [C,H,W] tensor are 32-bit (buffer descriptors per image)
-  EINX_CHECK_ARG((size_t)d->cin * Hs * Ws < (1u << 30) && (size_t)d->cout * H * W < (1u << 30) && (size_t)d->cin * H * W < (1u << 30),
-                 "image too large (2^30 elements per image and tensor)");
+  const ConvPlanLayer pl = {d->cin, d->cout, d->ks, d->pool};
+  const char* refused = conv_shape_refused(&pl, B, Hs, Ws, h0, w0, H, W);
+  EINX_CHECK_ARG(!refused, refused);
   hipStream_t s = (hipStream_t)stream;
   ConvArgs a;
   a.in = in;
@@ -1231,186 +1465,64 @@ EINX_EXPORT int einx_conv_block(const float* in, int B, int Hs, int Ws, int h0, 
   a.H = H;
   a.W = W;
   a.relu = d->relu;
-  if (d->ks == 1) {
-    // small maps (the 33x44 heads): 128-pixel runs double the workgroup count so that the 256 CUs hold
-    // enough waves to hide the staging latency (768 -> 1536 workgroups for 256 output channels at B=32)
-    const long blocks256 = (long)einx_cdiv(H * W, 256) * B * (a.CoutPad / kCoutTile);
-    a.tilesY = 1;
-    {  // small grids: one 16x16 accumulator per wave (conv16_1x1_kernel), the widest pixel run that still gives 512 workgroups
-      const long max_wg128 = 512;
-      const long blocks128 = (long)einx_cdiv(H * W, 128) * B * (a.CoutPad / kCoutTile);
-      if (blocks128 < max_wg128 && d->cin % 32 == 0) {
-        int npw = 1;
-        for (int cand = 4; cand > 1; cand >>= 1)
-          if ((long)einx_cdiv(H * W, 16 * cand) * B * (a.CoutPad / kCoutTile) >= 512) {
-            npw = cand;
-            break;
-          }
-        a.tilesX = einx_cdiv(H * W, 16 * npw);
-        dim3 grid((unsigned)(a.tilesX * B), (unsigned)(a.CoutPad / kCoutTile));
-        static thread_local char nm[64];
-        snprintf(nm, sizeof nm, "conv16_1x1_kernel<%d>", npw);
-        g_last_conv_kernel = nm;
-        EINX_PROF("conv16_1x1_kernel (small grid)", s);
-        if (npw == 4) hipLaunchKernelGGL(conv16_1x1_kernel<4>, grid, dim3(256), 0, s, a);
-        else if (npw == 2) hipLaunchKernelGGL(conv16_1x1_kernel<2>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(conv16_1x1_kernel<1>, grid, dim3(256), 0, s, a);
-        EINX_CHECK_LAUNCH();
-        return EINX_OK;
-      }
+  const ConvPlan p = conv_plan(&pl, B, Hs, Ws, h0, w0, H, W);
+  a.tilesX = p.tilesX;
+  a.tilesY = p.tilesY;
+  static thread_local char nm[96];  // names that carry a run-time argument; launch<> keeps one string per instantiation
+  switch (p.variant) {
+#define X(V, KS, TH, TW, WM, WN, MT, NT, CK, POOL, DENSE3) \
+  case V: launch<KS, TH, TW, WM, WN, MT, NT, CK, POOL, DENSE3>(a, B, s, p.three); break;
+    EINX_CONV_BLOCK_VARIANTS(X)
+#undef X
+    case CB_1X1_128_XTRA: {
+      dim3 grid((unsigned)(a.tilesX * B), (unsigned)(a.CoutPad / kCoutTile - 1));
+      conv_plan_name(p, d->pool, nm, sizeof nm);
+      g_last_conv_kernel = nm;
+      EINX_PROF("conv_block_kernel 1x1", s);
+      hipLaunchKernelGGL((conv_block_kernel<1, 1, 128, 1, 4, 2, 1, 32, false, true>), grid, dim3(256), 0, s, a);
+      break;
     }
-    const long min256 = 1024;
-    if (blocks256 < min256) {
-      a.tilesX = einx_cdiv(H * W, 128);
-      if (d->cout == a.CoutPad - kCoutTile + 1 && d->cout > kCoutTile && d->cin % 32 == 0) {
-        // 64 n + 1 output channels (the detector's 65): n channel tiles, the last one also carries channel 64 n (see XTRA)
-        dim3 grid((unsigned)(a.tilesX * B), (unsigned)(a.CoutPad / kCoutTile - 1));
-        g_last_conv_kernel = "conv_block_kernel<1,1,128,1,4,2,1,32,false,xtra>";
-        EINX_PROF("conv_block_kernel 1x1", s);
-        hipLaunchKernelGGL((conv_block_kernel<1, 1, 128, 1, 4, 2, 1, 32, false, true>), grid, dim3(256), 0, s, a);
-      } else {
-        launch<1, 1, 128, 1, 4, 2, 1, 32, false>(a, B, s);
-      }
-    } else {
-      a.tilesX = einx_cdiv(H * W, 256);
-      launch<1, 1, 256, 1, 4, 2, 2, 32, false>(a, B, s);
+    case C16_1X1: {
+      dim3 grid((unsigned)(a.tilesX * B), (unsigned)(a.CoutPad / kCoutTile));
+      conv_plan_name(p, d->pool, nm, sizeof nm);
+      g_last_conv_kernel = nm;
+      EINX_PROF("conv16_1x1_kernel (small grid)", s);
+      if (p.npw == 4) hipLaunchKernelGGL(conv16_1x1_kernel<4>, grid, dim3(256), 0, s, a);
+      else if (p.npw == 2) hipLaunchKernelGGL(conv16_1x1_kernel<2>, grid, dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(conv16_1x1_kernel<1>, grid, dim3(256), 0, s, a);
+      break;
     }
-    EINX_CHECK_LAUNCH();
-    return EINX_OK;
-  }
-  // candidate tile shapes: (8,32) and (11,22) with 256 pixel slots (8 waves), (12,16) and (22,8) with 192
-  // (4 waves), (11,11) with 128 for small maps.  Pooled layers need even tile dims so that every 2x2 window
-  // lives inside one tile.  First choice: the least pixel-slot waste; then the two corrections below.
-  static const TileCfg cfgs[5] = {{8, 32, 256}, {12, 16, 192}, {22, 8, 192}, {11, 22, 256}, {11, 11, 128}};
-  int best = 0;
-  double bw = 1e30;
-  for (int i = 0; i < 4; ++i) {
-    if (d->pool && ((cfgs[i].th & 1) || (cfgs[i].tw & 1))) continue;
-    const double wst = tile_waste(H, W, cfgs[i]);
-    if (wst < bw - 1e-9) {
-      bw = wst;
-      best = i;
-    }
-  }
-  // small maps: when the launch would not even give every CU two workgroups, halve the tile
-  // (11x11, 128 pixel slots) so the 256 CUs are loaded evenly (33x44 map, 128 channels: 384 -> 768)
-  if (!d->pool) {
-    const long blocks = (long)einx_cdiv(H, cfgs[best].th) * einx_cdiv(W, cfgs[best].tw) * B * (a.CoutPad / kCoutTile);
-    if (blocks < 640 && tile_waste(H, W, cfgs[4]) <= bw * 1.05 + 1e-9) best = 4;
-  }
-  // (rounds 2-4 preferred the 8-wave 11x22 tile over the 4-wave 192-slot tiles at up to 6 % more pixel slots; with the
-  // round-5 kernel the exact 12x16 tiling of the 132x176 maps is 10 % faster: 455 -> 412 us at B=32)
-  {
-    // Small grids (single images: the reference's own call pattern): the launch does not fill the chip, so what counts is the
-    // LATENCY of one workgroup = (waves it puts on a SIMD) x (accumulator tiles per wave) x K-steps x 64 cycles -- the k-ordered
-    // accumulation forbids splitting K -- times the rounds the grid needs on 256 CUs.  Finer tiles with one single-tile wave
-    // per SIMD cut it up to 4x; bit-identical results (same kernel, other template arguments).  Thin first layers stay on the
-    // generic path (they are store-bound).
-    const long blocks_best = (long)einx_cdiv(H, cfgs[best].th) * einx_cdiv(W, cfgs[best].tw) * B * (a.CoutPad / kCoutTile);
-    // the finest grain: one 16x16 accumulator per wave on the 16x16x4 instruction, when even that leaves SIMDs to spare
-    // (MFMA tiles = pixels / 16 x channels / 16 <= 8192) -- see conv16_kernel
-    {
-      const long max_tiles = 8192;
-      const long t16 = (long)einx_cdiv(H, 2) * einx_cdiv(W, 8) * B * (a.CoutPad / 16);
-      if (blocks_best < 512 && d->cin % 8 == 0 && Hs == H && Ws == W && h0 == 0 && w0 == 0 && t16 <= max_tiles && (!d->pool || (H % 2 == 0 && W % 2 == 0))) {
-        // pixels per workgroup: the widest tile that still leaves every CU two workgroups (weights are re-streamed per
-        // workgroup; measured at B=1: 132x176 layers 28 -> 24.5 us with two N-tiles per wave, 29 with one or four)
-        const long min_wg = 512;
-        int npw = 1;
-        for (int cand = 4; cand > 1; cand >>= 1)
-          if ((long)einx_cdiv(H, 2) * einx_cdiv(W, 8 * cand) * B * (a.CoutPad / kCoutTile) >= min_wg) {
-            npw = cand;
-            break;
-          }
-        a.tilesX = einx_cdiv(W, 8 * npw);
-        a.tilesY = einx_cdiv(H, 2);
-        dim3 grid((unsigned)(a.tilesX * a.tilesY * B), (unsigned)(a.CoutPad / kCoutTile));
-        static thread_local char nm[64];
-        snprintf(nm, sizeof nm, "conv16_kernel<%s,8,%d>", d->pool ? "true" : "false", npw);
-        g_last_conv_kernel = nm;
-        EINX_PROF("conv16_kernel 3x3 (small grid)", s);
+    default: {  // C16
+      dim3 grid((unsigned)(a.tilesX * a.tilesY * B), (unsigned)(a.CoutPad / kCoutTile));
+      conv_plan_name(p, d->pool, nm, sizeof nm);
+      g_last_conv_kernel = nm;
+      EINX_PROF("conv16_kernel 3x3 (small grid)", s);
 #define EINX_C16(P, N) hipLaunchKernelGGL((conv16_kernel<P, 8, N>), grid, dim3(256), 0, s, a)
-        if (d->pool) {
-          if (npw == 4) EINX_C16(true, 4);
-          else if (npw == 2) EINX_C16(true, 2);
-          else EINX_C16(true, 1);
-        } else {
-          if (npw == 4) EINX_C16(false, 4);
-          else if (npw == 2) EINX_C16(false, 2);
-          else EINX_C16(false, 1);
-        }
-#undef EINX_C16
-        EINX_CHECK_LAUNCH();
-        return EINX_OK;
-      }
-    }
-    if (blocks_best < 512 && d->cin > 6) {
-      struct Lat {
-        int th, tw, unit;  // unit = waves per SIMD x accumulator tiles per wave
-      };
-      static const Lat pooled[4] = {{8, 32, 4}, {12, 16, 3}, {8, 16, 2}, {4, 16, 1}};
-      static const Lat plain[5] = {{8, 32, 4}, {11, 22, 4}, {12, 16, 3}, {11, 11, 2}, {11, 5, 1}};
-      const Lat* cand = d->pool ? pooled : plain;
-      const int nc = d->pool ? 4 : 5;
-      int pick = -1;
-      double best_est = 1e30;
-      for (int i = 0; i < nc; ++i) {
-        const long blocks = (long)einx_cdiv(H, cand[i].th) * einx_cdiv(W, cand[i].tw) * B * (a.CoutPad / kCoutTile);
-        const double est = (double)((blocks + 255) / 256) * cand[i].unit;
-        if (est < best_est - 1e-9) {
-          best_est = est;
-          pick = i;
-        }
-      }
-      a.tilesX = einx_cdiv(W, cand[pick].tw);
-      a.tilesY = einx_cdiv(H, cand[pick].th);
       if (d->pool) {
-        switch (pick) {
-          case 0: launch<3, 8, 32, 2, 4, 1, 2, 8, true>(a, B, s); break;
-          case 1: launch<3, 12, 16, 2, 2, 1, 3, 8, true>(a, B, s); break;
-          case 2: launch<3, 8, 16, 2, 2, 1, 2, 8, true>(a, B, s); break;
-          default: launch<3, 4, 16, 2, 2, 1, 1, 8, true>(a, B, s); break;
-        }
+        if (p.npw == 4) EINX_C16(true, 4);
+        else if (p.npw == 2) EINX_C16(true, 2);
+        else EINX_C16(true, 1);
       } else {
-        switch (pick) {
-          case 0: launch<3, 8, 32, 2, 4, 1, 2, 8, false>(a, B, s); break;
-          case 1: launch<3, 11, 22, 2, 4, 1, 2, 8, false>(a, B, s); break;
-          case 2: launch<3, 12, 16, 2, 2, 1, 3, 8, false>(a, B, s); break;
-          case 3: launch<3, 11, 11, 2, 2, 1, 2, 8, false>(a, B, s); break;
-          default: launch<3, 11, 5, 2, 2, 1, 1, 8, false>(a, B, s); break;
-        }
+        if (p.npw == 4) EINX_C16(false, 4);
+        else if (p.npw == 2) EINX_C16(false, 2);
+        else EINX_C16(false, 1);
       }
-      EINX_CHECK_LAUNCH();
-      return EINX_OK;
-    }
-  }
-  a.tilesX = einx_cdiv(W, cfgs[best].tw);
-  a.tilesY = einx_cdiv(H, cfgs[best].th);
-  // Wave layouts (measured per layer, bench.py --layer-table): 8 waves (2 channel groups x 4 pixel
-  // groups, one 32x64 accumulator block each) for the 256-slot tiles -- two waves per SIMD from one
-  // workgroup hide each other's LDS/epilogue latency at half the accumulator registers per wave;
-  // 4 waves of 1x3 tiles for the 192-slot tiles (6 waves load the 4 SIMDs unevenly: -25 %) and
-  // 4 waves for the 1x1 heads.
-  if (d->pool) {
-    switch (best) {
-      case 0: launch<3, 8, 32, 2, 4, 1, 2, 8, true, true>(a, B, s); break;
-      case 1: launch<3, 12, 16, 2, 2, 1, 3, 8, true>(a, B, s); break;
-      default: launch<3, 22, 8, 2, 2, 1, 3, 8, true>(a, B, s); break;
-    }
-  } else {
-    switch (best) {
-      case 0:
-        // thin first layers (1 / 5 input channels): stage only the channel pairs that exist
-        if (d->cin <= 2) launch<3, 8, 32, 2, 4, 1, 2, 2, false>(a, B, s);
-        else if (d->cin <= 6) launch<3, 8, 32, 2, 4, 1, 2, 6, false>(a, B, s);
-        else launch<3, 8, 32, 2, 4, 1, 2, 8, false, true>(a, B, s);
-        break;
-      case 1: launch<3, 12, 16, 2, 2, 1, 3, 8, false>(a, B, s); break;
-      case 2: launch<3, 22, 8, 2, 2, 1, 3, 8, false>(a, B, s); break;
-      case 3: launch<3, 11, 22, 2, 4, 1, 2, 8, false>(a, B, s); break;
-      default: launch<3, 11, 11, 2, 2, 1, 2, 8, false>(a, B, s); break;
+#undef EINX_C16
+      break;
     }
   }
   EINX_CHECK_LAUNCH();
   return EINX_OK;
+}
+
+// the name of the instantiation einx_conv_block would launch for these arguments: conv_plan without the launch
+EINX_EXPORT const char* einx_conv_plan(int cin, int cout, int ks, int pool, int B, int Hs, int Ws, int h0, int w0, int H, int W) {
+  const ConvPlanLayer pl = {cin, cout, ks, pool};
+  if (const char* refused = conv_shape_refused(&pl, B, Hs, Ws, h0, w0, H, W)) {  // what einx_conv_block refuses has no plan
+    einx_set_error("%s: %s", __func__, refused);
+    return nullptr;
+  }
+  static thread_local char nm[96];
+  conv_plan_name(conv_plan(&pl, B, Hs, Ws, h0, w0, H, W), pool, nm, sizeof nm);
+  return nm;
 }

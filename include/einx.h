@@ -137,6 +137,13 @@ int einx_conv_first_two_fused(const float* in, int B, int Hs, int Ws, int h0, in
  * profiles and bench lines, so that a reported kernel name cannot go stale against the dispatcher */
 const char* einx_conv_last_kernel(void);
 
+/* name of the instantiation einx_conv_block WOULD launch for a layer (cin, cout, ks, pool) and a call (B, Hs, Ws, h0, w0, H, W):
+ * the dispatcher's own selection code without the launch, the same strings as einx_conv_last_kernel.  Host only: no device
+ * pointer, no HIP call, usable without a GPU (the tests' coverage table of instantiations is checked with it).  NULL for
+ * arguments einx_conv_block refuses.  The string belongs to the calling thread and holds until its next call.
+ * (einx_conv_first_two_fused_ok stays the query for the fused first pair.) */
+const char* einx_conv_plan(int cin, int cout, int ks, int pool, int B, int Hs, int Ws, int h0, int w0, int H, int W);
+
 /* x /= divisor in place (SuperPointv1.forward `image /= 255.0`, superpoint_extractor.py:372) */
 int einx_div_inplace(float* x, size_t n, float divisor, void* stream);
 

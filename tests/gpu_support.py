@@ -28,25 +28,27 @@ def _np(t):
 
 # ------------------------------------------------------------------ conv blocks vs oracle (bit exact)
 CONV_SHAPES = [
-    # cin, cout, H, W, ks, relu, bn, pool, fold(h0,w0,Hs,Ws) or None
-    (1, 64, 40, 48, 3, True, False, False, (1, 2, 37, 45)),
-    (5, 64, 40, 48, 3, True, True, False, (1, 2, 37, 45)),
-    (16, 64, 24, 64, 3, True, True, False, None),
-    (64, 64, 40, 64, 3, True, True, True, None),       # tile (8,32) pooled
-    (64, 64, 24, 32, 3, True, False, True, None),      # tile (12,16) pooled
-    (64, 128, 22, 24, 3, True, True, False, None),
-    (128, 128, 44, 16, 3, True, True, True, None),     # tile (22,8) pooled
-    (128, 128, 33, 44, 3, True, True, False, None),    # tile (11,22)
-    (128, 256, 33, 44, 3, True, False, False, None),
-    (256, 65, 33, 44, 1, False, False, False, None),
-    (256, 256, 5, 6, 1, False, True, False, None),
-    (128, 1, 37, 45, 1, False, True, False, None),
-    (6, 7, 9, 10, 3, False, True, False, None),        # ragged everything
-    (64, 256, 132, 176, 3, True, True, False, None),   # 11x22 tile preferred over 12x16 (768 workgroups), generic reload path
-    (64, 64, 132, 176, 3, True, False, True, None),    # 12x16 pooled, offset-table reload
-    (8, 64, 16, 16, 3, True, True, False, None),       # one chunk, offset-table reload
-    (256, 64, 33, 44, 1, False, True, False, None),    # 1x1 with 128-pixel runs
-    (256, 130, 120, 90, 1, True, False, False, None),  # 1x1, ragged cout (the 256-pixel-run variant is exercised by the SiLK e2e cases)
+    # cin, cout, H, W, ks, relu, bn, pool, fold(h0,w0,Hs,Ws) or None        # the kernel the dispatcher selects at the test's B = 2
+    # (comments checked against einx_conv_plan; test_conv_block_bit_exact asserts launch == plan.  Per-instantiation coverage is
+    # conv_plan_cases.CONV_PLAN_CASES, not this table: 13 of its 18 entries are small grids that land on the conv16 kernels)
+    (1, 64, 40, 48, 3, True, False, False, (1, 2, 37, 45)),  # generic 12x16 (thin layer, CK = 8), fold
+    (5, 64, 40, 48, 3, True, True, False, (1, 2, 37, 45)),   # generic 12x16 (thin layer), fold
+    (16, 64, 24, 64, 3, True, True, False, None),            # conv16_kernel<false,8,1>
+    (64, 64, 40, 64, 3, True, True, True, None),             # conv16_kernel<true,8,1>
+    (64, 64, 24, 32, 3, True, False, True, None),            # conv16_kernel<true,8,1>
+    (64, 128, 22, 24, 3, True, True, False, None),           # conv16_kernel<false,8,1>
+    (128, 128, 44, 16, 3, True, True, True, None),           # conv16_kernel<true,8,1>
+    (128, 128, 33, 44, 3, True, True, False, None),          # conv16_kernel<false,8,1>
+    (128, 256, 33, 44, 3, True, False, False, None),         # conv16_kernel<false,8,1>
+    (256, 65, 33, 44, 1, False, False, False, None),         # conv16_1x1_kernel<1>
+    (256, 256, 5, 6, 1, False, True, False, None),           # conv16_1x1_kernel<1>
+    (128, 1, 37, 45, 1, False, True, False, None),           # conv16_1x1_kernel<1>
+    (6, 7, 9, 10, 3, False, True, False, None),              # generic 11x11 (thin layer); ragged everything
+    (64, 256, 132, 176, 3, True, True, False, None),         # generic 12x16, un-pooled (exact tiling, 968 workgroups)
+    (64, 64, 132, 176, 3, True, False, True, None),          # generic 12x16 pooled
+    (8, 64, 16, 16, 3, True, True, False, None),             # conv16_kernel<false,8,1>, one chunk
+    (256, 64, 33, 44, 1, False, True, False, None),          # conv16_1x1_kernel<1>
+    (256, 130, 120, 90, 1, True, False, False, None),        # conv16_1x1_kernel<4>, ragged cout
 ]
 
 

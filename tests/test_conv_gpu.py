@@ -13,6 +13,7 @@ import time
 from importlib import import_module
 
 from helpers import (score_map, sub_dict, synth)
+from conv_plan_cases import CONV_PLAN_CASES, case_id, plan_args, plan_name
 from gpu_support import (CONV16_1X1_SHAPES, CONV16_SHAPES, CONV_SEEDS, CONV_SHAPES, DEV, _four_pairs, _need_free_gb, _np, _rng,
                          _sp_mnn_model, _t, _tiled, pkg)
 
@@ -43,7 +44,56 @@ def test_conv_block_bit_exact(oracle, shape):
     exp = oracle.conv_block(xin, w, b, scale, shift, relu=relu, pool=pool)
     layer = pkg.native.ConvLayer(_t(w), _t(b), bnp, relu=relu, pool=pool)
     got = layer(_t(x), fold=(fold[0], fold[1], H, W) if fold else None)
+    L = pkg.native.lib()  # what was launched is what the plan query answers for the same call
+    assert L.einx_conv_last_kernel().decode() == plan_name(L, cin, cout, ks, pool, B, Hs, Ws, fold[0] if fold else 0, fold[1] if fold else 0, H, W)
     assert np.array_equal(_np(got), exp)
+
+
+GUARD = 4096    # bytes before and after the output tensor (the convention of test_workspace_gpu.py)
+PATTERN = 0xA5
+
+
+@pytest.mark.parametrize("case", CONV_PLAN_CASES, ids=case_id)
+def test_every_conv_instantiation_bit_exact(oracle, case):
+    """One launch per row of the coverage table (conv_plan_cases.py: every kernel instantiation einx_conv_block can select, at
+    partial and exact tiles, ragged channels, folds) through the op-level ABI: the kernel launched is the one the row names and
+    the one einx_conv_plan answers; the output equals the oracle bit for bit; the output tensor was pre-filled with NaN and sits
+    between two guard zones, which a partial tile's stray store would break without showing in the comparison."""
+    import ctypes
+    B, cin, cout, H, W, ks, relu, bn, pool, fold, name = case
+    seed = 9000 + 13 * CONV_PLAN_CASES.index(case)
+    h0, w0, Hs, Ws = fold if fold else (0, 0, H, W)
+    x = synth.normalish(seed, (B, cin, Hs, Ws))
+    w = synth.synth_param("c.weight", (cout, cin, ks, ks), seed)
+    b = synth.uniform(seed + 1, (cout,), -0.5, 0.5)
+    bnp = scale = shift = None
+    if bn:
+        g, be = synth.uniform(seed + 2, (cout,), 0.5, 1.5), synth.uniform(seed + 3, (cout,), -0.3, 0.3)
+        mu, var = synth.uniform(seed + 4, (cout,), -0.3, 0.3), synth.uniform(seed + 5, (cout,), 0.5, 1.5)
+        g[cout // 2] = -g[cout // 2]  # negative gain: BN must stay after ReLU and before the pool
+        scale, shift = oracle.bn_fold(g, be, mu, var)
+        bnp = (_t(g), _t(be), _t(mu), _t(var), 1e-5)
+    xin = oracle.pad_replicate(x, (w0, W - Ws - w0, h0, H - Hs - h0)) if fold else x
+    exp = oracle.conv_block(xin, w, b, scale, shift, relu=relu, pool=pool)
+    layer = pkg.native.ConvLayer(_t(w), _t(b), bnp, relu=relu, pool=pool)
+    xt = _t(x)
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    nbytes = 4 * B * cout * Ho * Wo
+    buf = torch.full((GUARD + nbytes + GUARD,), PATTERN, dtype=torch.uint8, device=DEV)
+    got = buf[GUARD:GUARD + nbytes].view(torch.float32).view(B, cout, Ho, Wo)
+    got.fill_(float("nan"))
+    torch.cuda.synchronize()
+    L = pkg.native.lib()
+    rc = L.einx_conv_block(ctypes.c_void_p(xt.data_ptr()), B, Hs, Ws, h0, w0, H, W, ctypes.byref(layer.desc), ctypes.c_void_p(got.data_ptr()), None)
+    assert rc == 0, L.einx_last_error()
+    launched = L.einx_conv_last_kernel().decode()
+    torch.cuda.synchronize()
+    assert launched == name, launched
+    assert launched == plan_name(L, *plan_args(case))
+    assert np.array_equal(_np(got), exp)
+    for side, zone in (("before", buf[:GUARD]), ("behind", buf[GUARD + nbytes:])):
+        bad = int((zone != PATTERN).sum())
+        assert bad == 0, f"{bad} of the {GUARD} guard bytes {side} the output were overwritten"
 
 
 @pytest.mark.parametrize("pool", [True, False])
@@ -319,4 +369,7 @@ def test_random_conv_blocks(oracle, seed):
     exp = oracle.conv_block(xin, w, b, scale, shift, relu=relu, pool=pool)
     layer = pkg.native.ConvLayer(_t(w), _t(b), bnp, relu=relu, pool=pool)
     got = layer(_t(x), fold=(fold[0], fold[1], H, W) if fold else None)
+    L = pkg.native.lib()
+    launched = L.einx_conv_last_kernel().decode()
+    assert launched == plan_name(L, cin, cout, ks, pool, B, Hs, Ws, fold[0] if fold else 0, fold[1] if fold else 0, H, W), launched
     assert np.array_equal(_np(got), exp), (ks, cin, cout, H, W, B, pool, relu, bn, fold)
