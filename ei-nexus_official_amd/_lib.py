@@ -161,6 +161,7 @@ SIGNATURES = {
                                  c_void_p]),
     "einx_distance_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
+    "einx_distance_map_plan": (c_char_p, [c_int, c_int]),
     "einx_events_windows_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "einx_voxel_windows_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, ctypes.c_int64]),
     "einx_voxel_grid_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -191,6 +191,32 @@ __global__ __launch_bounds__(64) void distance_map_kernel(const uint32_t* bits_a
   dm_sweep<PPL, true>(bits, ww, (int*)out, out, H, W);
 }
 
+template <int PPL>
+void launch_distance_map(const uint32_t* bits, int slices, int H, int W, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(distance_map_kernel<PPL>, dim3((unsigned)slices), dim3(64), 0, s, bits, H, W, out);
+}
+
+// The instantiations, narrowest first: pixels per lane, the name einx_distance_map_plan reports, the launch.  A new arm is a line
+// here (and its widths in tests/event_reps_cases.py).
+struct DmArm {
+  int ppl;
+  const char* name;
+  void (*launch)(const uint32_t*, int, int, int, float*, hipStream_t);
+};
+#define DM_ARM(P) {P, "distance_map_kernel<" #P ">", launch_distance_map<P>}
+constexpr DmArm DM_ARMS[] = {DM_ARM(2), DM_ARM(4), DM_ARM(6), DM_ARM(8), DM_ARM(12), DM_ARM(16)};
+#undef DM_ARM
+static_assert(DM_ARMS[sizeof(DM_ARMS) / sizeof(DM_ARMS[0]) - 1].ppl * 64 == DM_MAX_W, "the widest arm sets the documented limit");
+
+// the one selection, used by the launch and by einx_distance_map_plan: the first arm whose 64 lanes hold a row of W pixels;
+// nullptr for a shape the op refuses
+const DmArm* dm_select(int H, int W) {
+  if (H <= 0 || W <= 0 || W > DM_MAX_W || H > DM_MAX_H) return nullptr;
+  for (const DmArm& a : DM_ARMS)
+    if (einx_cdiv(W, 64) <= a.ppl) return &a;
+  return nullptr;
+}
+
 // workspace of all three ops: ONE region of 32-bit words the event pass fills (time surface: winner index + 1 per cell, event
 // stack: int32 sum per cell, distance map: one bit per pixel in rows of ceil(W / 32) words), and 256 bytes of slack that pay
 // for rounding the caller's base up
@@ -204,7 +230,7 @@ uint32_t* carve(WsCarver& c, int mode, int B, int bins, int H, int W) {
 bool rep_shape_ok(int mode, int B, int bins, int H, int W) {
   if (B <= 0 || bins <= 0 || H <= 0 || W <= 0 || H >= 60000 || W >= 60000) return false;
   if (mode == REP_TIME_SURFACE && bins < 2) return false;  // bins // 2 == 0 bins: the reference divides by zero
-  if (mode == REP_DISTANCE_MAP && (W > DM_MAX_W || H > DM_MAX_H)) return false;
+  if (mode == REP_DISTANCE_MAP && !dm_select(H, W)) return false;
   return true;
 }
 
@@ -213,11 +239,6 @@ size_t rep_ws_bytes(int mode, int B, int bins, int H, int W, int64_t total_event
   WsCarver c{nullptr};
   carve(c, mode, B, bins, H, W);
   return c.bytes;
-}
-
-template <int PPL>
-void launch_distance_map(const uint32_t* bits, int slices, int H, int W, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(distance_map_kernel<PPL>, dim3((unsigned)slices), dim3(64), 0, s, bits, H, W, out);
 }
 
 template <int MODE>
@@ -278,13 +299,7 @@ int rep_run(const char* name, const float* x, const float* y, const double* t, c
     EINX_CHECK_LAUNCH();
   }
   if (MODE == REP_DISTANCE_MAP) {
-    const int ppl = einx_cdiv(W, 64), slices = B * bins;
-    if (ppl <= 2) launch_distance_map<2>(words, slices, H, W, out, s);
-    else if (ppl <= 4) launch_distance_map<4>(words, slices, H, W, out, s);
-    else if (ppl <= 6) launch_distance_map<6>(words, slices, H, W, out, s);
-    else if (ppl <= 8) launch_distance_map<8>(words, slices, H, W, out, s);
-    else if (ppl <= 12) launch_distance_map<12>(words, slices, H, W, out, s);
-    else launch_distance_map<16>(words, slices, H, W, out, s);
+    dm_select(H, W)->launch(words, B * bins, H, W, out, s);  // never null here: rep_shape_ok asked dm_select too
     EINX_CHECK_LAUNCH();
   }
   return EINX_OK;
@@ -300,6 +315,11 @@ EINX_EXPORT size_t einx_event_stack_ws_bytes(int B, int bins, int H, int W, int6
 }
 EINX_EXPORT size_t einx_distance_map_ws_bytes(int B, int bins, int H, int W, int64_t total_events) {
   return rep_ws_bytes(REP_DISTANCE_MAP, B, bins, H, W, total_events);
+}
+
+EINX_EXPORT const char* einx_distance_map_plan(int H, int W) {
+  const DmArm* a = dm_select(H, W);
+  return a ? a->name : nullptr;
 }
 
 EINX_EXPORT int einx_time_surface(const float* x, const float* y, const double* t, const float* p, const int64_t* offsets_host, int B,

@@ -432,6 +432,11 @@ int einx_event_stack(const float* x, const float* y, const double* t, const floa
  * W <= 1024, H <= 4096. */
 int einx_distance_map(const float* x, const float* y, const double* t, const float* p, const int64_t* offsets_host, int B, int bins, int H,
                       int W, float* out, void* ws, size_t ws_bytes, void* stream);
+/* name of the instantiation einx_distance_map WOULD launch for [H,W] slices, e.g. "distance_map_kernel<8>" (pixels per lane, from
+ * ceil(W / 64): 2, 4, 6, 8, 12 or 16): the op's own selection function without the launch, the names tools/kernel_resources.py
+ * prints.  Host only: no HIP call, usable without a GPU (the tests' table of widths is checked with it).  NULL for a shape the op
+ * refuses (W > 1024, H > 4096, H <= 0 or W <= 0).  The string is static. */
+const char* einx_distance_map_plan(int H, int W);
 
 /* Windowed forms of einx_voxel_grid and einx_events_mask: x / y / p (fp32) and t (fp64) are the device arrays of a
  * WHOLE sequence of stream_len events, uploaded once, and sample b is its events begin_host[b] <= k < end_host[b], in stream order

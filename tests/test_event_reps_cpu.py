@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import event_reps_ref as R
+from event_reps_cases import DISTANCE_MAP_CASES, DISTANCE_MAP_NAMES, MAX_SET, case_events, case_id, plan_name
 from helpers import Golden, load_pkg, row_checksums
 
 pkg = load_pkg()
@@ -106,6 +107,66 @@ def test_ws_bytes_queries(op):
     assert q(32, 16, 260, 346, 0) == n  # the events take no workspace
 
 
+def test_distance_map_plan_covers_every_width():
+    """einx_distance_map_plan (the selection einx_distance_map launches from, without the launch): every width the op takes, at
+    the smallest and the largest height, plans to a name that has rows in tests/event_reps_cases.py; all six arms occur there; what
+    the op refuses plans to NULL, and the size query gives 0 for the same shapes"""
+    L = pkg.native.lib()
+    assert "einx_distance_map_plan" in import_module(pkg.__name__ + "._lib").SIGNATURES
+    assert DISTANCE_MAP_NAMES == [f"distance_map_kernel<{ppl}>" for ppl in (2, 4, 6, 8, 12, 16)]
+    for H in (1, 4096):
+        for W in range(1, 1025):
+            name = plan_name(L, H, W)
+            assert name in DISTANCE_MAP_NAMES, (H, W, name)
+            assert L.einx_distance_map_ws_bytes(1, 1, H, W, 0) > 0, (H, W)
+    for H, W in ((1, 1025), (4096, 1025), (4097, 1), (4097, 1024), (0, 5), (5, 0), (-1, 5), (5, -1), (0, 0)):
+        assert plan_name(L, H, W) is None, (H, W)
+        assert L.einx_distance_map_ws_bytes(1, 1, H, W, 0) == 0, (H, W)
+
+
+@pytest.mark.parametrize("case", DISTANCE_MAP_CASES, ids=case_id)
+def test_distance_map_case_plans_to_its_name(case):
+    H, W, name = case
+    assert plan_name(pkg.native.lib(), H, W) == name
+
+
+def _forward_sweep_only(mask):
+    """event_reps_ref.chamfer_sweep without its second half: the distances a kernel would give whose backward sweep did nothing"""
+    H, W = mask.shape
+    d = np.where(mask, 0, R.INF).astype(np.int64)
+    ramp = R.HV * np.arange(W, dtype=np.int64)
+    prev = np.full(W, R.INF, np.int64)
+    for y in range(H):
+        p = np.concatenate(([R.INF], prev, [R.INF]))
+        c = np.minimum(d[y], np.minimum(np.minimum(p[:-2], p[2:]) + R.DIAG, prev + R.HV))
+        prev = d[y] = ramp + np.minimum.accumulate(c - ramp)
+    return np.minimum(d, R.INF).astype(np.float32) * np.float32(1.0 / 65536.0)
+
+
+@pytest.mark.parametrize("case", DISTANCE_MAP_CASES, ids=case_id)
+def test_distance_map_case_events_draw_their_patterns(case):
+    """the events of a table row: their occupancy under the contract (first and last event dropped, yet defining the time
+    normalisation) is exactly the intended pattern per bin; no slice has more than 16 set pixels, so the closed form is cheap; the
+    closed form equals the two sweeps; and the forward sweep alone does not, so the row needs the backward sweep.  (The 1x1 map
+    is the one exception to the last point: its only pixel has no neighbour, so the forward sweep alone is exact there.)"""
+    H, W, _ = case
+    events_list, size, masks = case_events(H, W)
+    assert len(events_list) == 2 and size == (9, H, W)
+    forward_differs = False
+    for b, (ev, mask) in enumerate(zip(events_list, masks)):
+        empty = 8 - b  # sample 1 holds the patterns rotated by one bin
+        assert ev["x"][0] < 0 and ev["x"][-1] < 0 and ev["t"][0] == 1.5e9 and ev["t"][-1] == 1.5e9 + 0.05
+        assert np.array_equal(R.occupancy(ev, size), mask)
+        assert mask.reshape(9, -1).sum(1).max() <= MAX_SET
+        assert [i for i in range(9) if not mask[i].any()] == [empty]
+        for m in mask:
+            closed = R.chamfer(m)
+            assert np.array_equal(closed, R.chamfer_sweep(m))
+            forward_differs |= not np.array_equal(closed, _forward_sweep_only(m))
+        assert np.array_equal(R.chamfer(mask[empty]), np.full((H, W), 8192.0, np.float32))
+    assert forward_differs == ((H, W) != (1, 1))
+
+
 def test_representation_table():
     rep = import_module(pkg.__name__ + ".datasets.representations")
     assert set(rep.REPRESENTATIONS) == {"VoxelGrid", "TimeSurface", "EventStack", "EventDistanceMap"}
@@ -127,7 +188,7 @@ def test_no_kernel_uses_scratch():
     kernels = json.loads(subprocess.run(cmd, capture_output=True, text=True, check=True).stdout)
     names = " ".join(k["name"] for k in kernels)
     for want in ("rep_events_kernel<0>", "rep_events_kernel<1>", "rep_events_kernel<2>", "time_surface_gather_kernel", "event_stack_convert_kernel",
-                 "distance_map_kernel<2>", "distance_map_kernel<6>", "distance_map_kernel<16>"):
+                 *DISTANCE_MAP_NAMES):
         assert want in names, (want, names)
     for k in kernels:
         assert int(k["ScratchSize [bytes/lane]"]) == 0 and int(k["VGPRs Spill"]) == 0 and int(k["LDS Size [bytes/block]"]) == 0, k

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import event_reps_ref as R
+from event_reps_cases import DISTANCE_MAP_CASES, case_events, case_id, plan_name
 from helpers import Golden, row_checksums, synth, synth_raw_events
 from gpu_support import DEV, _np, _t, pkg
 
@@ -129,6 +130,70 @@ def test_batch_with_empty_sample_stage_path_and_capture():
             graph.replay()
             torch.cuda.synchronize()
             assert np.array_equal(_bits(_np(out)), _bits(got)), name
+
+
+@pytest.mark.parametrize("case", DISTANCE_MAP_CASES, ids=case_id)
+def test_every_distance_map_arm(case):
+    """tests/event_reps_cases.py: every instantiation of distance_map_kernel at the first, the last and the exact-fit widths of its
+    arm, H = 1 / 2 / 7, sparse patterns (corners, far columns, an empty bin) whose distances cross all 64 lanes and climb from the
+    last row: bit-equal to the closed form for both samples, from the instantiation the row names, twice the same bits"""
+    H, W, name = case
+    events_list, size, _ = case_events(H, W)
+    got = _np(rep.events_to_distance_map_batch(events_list, size, DEV))
+    assert got.shape == (2,) + size and got.dtype == np.float32
+    for b, ev in enumerate(events_list):
+        assert np.array_equal(_bits(got[b]), _bits(R.distance_map(ev, size, form=R.chamfer))), (case, b)
+    assert plan_name(pkg.native.lib(), H, W) == name
+    assert np.array_equal(_bits(got), _bits(_np(rep.events_to_distance_map_batch(events_list, size, DEV)))), "two runs differ"
+
+
+BIG_B, BIG_SIZE = 193, (4, 5, 9)
+
+
+def _big_batch():
+    """B = 193 samples: four launches of 64 (the offsets travel as kernel arguments, 64 samples at a time).  Samples 63 and 191
+    (the last of a launch) are empty; all of 64..127 are, so the second launch has no event at all; sample 150 has 700 events, so
+    only the third launch has more than one block of events; sample 192 makes a last launch of one sample; every other sample
+    has (37 b) % 23 events."""
+    bins, H, W = BIG_SIZE
+    n = [0 if b in (63, 191) or 64 <= b < 128 else 700 if b == 150 else (37 * b) % 23 for b in range(BIG_B)]
+    assert n[192] > 0 and n[62] > 0 and n[128] > 0 and max(n[:128] + n[151:]) < 256
+    return [synth_raw_events(dict(seed=1000 + 5 * b, n=k, H=H, W=W, bins=bins, frac=True, pneg=True)) for b, k in enumerate(n)]
+
+
+def test_batches_beyond_one_chunk():
+    """all three ops at B = 193: every sample equals its own restatement bit for bit (the distance map: the closed form), the
+    empty samples are all 0.0 (distance map: 8192.0); a capture of the raw call, replayed into an output poisoned with NaN, gives the
+    same bits, the launch without events included"""
+    evs = _big_batch()
+    L, N = pkg.native.lib(), pkg.native
+    x, y, t, p, offs = rep._pack(evs, DEV)
+    for name, (_, ref) in OPS.items():
+        op = {"TimeSurface": "time_surface", "EventStack": "event_stack", "EventDistanceMap": "distance_map"}[name]
+        expect = np.stack([ref(e, BIG_SIZE) for e in evs])
+        fill = 8192.0 if name == "EventDistanceMap" else 0.0
+        for b, e in enumerate(evs):
+            if len(e["t"]) == 0:
+                assert (expect[b] == fill).all()
+        out = torch.full((BIG_B,) + BIG_SIZE, float("nan"), device=DEV)
+        ws = torch.empty(getattr(L, f"einx_{op}_ws_bytes")(BIG_B, *BIG_SIZE, int(offs[-1])), dtype=torch.uint8, device=DEV)
+        call = lambda: getattr(L, f"einx_{op}")(N._ptr(x), N._ptr(y), N._ptr(t), N._ptr(p), offs.ctypes.data_as(ctypes.c_void_p), BIG_B,  # noqa: E731
+                                                *BIG_SIZE, N._ptr(out), N._ptr(ws), ws.numel(), N._stream(out))
+        assert call() == 0
+        torch.cuda.synchronize()
+        got = _np(out)
+        bad = [b for b in range(BIG_B) if not np.array_equal(_bits(got[b]), _bits(expect[b]))]
+        assert not bad, (name, bad)
+        assert np.array_equal(_bits(got), _bits(_np(rep.REPRESENTATIONS[name](evs, BIG_SIZE, DEV)))), name  # the package's own path
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rc = call()
+        assert rc == 0
+        out.fill_(float("nan"))
+        ws.fill_(0xAB)
+        graph.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(_bits(_np(out)), _bits(expect)), name
 
 
 def test_bad_arguments_are_refused():
