@@ -112,8 +112,8 @@ def upsample_case(seed):
 
 def mnn_case(seed):
     r = np.random.default_rng(seed)
-    D = int(r.choice([32, 64, 128, 256]))
-    n0, n1 = int(r.choice([1, 2, 3, 17, 130, 700, 1024])), int(r.choice([2, 3, 17, 129, 700, 1024]))
+    D = int(r.choice([32, 36, 64, 100, 128, 256, 260]))  # 36, 100, 260: a partial last K-slab of the 32-wide tile engine
+    n0, n1 = int(r.choice([1, 2, 3, 17, 130, 700, 1024, 1500])), int(r.choice([2, 3, 17, 129, 700, 1024, 1500]))  # 1500: a second trip of the 1024-thread loops
     ratio = r.choice([None, 0.8, 0.95]) if n1 >= 2 and n0 >= 2 else None
     dist = r.choice([None, 0.7, 1.2])
     ratio = None if ratio is None else float(ratio)
