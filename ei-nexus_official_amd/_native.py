@@ -321,12 +321,16 @@ def upsample_normalize(raw, padded_size, pads, scale):
 
 # ------------------------------------------------------------------------------ matching
 class MatchResult:
-    __slots__ = ("matches0", "matches1", "scores0", "scores1", "la", "mk0", "mk1", "nmatch", "ref0", "ref1", "mk0_flat", "mk1_flat", "stale", "stop")
+    __slots__ = ("matches0", "matches1", "scores0", "scores1", "la", "mk0", "mk1", "nmatch", "ref0", "ref1", "mk0_flat", "mk1_flat", "stale", "stop",
+                 "prune0", "prune1", "kept0", "kept1", "live")
 
     def __init__(self):
         self.mk0_flat = self.mk1_flat = None
         self.stale = None  # device int32 [1]: the matcher's weight watch (LightGlue), read back with the match counts
         self.stop = None  # device int32 [B]: the layer count each pair ran (LightGlue with early stopping only)
+        # LightGlue with point pruning only: prune0/1 float32 [B,cap] (1 + the pruning steps a point survived), kept0/1
+        # int64 [B,cap] (the survivors' original indices in compacted order, -1 behind them), live int32 [2B] (survivors per side)
+        self.prune0 = self.prune1 = self.kept0 = self.kept1 = self.live = None
 
 
 def mnn(desc0, n, desc1, m, want_la=True, ratio_thresh=None, distance_thresh=None, gather=None):
@@ -398,18 +402,27 @@ def compact_matches(r):
     return r
 
 
-def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False, early_stop=None):
+def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False, early_stop=None, pruning=None):
     """weights: _lib.LgWeights; pb0/pb1: PairBatch (kpts [B,cap,3], desc [B,cap,Din], counts).
     all_layers: ref0/ref1 are [B,n_layers,cap,d] (training-mode ref_descriptors) instead of [B,cap,d].
     early_stop = (heads, depth_confidence): einx_lightglue_early_stop with the _lib.LgHead array of every layer's heads; r.stop
-    [B] int32 is the number of layers each pair ran."""
+    [B] int32 is the number of layers each pair ran.
+    pruning = (heads, width_confidence, min_kpts): einx_lightglue_adaptive, with `early_stop` or without; r.prune0/1,
+    r.kept0/1 and r.live are set, r.la is None whatever want_la says, ref0 / ref1 hold the survivors' rows (zeros behind them)."""
     _dev_check(pb0.kpts, pb0.desc, pb1.kpts, pb1.desc)
     _dev_check(pb0.counts, pb1.counts, dt=I32)
     B, cap0, cap1 = pb0.B, pb0.cap, pb1.cap
     L = lib()
     dev = pb0.desc.device
     d = int(weights.d)
-    if early_stop is not None:
+    if pruning is not None:
+        if all_layers:
+            raise ValueError("einx LightGlue: point pruning returns the surviving rows the head read, not every layer's")
+        if not 0.0 < float(pruning[1]) <= 1.0:
+            raise ValueError("einx LightGlue: point pruning takes a width_confidence in (0, 1]")
+        want_la = False  # not produced (DESIGN.md 8j)
+        nbytes = L.einx_lightglue_adaptive_ws_bytes(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim), int(weights.n_layers))
+    elif early_stop is not None:
         if all_layers:
             raise ValueError("einx LightGlue: early stopping returns the descriptors the stopping head read, not every layer's")
         nbytes = L.einx_lightglue_early_stop_ws_bytes(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim), int(weights.n_layers))
@@ -432,6 +445,26 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False,
         r.ref0 = torch.empty((B, cap0, d), dtype=F32, device=dev) if want_ref else None
         r.ref1 = torch.empty((B, cap1, d), dtype=F32, device=dev) if want_ref else None
     (h0, w0), (h1, w1) = pb0.image_size, pb1.image_size
+    if pruning is not None:
+        heads, width, min_kpts = pruning
+        depth = float(early_stop[1]) if early_stop is not None else -1.0
+        if early_stop is not None:
+            r.stop = torch.empty((B,), dtype=torch.int32, device=dev)
+        if want_ref:  # rows past the live count are zero
+            r.ref0.zero_()
+            r.ref1.zero_()
+        r.prune0 = torch.empty((B, cap0), dtype=F32, device=dev)
+        r.prune1 = torch.empty((B, cap1), dtype=F32, device=dev)
+        r.kept0 = torch.empty((B, cap0), dtype=I64, device=dev)
+        r.kept1 = torch.empty((B, cap1), dtype=I64, device=dev)
+        r.live = torch.empty((2 * B,), dtype=I32, device=dev)
+        check(L.einx_lightglue_adaptive(ctypes.byref(weights), heads, ctypes.sizeof(heads._type_), depth, float(width), int(min_kpts),
+                                        _ptr(pb0.kpts), _ptr(pb0.desc), _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc), _ptr(pb1.counts),
+                                        cap1, B, float(h0), float(w0), float(h1), float(w1), _ptr(ws), _ptr(r.matches0), _ptr(r.matches1),
+                                        _ptr(r.scores0), _ptr(r.scores1), None, _ptr(r.ref0), _ptr(r.ref1), _ptr(r.stop), _ptr(r.prune0),
+                                        _ptr(r.prune1), _ptr(r.kept0), _ptr(r.kept1), _ptr(r.live), _stream(pb0.desc)),
+              "einx_lightglue_adaptive")
+        return r
     if early_stop is not None:
         heads, depth = early_stop
         r.stop = torch.empty((B,), dtype=torch.int32, device=dev)

@@ -333,7 +333,9 @@ class EIM(nn.Module):
         m = self.matcher.matcher
         mk = None if m is None else (type(m).__name__,) + tuple(repr(getattr(m, k, None)) for k in ("want_log_assignment", "ratio_thresh", "distance_thresh")) \
             + (repr(getattr(getattr(m, "conf", None), "filter_threshold", None)),) \
-            + (repr(getattr(m, "early_stop", None)), repr(getattr(getattr(m, "conf", None), "depth_confidence", None)))  # baked into a capture
+            + (repr(getattr(m, "early_stop", None)), repr(getattr(getattr(m, "conf", None), "depth_confidence", None))) \
+            + (repr(getattr(m, "point_pruning", None)), repr(getattr(getattr(m, "conf", None), "width_confidence", None)),
+               repr(getattr(m, "pruning_keypoint_thresholds", None)))  # baked into a capture
         return (ext(self.event_extractor.extractor), ext(self.image_extractor.extractor), mk, bool(getattr(self, "overlap_extractors", True)))
 
     @on_input_device

@@ -63,6 +63,11 @@ class Matcher(nn.Module):
         out = materialize_matches(r, n_host, m_host, nmatch_host, self._cols, prebuilt=prebuilt)
         if getattr(r, "stop", None) is not None:  # LightGlue with early stopping on: layers run, one int32 scalar per pair
             out["stop"] = list(r.stop.unbind(0))
+        if getattr(r, "live", None) is not None:  # LightGlue with point pruning on: per pair, padded to the capacity
+            B = r.kept0.shape[0]
+            out["kept0"], out["kept1"] = list(r.kept0.unbind(0)), list(r.kept1.unbind(0))  # int64, -1 behind the survivors
+            out["prune0"], out["prune1"] = list(r.prune0.unbind(0)), list(r.prune1.unbind(0))
+            out["live"] = list(r.live.view(2, B).t().unbind(0))  # int32 [2] per pair: survivors of side 0 and side 1
         return out
 
     # ---- un-frozen branch: pad to max_points_num (Matchers.py:67-149) ---------------------------

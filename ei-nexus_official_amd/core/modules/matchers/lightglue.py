@@ -10,7 +10,8 @@ a dense matrix (einx_lg_assign_nll); `NLLLoss` (:66-133) is the de
 torch operators.  Training mode (the layer loop, the token-confidence loss :190-203, autograd) is
 out of scope.
 Early stopping / point pruning are commented out in the reference (:606-652).  Early stopping (per-pair adaptive depth) is
-available here as an opt-in, `LightGlue.early_stop`; point pruning is refused.
+available here as an opt-in, `LightGlue.early_stop`, and so is point pruning (per-pair, per-side adaptive width),
+`LightGlue.point_pruning`.
 """
 import ctypes
 
@@ -166,7 +167,15 @@ class LightGlue(nn.Module):
     `confidence_thresholds`, is never created, so every pair runs every layer.  This class does the same by default.  Setting
     `early_stop = True` (with conf.depth_confidence > 0, in eval mode) runs the branch on the device, per pair
     (einx_lightglue_early_stop): results then DIFFER from the reference's for every pair that stops, which is
-    why the switch is opt-in rather than driven by the config key alone.  Outputs gain "stop" (layers run per pair)."""
+    why the switch is opt-in rather than driven by the config key alone.  Outputs gain "stop" (layers run per pair).
+
+    Point pruning.  The same holds for `width_confidence`: the reference's branch is commented out (:608-617, 637-652, 658-670),
+    `get_pruning_mask` / `pruning_min_kpts` are live, the dict they read, `pruning_keypoint_thresholds`, is never created.
+    `point_pruning = True` (with conf.width_confidence > 0, in eval mode) runs the branch on the device, per pair and per side
+    (einx_lightglue_adaptive): after every non-final layer a side with more than `pruning_min_kpts(device)` rows
+    drops the rows its matchability head calls unmatchable.  matches / scores stay in original indexing, prune0/1 hold the real
+    counts, outputs gain kept0/1 (the survivors' original indices), ref_descriptors hold the survivors' rows, and
+    "log_assignment" is absent.  A side pruned to zero rows finishes its pair without matches (upstream raises there)."""
     default_conf = {
         "name": "lightglue", "input_dim": 256, "add_scale_ori": False, "descriptor_dim": 256, "n_layers": 9, "num_heads": 4,
         "flash": False, "mp": False, "depth_confidence": -1, "width_confidence": -1, "filter_threshold": 0.0,
@@ -206,6 +215,10 @@ class LightGlue(nn.Module):
         # what the reference's confidence_threshold reads and never creates (:718-722, 468-470 commented out)
         self.confidence_thresholds = [self.confidence_threshold(i) for i in range(conf.n_layers)]
         self.early_stop = False  # opt-in: the reference ignores depth_confidence (see the class docstring)
+        self.point_pruning = False  # opt-in: the reference ignores width_confidence (see the class docstring)
+        # what the reference's pruning_min_kpts reads and never creates (:745-749): upstream LightGlue's published values, quoted
+        # (upstream is not at hand to check them against).  A side is pruned only while it has MORE rows than this.
+        self.pruning_keypoint_thresholds = {"cpu": -1, "mps": -1, "cuda": 1024, "flash": 1536}
         self._packed = None
         self._sig = None
         self._sig_tensors = None
@@ -229,10 +242,27 @@ class LightGlue(nn.Module):
         """whether the next eval-mode forward stops pairs early; depth_confidence is read at every call, like filter_threshold"""
         if not self.early_stop:
             return False
-        if float(self.conf.width_confidence) > 0:
+        if float(self.conf.width_confidence) > 0 and not self.point_pruning:
             raise NotImplementedError("einx LightGlue: early_stop with width_confidence > 0 asks for point pruning, which is not "
-                                      "implemented (DESIGN.md 8h)")
+                                      "implemented (DESIGN.md 8h); set point_pruning = True to run it (DESIGN.md 8j)")
         return not self.training and float(self.conf.depth_confidence) > 0
+
+    def point_pruning_active(self):
+        """whether the next eval-mode forward prunes points; width_confidence is read at every call, like depth_confidence"""
+        return bool(self.point_pruning) and not self.training and float(self.conf.width_confidence) > 0
+
+    def pruning_min_kpts(self, device):
+        """the gate (lightglue.py:745-749): a side is pruned only while it has more rows than this.  `flash` is not honoured here,
+        so its entry is never chosen."""
+        return self.pruning_keypoint_thresholds[torch.device(device).type]
+
+    def get_pruning_mask(self, confidences, scores, layer_index):
+        """which points stay (lightglue.py:723-730), in the float32 arithmetic of DESIGN.md 8j: the restatement of what the
+        device decides, on tensors of sigmoid outputs"""
+        keep = scores > float(np.float32(1.0 - float(self.conf.width_confidence)))
+        if confidences is not None:  # low-confidence points are never pruned
+            keep = keep | (confidences <= float(np.float32(self.confidence_thresholds[layer_index])))
+        return keep
 
     def refresh(self):
         """Drop the packed / folded weight images.  REQUIRED after edits through `p.data` (an alias with its own version
@@ -341,7 +371,10 @@ class LightGlue(nn.Module):
         w.filter_threshold = float(self.conf.filter_threshold)  # read at every call like the reference's filter_matches call (lightglue.py:656)
         stale = self._watch.check()
         es = (self._pack()[3], float(self.conf.depth_confidence)) if self.early_stop_active() else None
-        r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers, early_stop=es)
+        pr = None
+        if self.point_pruning_active():
+            pr = (self._pack()[3], float(self.conf.width_confidence), int(self.pruning_min_kpts(pb0.desc.device)))
+        r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers, early_stop=es, pruning=pr)
         r.stale = stale
         return N.gather_matches(r, pb0.kpts, pb1.kpts, pb0.counts, 2)
 
@@ -377,6 +410,7 @@ class LightGlue(nn.Module):
             self.refresh()
             r = self.match_batched(pb0, pb1, all_layers=all_layers)
             nm_all = r.nmatch.cpu().tolist() + [0]
+        pruned = r.live is not None  # point pruning ran: real prune counts, kept0/1, no log_assignment
         n = pb0.counts_host or pb0.counts.cpu().tolist()
         m = pb1.counts_host or pb1.counts.cpu().tolist()
         L = self.conf.n_layers
@@ -388,8 +422,12 @@ class LightGlue(nn.Module):
                 ref1 = r.ref1 if all_layers else r.ref1[:, None]
                 out["ref_descriptors0"] = ref0[:, :, :n[0]]
                 out["ref_descriptors1"] = ref1[:, :, :m[0]]
-                out["prune0"] = torch.ones_like(out["matching_scores0"]) * L
-                out["prune1"] = torch.ones_like(out["matching_scores1"]) * L
+                out["prune0"] = r.prune0[:, :n[0]] if pruned else torch.ones_like(out["matching_scores0"]) * L
+                out["prune1"] = r.prune1[:, :m[0]] if pruned else torch.ones_like(out["matching_scores1"]) * L
+            if pruned:
+                live = r.live.cpu().tolist()
+                out["kept0"], out["kept1"] = r.kept0[:, :live[0]], r.kept1[:, :live[1]]
+                out.pop("log_assignment", None)
             if r.stop is not None:
                 out["stop"] = r.stop
             return out
@@ -403,8 +441,11 @@ class LightGlue(nn.Module):
         out = stacked_outputs(r, r.nmatch.cpu().tolist(), 2)
         out["ref_descriptors0"] = r.ref0 if all_layers else r.ref0[:, None]
         out["ref_descriptors1"] = r.ref1 if all_layers else r.ref1[:, None]
-        out["prune0"] = torch.ones_like(r.scores0) * L
-        out["prune1"] = torch.ones_like(r.scores1) * L
+        out["prune0"] = r.prune0 if pruned else torch.ones_like(r.scores0) * L
+        out["prune1"] = r.prune1 if pruned else torch.ones_like(r.scores1) * L
+        if pruned:
+            out["kept0"], out["kept1"] = r.kept0, r.kept1
+            out.pop("log_assignment", None)
         if r.stop is not None:
             out["stop"] = r.stop
         return out
@@ -420,7 +461,8 @@ class LightGlue(nn.Module):
         A gt_assignment that is still a lazy entry of gt_generation's dict is handed over as pos0 and stays lazy; a tensor is
         read as the dense 0/1 matrix it is.  The reference's failures are mirrored: stacked labels with n != m raise its
         RuntimeError, more than one layer of ref_descriptors raises KeyError('confidence'); m == 1 < n (a silent broadcast there)
-        and training mode raise NotImplementedError.  A `pred` that carries "stop" (early stopping was on) raises ValueError."""
+        and training mode raise NotImplementedError.  A `pred` that carries "stop" (early stopping was on) or "kept0" (point pruning
+        was on: its ref_descriptors are a subset of the rows) raises ValueError."""
         from ....core.geometry.gt_generation import lazy_pos0
         if self.training:
             raise NotImplementedError("einx LightGlue.loss: training mode (layerwise totals, the token-confidence loss and a backward "
@@ -428,6 +470,9 @@ class LightGlue(nn.Module):
         if "stop" in pred:
             raise ValueError("einx LightGlue.loss: `pred` comes from a forward with early stopping on (it carries \"stop\"): its "
                              "ref_descriptors are those of each pair's stopping layer, and the loss applies the LAST head (DESIGN.md 8h)")
+        if "kept0" in pred:
+            raise ValueError("einx LightGlue.loss: `pred` comes from a forward with point pruning on (it carries \"kept0\"): its "
+                             "ref_descriptors hold only the surviving rows, and the labels are those of every keypoint (DESIGN.md 8j)")
         ref0, ref1 = pred["ref_descriptors0"], pred["ref_descriptors1"]
         if ref0.shape[1] > 1:
             raise KeyError("confidence")  # the reference's layer loop adds to a key that only training mode creates (:781)

@@ -914,6 +914,7 @@ struct StopArgs {
   float thr, depth;
   int32_t *below, *done;  // [B], zero between launches
   int32_t* stop;
+  const int32_t *tot0, *tot1;  // null, or the caller's counts: the ratio's denominator when rows have been pruned
 };
 
 // One launch per non-final layer: entry e < B is side 0 of pair e, entry e >= B side 1 of pair e - B; a workgroup takes STOP_ROWS
@@ -957,11 +958,192 @@ __global__ __launch_bounds__(256) void lg_stop_kernel(const StopArgs a) {
   __threadfence();
   const int total = atomicExch(&a.below[p], 0);
   atomicExch(&a.done[p], 0);
-  const float r = 1.0f - (float)total / (float)(n + m);
+  const int den = a.tot0 ? min(a.tot0[p], a.cap0) + min(a.tot1[p], a.cap1) : n + m;  // the reference divides by the ORIGINAL m + n (:635)
+  const float r = 1.0f - (float)total / (float)den;
   if (r > a.depth) {
     a.stop[p] = a.layer + 1;
     a.act0[p] = 0;
     a.act1[p] = 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Point pruning: per pair and side, rows whose matchability head calls them unmatchable leave the network.  The
+// survivors are compacted to the front in their order, and the side's active count shrinks: every kernel above skips the rest.
+// Per non-final layer, after the stop decision: lg_keep_kernel (the flags), lg_prune_scan_kernel (one workgroup per pair: new
+// positions, ind, prune, the counts), lg_prune_gather_kernel (x and the rotary encoding into buffers that are free between
+// layers) and lg_prune_copyback_kernel.  Launch boundaries are the only synchronisation; no float atomics, no atomics at all.
+// ------------------------------------------------------------------------------------------
+struct PruneArgs {
+  float *x0, *x1;      // [B,cap0,d], [B,cap1,d]
+  float *enc0, *enc1;  // [B,cap,2 dh]
+  float *tx0, *tx1;    // where the gather puts x: the sides' ctx
+  float *te0, *te1;    // ... and the encoding: the sides' h, rows packed at 2 dh floats from each entry's base
+  int32_t *act, *live, *prev;  // [2B] each: the layers' counts, the surviving rows, the surviving rows before this layer's step
+  int32_t *dst0, *dst1;        // [B,cap0], [B,cap1]: the keep flag, then the row's new position or -1
+  int64_t *kept0, *kept1;      // ind: position -> original index; -1 past the live count
+  float *prune0, *prune1;
+  int32_t* stop;
+  const int32_t *n, *m;        // the caller's counts
+  int cap0, cap1, d, dh2, B, layer, min_kpts, set_stop;
+  const float *mw, *mb;  // log_assignment[layer].matchability
+  const float *tw, *tb;  // token_confidence[layer].token[0], or null: no early stopping, no token term
+  float thr_w, thr_t;
+};
+
+// ind = identity, prune = 1 for every original point (0 in the padding), live = prev = the clamped counts
+__global__ void lg_prune_init_kernel(const PruneArgs a) {
+  const int e = blockIdx.y;
+  const bool side = e >= a.B;
+  const int p = side ? e - a.B : e;
+  const int cap = side ? a.cap1 : a.cap0;
+  const int cnt = max(0, min(side ? a.m[p] : a.n[p], cap));
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0) {
+    a.live[e] = cnt;
+    a.prev[e] = cnt;
+  }
+  if (t >= cap) return;
+  (side ? a.kept1 : a.kept0)[(size_t)p * cap + t] = t < cnt ? t : -1;
+  (side ? a.prune1 : a.prune0)[(size_t)p * cap + t] = t < cnt ? 1.0f : 0.0f;
+}
+
+// keep = sigmoid(matchability(x)) > thr_w, or (early stopping on) sigmoid(token(x)) <= thr_t: the dot products in the order of
+// lg_matchability_kernel, one wave per row; grid and entries as lg_stop_kernel.  Pairs that have stopped, and sides that do not
+// pass the gate (rows > min_kpts), are left alone.
+__global__ __launch_bounds__(256) void lg_keep_kernel(const PruneArgs a) {
+  const int e = blockIdx.y;
+  const bool side = e >= a.B;
+  const int p = side ? e - a.B : e;
+  const int n = min(a.act[p], a.cap0), m = min(a.act[a.B + p], a.cap1);
+  if (n <= 0 || m <= 0) return;
+  const int rows = side ? m : n, cap = side ? a.cap1 : a.cap0;
+  if (rows <= a.min_kpts) return;
+  const int r0 = (int)blockIdx.x * STOP_ROWS;
+  if (r0 >= rows) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* x = (side ? a.x1 : a.x0) + (size_t)p * cap * a.d;
+  int32_t* dst = (side ? a.dst1 : a.dst0) + (size_t)p * cap;
+  for (int k = 0; k < STOP_ROWS / 4; ++k) {
+    const int i = r0 + wave * (STOP_ROWS / 4) + k;
+    if (i >= rows) break;
+    const float* row = x + (size_t)i * a.d;
+    float s = 0.0f;
+    for (int c = lane; c < a.d; c += 64) s = fmaf(row[c], a.mw[c], s);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    bool keep = einx_sigmoidf(s + a.mb[0]) > a.thr_w;
+    if (a.tw) {  // low-confidence points are never pruned (lightglue.py:728-729)
+      float t = 0.0f;
+      for (int c = lane; c < a.d; c += 64) t = fmaf(row[c], a.tw[c], t);
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
+      keep = keep || einx_sigmoidf(t + a.tb[0]) <= a.thr_t;
+    }
+    if (lane == 0) dst[i] = keep ? 1 : 0;
+  }
+}
+
+// One workgroup per pair, its two sides one after the other: an exclusive scan of the flags in chunks of 256 rows gives every kept
+// row its new position (stable).  ind is compacted in place -- a chunk is read by every thread before any of it is written, and
+// a row only moves forward, into places the earlier chunks have left -- and prune[ind] grows by one for the rows that stay.  Then
+// the counts: live = act = the rows kept; a side with no rows left finishes the pair (both active counts zero, stop = layer + 1
+// when early stopping is on).  prev keeps what live was, so that the two launches behind this one know which sides moved.
+__global__ __launch_bounds__(256) void lg_prune_scan_kernel(const PruneArgs a) {
+  __shared__ int wsum[4];
+  const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = min(a.act[p], a.cap0), m = min(a.act[a.B + p], a.cap1);
+  if (tid == 0) {
+    a.prev[p] = a.live[p];
+    a.prev[a.B + p] = a.live[a.B + p];
+  }
+  if (n <= 0 || m <= 0) return;  // stopped, finished or empty (uniform over the workgroup)
+  int newc[2] = {n, m};
+  for (int side = 0; side < 2; ++side) {
+    const int rows = side ? m : n, cap = side ? a.cap1 : a.cap0;
+    if (rows <= a.min_kpts) continue;  // the gate: untouched at this layer, prune not incremented
+    int32_t* dst = (side ? a.dst1 : a.dst0) + (size_t)p * cap;
+    int64_t* kept = (side ? a.kept1 : a.kept0) + (size_t)p * cap;
+    float* prune = (side ? a.prune1 : a.prune0) + (size_t)p * cap;
+    int run = 0;
+    for (int base = 0; base < rows; base += 256) {
+      const int i = base + tid;
+      const int flag = i < rows ? dst[i] : 0;
+      const int64_t src = i < rows ? kept[i] : -1;
+      const unsigned long long bal = __ballot(flag != 0);
+      const int within = __popcll(bal & ((1ull << lane) - 1ull));
+      if (lane == 0) wsum[wave] = __popcll(bal);
+      __syncthreads();
+      int off = run, total = 0;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        if (w < wave) off += wsum[w];
+        total += wsum[w];
+      }
+      __syncthreads();
+      if (i < rows) {
+        dst[i] = flag ? off + within : -1;
+        if (flag) {
+          kept[off + within] = src;
+          prune[src] += 1.0f;
+        }
+      }
+      run += total;
+    }
+    __syncthreads();
+    for (int i = run + tid; i < rows; i += 256) kept[i] = -1;
+    newc[side] = run;
+  }
+  if (tid != 0) return;
+  a.live[p] = newc[0];
+  a.live[a.B + p] = newc[1];
+  const bool finished = newc[0] == 0 || newc[1] == 0;
+  a.act[p] = finished ? 0 : newc[0];
+  a.act[a.B + p] = finished ? 0 : newc[1];
+  if (finished && a.set_stop) a.stop[p] = a.layer + 1;
+}
+
+// the rows that stay, of the sides that lost rows at this layer: x -> tx, enc -> te at the new position; one wave per row
+__global__ __launch_bounds__(256) void lg_prune_gather_kernel(const PruneArgs a) {
+  const int e = blockIdx.y;
+  const int old = a.prev[e];
+  if (a.live[e] == old) return;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= old) return;
+  const bool side = e >= a.B;
+  const int p = side ? e - a.B : e;
+  const int cap = side ? a.cap1 : a.cap0;
+  const int j = (side ? a.dst1 : a.dst0)[(size_t)p * cap + i];
+  if (j < 0) return;
+  const int lane = threadIdx.x & 63;
+  const size_t xb = (size_t)p * cap * a.d, eb = (size_t)p * cap * a.dh2;
+  const float* xs = (side ? a.x1 : a.x0) + xb + (size_t)i * a.d;
+  float* xd = (side ? a.tx1 : a.tx0) + xb + (size_t)j * a.d;
+  for (int c = lane * 4; c < a.d; c += 256) *reinterpret_cast<f32x4*>(xd + c) = *reinterpret_cast<const f32x4*>(xs + c);
+  const float* es = (side ? a.enc1 : a.enc0) + eb + (size_t)i * a.dh2;
+  float* ed = (side ? a.te1 : a.te0) + (size_t)p * cap * 2 * a.d + (size_t)j * a.dh2;
+  for (int c = lane * 4; c < a.dh2; c += 256) *reinterpret_cast<f32x4*>(ed + c) = *reinterpret_cast<const f32x4*>(es + c);
+}
+
+// ... and back: the first live rows of x and enc (16 bytes per thread; the x part, then the enc part of an entry)
+__global__ __launch_bounds__(256) void lg_prune_copyback_kernel(const PruneArgs a) {
+  const int e = blockIdx.y;
+  const int nw = a.live[e];
+  if (nw == a.prev[e]) return;
+  const bool side = e >= a.B;
+  const int p = side ? e - a.B : e;
+  const int cap = side ? a.cap1 : a.cap0;
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t xq = (size_t)cap * (a.d / 4), eq = (size_t)cap * (a.dh2 / 4);
+  if (t < xq) {
+    if (t >= (size_t)nw * (a.d / 4)) return;
+    const size_t o = (size_t)p * cap * a.d + t * 4;
+    *reinterpret_cast<f32x4*>((side ? a.x1 : a.x0) + o) = *reinterpret_cast<const f32x4*>((side ? a.tx1 : a.tx0) + o);
+  } else if (t - xq < eq) {
+    const size_t u = t - xq;
+    if (u >= (size_t)nw * (a.dh2 / 4)) return;
+    *reinterpret_cast<f32x4*>((side ? a.enc1 : a.enc0) + (size_t)p * cap * a.dh2 + u * 4) =
+        *reinterpret_cast<const f32x4*>((side ? a.te1 : a.te0) + (size_t)p * cap * 2 * a.d + u * 4);
   }
 }
 
@@ -1002,6 +1184,49 @@ __global__ void lg_finalize_kernel(const unsigned long long* rowkey, const unsig
     }
     m1[(size_t)b * cap1 + t] = r;
     s1[(size_t)b * cap1 + t] = sc;
+  }
+}
+
+// The same after point pruning: the keys are those of the LIVE rows, and the results go back to original indexing
+// through ind (lightglue.py:659-667).  One workgroup per pair: every row gets -1 / 0 first, then the live rows scatter.
+__global__ __launch_bounds__(256) void lg_finalize_scatter_kernel(const unsigned long long* rowkey, const unsigned long long* colkey, const int32_t* live,
+                                                                  int B, const int64_t* kept0, const int64_t* kept1, int cap0, int cap1, float th,
+                                                                  int64_t* m0, int64_t* m1, float* s0, float* s1) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = min(live[b], cap0), m = min(live[B + b], cap1);
+  m0 += (size_t)b * cap0;
+  s0 += (size_t)b * cap0;
+  m1 += (size_t)b * cap1;
+  s1 += (size_t)b * cap1;
+  for (int t = tid; t < cap0; t += 256) {
+    m0[t] = -1;
+    s0[t] = 0.0f;
+  }
+  for (int t = tid; t < cap1; t += 256) {
+    m1[t] = -1;
+    s1[t] = 0.0f;
+  }
+  __syncthreads();
+  if (n <= 0 || m <= 0) return;
+  const unsigned long long* rk = rowkey + (size_t)b * cap0;
+  const unsigned long long* ck = colkey + (size_t)b * cap1;
+  const int64_t* i0 = kept0 + (size_t)b * cap0;
+  const int64_t* i1 = kept1 + (size_t)b * cap1;
+  auto idx_of = [](unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); };
+  auto val_of = [](unsigned long long k) { return einx_ordered_unkey((unsigned)(k >> 32)); };
+  for (int t = tid; t < n; t += 256) {
+    const int j = idx_of(rk[t]);
+    const bool mutual = idx_of(ck[j]) == t;
+    const float sc = mutual ? einx_expf(val_of(rk[t])) : 0.0f;
+    m0[i0[t]] = (mutual && sc > th) ? i1[j] : -1;
+    s0[i0[t]] = sc;
+  }
+  for (int t = tid; t < m; t += 256) {
+    const int i = idx_of(ck[t]);
+    const bool mutual1 = idx_of(rk[i]) == t;
+    const float ms0 = mutual1 ? einx_expf(val_of(rk[i])) : 0.0f;
+    m1[i1[t]] = (mutual1 && ms0 > th) ? i0[i] : -1;
+    s1[i1[t]] = ms0;
   }
 }
 
@@ -1079,6 +1304,21 @@ void carve_es(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, EsWs&
   e.act = c.take<int32_t>((size_t)2 * B);
   e.below = c.take<int32_t>((size_t)B);
   e.done = c.take<int32_t>((size_t)B);
+  c.slack(256);
+}
+
+// what point pruning adds behind carve_es()'s regions (einx_lightglue_adaptive_ws_bytes walks the same function)
+struct AdWs {
+  int32_t *dst0, *dst1;  // [B,cap0], [B,cap1]
+  int32_t *prev, *stop;  // [2B]; [B], used when the caller passes no stop
+};
+void carve_ad(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, EsWs& e, AdWs& p, bool stacked, int B, int cap0, int cap1, int d, int dh,
+              int n_layers) {
+  carve_es(c, s0, s1, cnt2, a, e, stacked, B, cap0, cap1, d, dh, n_layers);
+  p.dst0 = c.take<int32_t>((size_t)B * cap0);
+  p.dst1 = c.take<int32_t>((size_t)B * cap1);
+  p.prev = c.take<int32_t>((size_t)2 * B);
+  p.stop = c.take<int32_t>((size_t)B);
   c.slack(256);
 }
 
@@ -1318,10 +1558,18 @@ EINX_EXPORT size_t einx_lg_ws_bytes(int B, int cap0, int cap1, int d, int input_
 
 namespace {
 // what einx_lightglue_early_stop hands to the shared body (null: einx_lightglue)
+struct Adaptive {  // point pruning
+  float thr_w;  // float32(1.0 - double(width_confidence))
+  int min_kpts;
+  float *prune0, *prune1;
+  int64_t *kept0, *kept1;
+  int32_t* live;
+};
 struct EarlyStop {
   const einx_lg_head* heads;
-  float depth_confidence;
-  int32_t* stop;
+  float depth_confidence;  // with `ad`: <= 0 means no stop decision
+  int32_t* stop;           // with `ad`: may be null (carved in the workspace; route (a) reads it either way)
+  const Adaptive* ad;      // null: einx_lightglue_early_stop
 };
 
 int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
@@ -1355,12 +1603,20 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
   int32_t* cnt2;
   MnnArgs a;
   EsWs ew{};
+  AdWs aw{};
+  const Adaptive* ad = es ? es->ad : nullptr;
   WsCarver c{(char*)ws};
-  if (es) carve_es(c, s0, s1, cnt2, a, ew, stacked, B, cap0, cap1, D, dm.dh, w->n_layers);
+  if (ad) carve_ad(c, s0, s1, cnt2, a, ew, aw, stacked, B, cap0, cap1, D, dm.dh, w->n_layers);
+  else if (es) carve_es(c, s0, s1, cnt2, a, ew, stacked, B, cap0, cap1, D, dm.dh, w->n_layers);
   else carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, D, dm.dh);
   // r0 / r1: the sides as the LAYERS see them.  Early stopping: on the private active counts (ew.act = n | m, zeroed per pair as
   // it stops); the input stage, ref_descriptors and the assignment keep the caller's counts.  sa: the stacked view of those.
+  // Point pruning: the layers still run on ew.act, which shrinks with the rows kept; ref_descriptors and the assignment run on
+  // the LIVE counts (what survived, also of a pair that has stopped), and the input stage alone keeps the caller's counts.
   Side sb{}, sa{}, r0 = s0, r1 = s1;
+  int32_t* const stop = es ? (es->stop ? es->stop : aw.stop) : nullptr;
+  const bool decide = es && (!ad || es->depth_confidence > 0.0f);
+  PruneArgs pa{};
   if (es) {
     HeadTable t;
     for (int i = 0; i < w->n_layers; ++i) {
@@ -1371,9 +1627,24 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
     }
     const int items = 4 * w->n_layers > 2 * B ? 4 * w->n_layers : 2 * B;
     hipLaunchKernelGGL(lg_es_init_kernel, dim3((unsigned)einx_cdiv(items, 256)), dim3(256), 0, st, t, (int)w->n_layers, ew.heads, n, m, B, cap0, cap1,
-                       cnt2, ew.act, es->stop, ew.below, ew.done);
+                       cnt2, ew.act, stop, ew.below, ew.done);
     r0.cnt = ew.act;
     r1.cnt = ew.act + B;
+    if (ad) {
+      pa.x0 = s0.x, pa.x1 = s1.x, pa.enc0 = s0.enc, pa.enc1 = s1.enc;
+      pa.tx0 = s0.ctx, pa.tx1 = s1.ctx, pa.te0 = s0.h, pa.te1 = s1.h;
+      pa.act = ew.act, pa.live = ad->live, pa.prev = aw.prev;
+      pa.dst0 = aw.dst0, pa.dst1 = aw.dst1;
+      pa.kept0 = ad->kept0, pa.kept1 = ad->kept1, pa.prune0 = ad->prune0, pa.prune1 = ad->prune1;
+      pa.stop = stop;
+      pa.n = n, pa.m = m;
+      pa.cap0 = cap0, pa.cap1 = cap1, pa.d = D, pa.dh2 = 2 * dm.dh, pa.B = B;
+      pa.min_kpts = ad->min_kpts;
+      pa.set_stop = decide ? 1 : 0;
+      pa.thr_w = ad->thr_w;
+      const int mxc = cap0 > cap1 ? cap0 : cap1;
+      hipLaunchKernelGGL(lg_prune_init_kernel, dim3((unsigned)einx_cdiv(mxc, 256), (unsigned)(2 * B)), dim3(256), 0, st, pa);
+    }
   } else if (stacked) {
     hipLaunchKernelGGL(lg_stack_counts_kernel, dim3((unsigned)einx_cdiv(2 * B, 256)), dim3(256), 0, st, n, m, B, cnt2);
   }
@@ -1385,7 +1656,14 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
   }
   Side* sides[2] = {&s0, &s1};
   Side* run[2] = {stacked ? &sb : &r0, &r1};  // what the shared-weight stages iterate over
-  Side* asg[2] = {stacked ? &sa : &s0, &s1};  // the assignment's projections: every pair's own rows
+  Side l0 = s0, l1 = s1;  // the sides at their live counts (point pruning)
+  if (ad) {
+    sa.cnt = ad->live;
+    l0.cnt = ad->live;
+    l1.cnt = ad->live + B;
+  }
+  Side* asg[2] = {stacked ? &sa : ad ? &l0 : &s0, ad ? &l1 : &s1};  // the assignment's projections: every pair's own rows
+  Side* outs[2] = {ad ? &l0 : &s0, ad ? &l1 : &s1};                // ... and ref_descriptors
   const int nrun = stacked ? 1 : 2, Br = stacked ? 2 * B : B;
   const float sz[2][2] = {{h0, w0}, {h1, w1}};
 #define LG_CHECK(expr)                                                    \
@@ -1466,7 +1744,7 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
         LG_CHECK(0);
       }
     }
-    if (es && li < w->n_layers - 1) {  // the pairs still running decide whether this was their last layer
+    if (decide && li < w->n_layers - 1) {  // the pairs still running decide whether this was their last layer
       StopArgs sa_;
       sa_.x0 = s0.x;
       sa_.x1 = s1.x;
@@ -1484,10 +1762,32 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
       sa_.depth = es->depth_confidence;
       sa_.below = ew.below;
       sa_.done = ew.done;
-      sa_.stop = es->stop;
+      sa_.stop = stop;
+      sa_.tot0 = ad ? n : nullptr;
+      sa_.tot1 = ad ? m : nullptr;
       const int mxr = cap0 > cap1 ? cap0 : cap1;
       EINX_PROF("lg_stop_kernel", st);
       hipLaunchKernelGGL(lg_stop_kernel, dim3((unsigned)einx_cdiv(mxr, STOP_ROWS), (unsigned)(2 * B)), dim3(256), 0, st, sa_);
+      LG_CHECK(0);
+    }
+    if (ad && li < w->n_layers - 1) {  // after the stop decision (lightglue.py:632-652): a pair that has just stopped is not pruned
+      pa.layer = li;
+      pa.mw = es->heads[li].match_w;
+      pa.mb = es->heads[li].match_b;
+      pa.tw = decide ? es->heads[li].token_w : nullptr;
+      pa.tb = decide ? es->heads[li].token_b : nullptr;
+      const double thr = 0.8 + 0.1 * exp(-4.0 * li / w->n_layers);
+      pa.thr_t = (float)(thr < 0.0 ? 0.0 : thr > 1.0 ? 1.0 : thr);
+      const int mxr = cap0 > cap1 ? cap0 : cap1;
+      EINX_PROF("lg_prune (keep + scan + gather + copy back)", st);
+      hipLaunchKernelGGL(lg_keep_kernel, dim3((unsigned)einx_cdiv(mxr, STOP_ROWS), (unsigned)(2 * B)), dim3(256), 0, st, pa);
+      LG_CHECK(0);
+      hipLaunchKernelGGL(lg_prune_scan_kernel, dim3((unsigned)B), dim3(256), 0, st, pa);
+      LG_CHECK(0);
+      hipLaunchKernelGGL(lg_prune_gather_kernel, dim3((unsigned)einx_cdiv(mxr, 4), (unsigned)(2 * B)), dim3(256), 0, st, pa);
+      LG_CHECK(0);
+      const size_t quads = (size_t)mxr * ((D + 2 * dm.dh) / 4);
+      hipLaunchKernelGGL(lg_prune_copyback_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)(2 * B)), dim3(256), 0, st, pa);
       LG_CHECK(0);
     }
   }
@@ -1496,9 +1796,9 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
     Side& s = *asg[sd];
     if (es) {  // route (a): one stage over every pair's own rows, each pair with the head it stopped at (x frozen since then)
       LG_CHECK(gemm(st, EPI_DIV_HEAD, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, nullptr, nullptr, D, s.q, D, sqrtf(sqrtf((float)D)), ew.heads,
-                    es->stop, B, w->n_layers));
+                    stop, B, w->n_layers));
       hipLaunchKernelGGL(lg_matchability_heads_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)Br), dim3(256), 0, st, s.x, s.cnt, s.cap, D,
-                         ew.heads, es->stop, B, (int)w->n_layers, s.cert, s.dust);
+                         ew.heads, stop, B, (int)w->n_layers, s.cert, s.dust);
       LG_CHECK(0);
       continue;
     }
@@ -1508,7 +1808,7 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
     LG_CHECK(0);
   }
   for (int sd = 0; sd < 2; ++sd) {
-    Side& s = *sides[sd];
+    Side& s = *outs[sd];
     float* ref = sd == 0 ? ref0 : ref1;
     if (ref && !all_layers) {
       const size_t per = (size_t)s.cap * D;
@@ -1519,8 +1819,8 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
   }
   a.d0 = s0.q;
   a.d1 = s1.q;
-  a.n = n;
-  a.m = m;
+  a.n = ad ? ad->live : n;
+  a.m = ad ? ad->live + B : m;
   a.cap0 = cap0;
   a.cap1 = cap1;
   a.D = D;
@@ -1543,8 +1843,12 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
   if (la) hipLaunchKernelGGL((mnn_tile_kernel<6, true>), grid, dim3(THREADS), 0, st, a);  // arg-max + log_assignment write in one visit
   else hipLaunchKernelGGL((mnn_tile_kernel<0, true>), grid, dim3(THREADS), 0, st, a);
   LG_CHECK(0);
-  hipLaunchKernelGGL(lg_finalize_kernel, dim3((unsigned)einx_cdiv(mx, 256), (unsigned)B), dim3(256), 0, st, a.rowkey, a.colkey, n, m, cap0, cap1,
-                     w->filter_threshold, matches0, matches1, scores0, scores1);
+  if (ad)
+    hipLaunchKernelGGL(lg_finalize_scatter_kernel, dim3((unsigned)B), dim3(256), 0, st, a.rowkey, a.colkey, ad->live, B, ad->kept0, ad->kept1, cap0,
+                       cap1, w->filter_threshold, matches0, matches1, scores0, scores1);
+  else
+    hipLaunchKernelGGL(lg_finalize_kernel, dim3((unsigned)einx_cdiv(mx, 256), (unsigned)B), dim3(256), 0, st, a.rowkey, a.colkey, n, m, cap0, cap1,
+                       w->filter_threshold, matches0, matches1, scores0, scores1);
   LG_CHECK(0);
 #undef LG_CHECK
   return EINX_OK;
@@ -1585,9 +1889,46 @@ EINX_EXPORT int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_l
     EINX_CHECK_ARG(h.proj_w && h.proj_b && h.match_w && h.match_b, "every layer needs its log_assignment head");
     EINX_CHECK_ARG(i == w->n_layers - 1 || (h.token_w && h.token_b), "every layer but the last needs its token_confidence head");
   }
-  const EarlyStop es{heads, depth_confidence, stop};
+  const EarlyStop es{heads, depth_confidence, stop, nullptr};
   return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
                 1, stream);
+}
+
+EINX_EXPORT size_t einx_lightglue_adaptive_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers) {
+  Dims dm;
+  if (B <= 0 || cap0 <= 0 || cap1 <= 0 || n_layers < 1 || n_layers > LG_MAX_HEADS || !dims_of(d, heads, dm)) return 0;
+  (void)input_dim;
+  Side s0, s1;
+  int32_t* cnt2;
+  MnnArgs a;
+  EsWs e;
+  AdWs p;
+  WsCarver c{nullptr};
+  carve_ad(c, s0, s1, cnt2, a, e, p, cap0 == cap1, B, cap0, cap1, d, dm.dh, n_layers);
+  return c.bytes;
+}
+
+EINX_EXPORT int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                                        double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                                        const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
+                                        float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
+                                        float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
+                                        int32_t* live, void* stream) {
+  EINX_CHECK_ARG(w && heads && prune0 && prune1 && kept0 && kept1 && live, "null pointer");
+  EINX_CHECK_ARG(head_size == sizeof(einx_lg_head), "head_size does not match this library's einx_lg_head (header / library ABI mismatch)");
+  EINX_CHECK_ARG(w->n_layers >= 1 && w->n_layers <= LG_MAX_HEADS, "point pruning takes 1..32 layers");
+  EINX_CHECK_ARG(width_confidence > 0.0 && width_confidence <= 1.0, "width_confidence must be in (0, 1]");
+  EINX_CHECK_ARG(la == nullptr, "log_assignment is not produced with point pruning (DESIGN.md 8j): la must be null");
+  for (int i = 0; i < w->n_layers; ++i) {
+    const einx_lg_head& h = heads[i];
+    EINX_CHECK_ARG(h.proj_w && h.proj_b && h.match_w && h.match_b, "every layer needs its log_assignment head");
+    EINX_CHECK_ARG(depth_confidence <= 0.0f || i == w->n_layers - 1 || (h.token_w && h.token_b),
+                   "with depth_confidence > 0 every layer but the last needs its token_confidence head");
+  }
+  const Adaptive ad{(float)(1.0 - width_confidence), min_kpts, prune0, prune1, kept0, kept1, live};
+  const EarlyStop es{heads, depth_confidence, stop, &ad};
+  return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, nullptr, ref0,
+                ref1, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -95,6 +95,15 @@ class _RunningMean:
         return (sums / (counts if empty_is_nan else counts.clamp_min(1))).tolist()
 
 
+def kept_ratio_rows(live, n, m, cap0, cap1):
+    """[B,1] float64 on the device: (live0 + live1) / (n + m) per pair from a MatchResult's `live` [2B] and the counts it was called
+    with; NaN, which the means skip, for a pair with n + m == 0"""
+    B = n.shape[0]
+    total = (n.clamp(0, cap0) + m.clamp(0, cap1)).double()
+    kept = (live[:B] + live[B:]).double()
+    return torch.where(total > 0, kept / total.clamp_min(1.0), torch.full_like(total, float("nan")))[:, None]
+
+
 class SameTimeEvaluator:
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), he_thresh=None, he_ransac_thresh=3.0,
                  he_conf=0.995, representation_type="VoxelGrid", losses=None):
@@ -128,6 +137,7 @@ class SameTimeEvaluator:
         self.names = metric_names(self.mma_thr, self.vdd_thr)
         self._metric_mean = _RunningMean(len(self.names))
         self._stop_mean = _RunningMean(1)  # layers run per pair, when the matcher stops pairs early (LightGlue.early_stop)
+        self._kept_mean = _RunningMean(1)  # (live0 + live1) / (n + m) per pair, when the matcher prunes points (LightGlue.point_pruning, 8j)
         self._stages = {}  # (slot, on its own stream, device) -> EventStage
         self.pairs = 0
 
@@ -205,6 +215,7 @@ class SameTimeEvaluator:
         self._metric_mean.add(rows)
         self.pairs += rows.shape[0]
         self._account_stop(self.model._last_match)
+        self._account_kept(self.model._last_match, ef._batched, imf._batched)
         if self.he_thresh is not None and batch.homography is not None:
             mr = self.model._last_match
             key = (tuple(ef._batched.image_size), mr.mk0.shape[0], mr.mk0.device)
@@ -219,6 +230,11 @@ class SameTimeEvaluator:
         stop = getattr(mr, "stop", None)
         if stop is not None:
             self._stop_mean.add(stop.double()[:, None])
+
+    def _account_kept(self, mr, bf0, bf1):
+        live = getattr(mr, "live", None)
+        if live is not None:
+            self._kept_mean.add(kept_ratio_rows(live, bf0.counts, bf1.counts, mr.kept0.shape[1], mr.kept1.shape[1]))
 
     @property
     def sums(self):
@@ -262,6 +278,9 @@ class SameTimeEvaluator:
         s, c = self._stop_mean.reduced(dev)
         if float(c.max()) > 0:  # some rank's matcher stopped pairs early: the mean number of layers a pair ran
             out["matcher_stop_layer"] = _RunningMean.means(s, c)[0]
+        s, c = self._kept_mean.reduced(dev)
+        if float(c.max()) > 0:  # some rank's matcher pruned points: the mean share of a pair's keypoints that survived
+            out["matcher_kept_ratio"] = _RunningMean.means(s, c)[0]
         return out
 
 
@@ -402,6 +421,9 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.early_stop_active():
             raise ValueError("einx: matcher_loss=True with early stopping on: the loss applies the LAST assignment head, the forward's "
                              "descriptors are those of each pair's stopping layer (LightGlue.loss refuses them too, DESIGN.md 8h)")
+        if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.point_pruning_active():
+            raise ValueError("einx: matcher_loss=True with point pruning on: the forward's descriptors hold only the surviving rows, "
+                             "the labels are those of every keypoint (LightGlue.loss refuses them too, DESIGN.md 8j)")
         if batch.depth is not None and batch.pose is None:
             raise ValueError("einx: depth=(depth0, depth1) needs pose=(K0, K1, T_0to1): ground-truth matches come from depth AND motion")
 

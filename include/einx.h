@@ -367,6 +367,28 @@ int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_lg_head* head
                               int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
                               float* ref1, int32_t* stop, void* stream);
 
+/* Point pruning: per-pair, per-side adaptive width, with or without early stopping.  The reference carries
+ * `width_confidence`, get_pruning_mask and pruning_min_kpts, but the branch that calls them is commented out (lightglue.py:608-617,
+ * 637-652, 658-670).  This entry point runs it; einx_lightglue and einx_lightglue_early_stop are unchanged.
+ * After layer i < n_layers - 1, for every pair still running (after that layer's stop decision when depth_confidence > 0), each
+ * side with more than min_kpts rows keeps the rows with sigmoid(match_w . x + match_b) > float(1.0 - width_confidence) -- or, with
+ * depth_confidence > 0 only, sigmoid(token_w . x + token_b) <= thr[i] -- compacted to the front in their order; prune[ind[kept]]
+ * grows by one.  The stop ratio's denominator stays the caller's n + m.  A side left without rows finishes its pair: no matches,
+ * and stop = i + 1 when depth_confidence > 0.  depth_confidence <= 0: no stop decision, the last head, token_* not read.
+ * Outputs in ORIGINAL indexing: matches0/1, scores0/1 (pruned points: -1 / 0), prune0 [B,cap0] / prune1 [B,cap1] float32 (1 +
+ * the steps survived; 0 in the padding).  kept0 [B,cap0] / kept1 [B,cap1] int64: the survivors' original indices in compacted
+ * order, -1 behind them; live [2B] int32: survivors of side 0 (entries 0..B-1) and side 1 (B..2B-1).  ref0 / ref1 [B,cap,d]: the
+ * survivors' rows in that order (rows past live are not written).  la must be NULL (no log_assignment).  stop: device int32 [B]
+ * or NULL.  width_confidence in (0, 1].  No host synchronisation, no allocation, no atomics: deterministic and capturable.
+ * ws: einx_lightglue_adaptive_ws_bytes(...) bytes (0 = unsupported widths, or more than 32 layers). */
+size_t einx_lightglue_adaptive_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers);
+int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                            double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                            const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
+                            float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
+                            float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
+                            int32_t* live, void* stream);
+
 /* Assignment NLL of ONE MatchAssignment head (lightglue.py:66-133 NLLLoss / weight_loss, :751-769 LightGlue.loss in eval mode): the
  * sums behind nll_pos / nll_neg / row_norm, without a log_assignment matrix or any other B x n x m buffer.
  * proj_w [d,d], proj_b [d]: the head's final_proj; match_w [d], match_b [1]: its matchability; d a multiple of 4.
