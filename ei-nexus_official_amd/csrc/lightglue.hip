@@ -838,43 +838,38 @@ __global__ __launch_bounds__(256) void lg_ln_gelu_any_kernel(float* hbuf, const 
   for (int c = lane; c < width; c += 64) row[c] = einx_geluf(fmaf((row[c] - mean) * rstd, g[c], be[c]));
 }
 
-// matchability logit z = x . w + b per token, plus logsigmoid(z) and logsigmoid(-z)
-__global__ __launch_bounds__(256) void lg_matchability_kernel(const float* x, const int32_t* cnt, int cap, int d, const float* w, const float* bm,
-                                                              float* cert, float* dust) {
-  const int b = blockIdx.y;
-  const int n = min(cnt[b], cap);
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const int lane = threadIdx.x & 63;
-  const float* row = x + ((size_t)b * cap + i) * d;
+// row . w by one wave: lane l adds the columns l, l + 64, ... in ascending order, then the xor butterfly; every lane gets the sum
+__device__ __forceinline__ float wave_row_dot(const float* row, const float* w, int d, int lane) {
   float s = 0.0f;
   for (int c = lane; c < d; c += 64) s = fmaf(row[c], w[c], s);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-  if (lane == 0) {
-    const float z = s + bm[0];
-    cert[(size_t)b * cap + i] = einx_logsigmoidf(z);
-    dust[(size_t)b * cap + i] = einx_logsigmoidf(-z);
-  }
+  return s;
 }
 
-// the same with every entry's weights taken from the head its pair stopped at (heads[4 h + 2 / 3], see GemmArgs)
-__global__ __launch_bounds__(256) void lg_matchability_heads_kernel(const float* x, const int32_t* cnt, int cap, int d, const float* const* heads,
-                                                                    const int32_t* stop, int pairs, int nheads, float* cert, float* dust) {
+// where a matchability head's weight and bias come from: the model's one head (w, b), or the head entry b's pair stopped at
+// (heads[4 h + 2 / 3], see GemmArgs)
+struct MatchHead {
+  const float *w, *b;
+};
+__device__ __forceinline__ MatchHead match_head(int, const float* w, const float* bm) { return {w, bm}; }
+__device__ __forceinline__ MatchHead match_head(int b, const float* const* heads, const int32_t* stop, int pairs, int nheads) {
+  const int h = head_of(stop, pairs, nheads, b);
+  return {heads[4 * h + 2], heads[4 * h + 3]};
+}
+
+// matchability logit z = x . w + b per token, plus logsigmoid(z) and logsigmoid(-z); Src...: the arguments of a match_head()
+template <typename... Src>
+__global__ __launch_bounds__(256) void lg_matchability_kernel(const float* x, const int32_t* cnt, int cap, int d, Src... src, float* cert, float* dust) {
   const int b = blockIdx.y;
   const int n = min(cnt[b], cap);
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
   const int lane = threadIdx.x & 63;
-  const int h = head_of(stop, pairs, nheads, b);
-  const float* w = heads[4 * h + 2];
-  const float* row = x + ((size_t)b * cap + i) * d;
-  float s = 0.0f;
-  for (int c = lane; c < d; c += 64) s = fmaf(row[c], w[c], s);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+  const MatchHead h = match_head(b, src...);
+  const float s = wave_row_dot(x + ((size_t)b * cap + i) * d, h.w, d, lane);
   if (lane == 0) {
-    const float z = s + heads[4 * h + 3][0];
+    const float z = s + h.b[0];
     cert[(size_t)b * cap + i] = einx_logsigmoidf(z);
     dust[(size_t)b * cap + i] = einx_logsigmoidf(-z);
   }
@@ -906,19 +901,36 @@ __global__ void lg_es_init_kernel(const HeadTable t, int nheads, const float** h
   }
 }
 
-struct StopArgs {
-  const float *x0, *x1;  // [B,cap0,d], [B,cap1,d] after the layer
-  int32_t *act0, *act1;  // the active counts, [B] each
-  int cap0, cap1, d, B, layer;
-  const float *w, *bias;  // token_confidence[layer].token[0]
-  float thr, depth;
-  int32_t *below, *done;  // [B], zero between launches
+// The launches behind a non-final layer (the stop decision, the pruning step) run over 2B entries: entry e < B is side 0 of pair
+// e, entry e >= B side 1 of pair e - B.
+struct Entry {
+  bool side;
+  int p, cap;
+};
+__device__ __forceinline__ Entry entry_of(int e, int B, int cap0, int cap1) {
+  const bool side = e >= B;
+  return {side, side ? e - B : e, side ? cap1 : cap0};
+}
+
+// ... and what their argument blocks share
+struct TailArgs {
+  float *x0, *x1;  // [B,cap0,d], [B,cap1,d] after the layer
+  int32_t* act;    // [2B]: the layers' active counts
   int32_t* stop;
+  int cap0, cap1, d, B, layer;
+  const float *tw, *tb;  // token_confidence[layer].token[0], or null: no stop decision
+  float thr;             // the layer's confidence threshold
+};
+
+struct StopArgs {
+  TailArgs t;
+  float depth;
+  int32_t *below, *done;       // [B], zero between launches
   const int32_t *tot0, *tot1;  // null, or the caller's counts: the ratio's denominator when rows have been pruned
 };
 
-// One launch per non-final layer: entry e < B is side 0 of pair e, entry e >= B side 1 of pair e - B; a workgroup takes STOP_ROWS
-// rows (a wave one row at a time: c = sigmoid(x . w + b), compared with the layer's threshold in float32).  The workgroups of a
+// One launch per non-final layer: a workgroup takes STOP_ROWS rows of an entry (a wave one row at a time: c = sigmoid(x . w + b),
+// compared with the layer's threshold in float32).  The workgroups of a
 // pair add their integer counts into below[pair] and take a ticket; the one that takes the last ticket has every count, applies
 // r = 1 - below / (n + m) > depth_confidence, writes stop and zeroes the pair's active counts, and leaves the counters at zero.
 // Integer sums only: the order in which the workgroups arrive does not matter.  Every workgroup with rows has read the counts
@@ -926,27 +938,23 @@ struct StopArgs {
 constexpr int STOP_ROWS = 32;
 __global__ __launch_bounds__(256) void lg_stop_kernel(const StopArgs a) {
   __shared__ int part[4];
-  const int e = blockIdx.y;
-  const bool side = e >= a.B;
-  const int p = side ? e - a.B : e;
-  const int n = min(a.act0[p], a.cap0), m = min(a.act1[p], a.cap1);
+  const TailArgs& t = a.t;
+  const Entry en = entry_of(blockIdx.y, t.B, t.cap0, t.cap1);
+  const int p = en.p;
+  const int n = min(t.act[p], t.cap0), m = min(t.act[t.B + p], t.cap1);
   if (n <= 0 || m <= 0) return;  // stopped earlier, or an empty pair (stop = 0)
-  const int rows = side ? m : n;
+  const int rows = en.side ? m : n;
   const int r0 = (int)blockIdx.x * STOP_ROWS;
   if (r0 >= rows) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* x = side ? a.x1 + (size_t)p * a.cap1 * a.d : a.x0 + (size_t)p * a.cap0 * a.d;
-  const float b0 = a.bias[0];
+  const float* x = (en.side ? t.x1 : t.x0) + (size_t)p * en.cap * t.d;
+  const float b0 = t.tb[0];
   int below = 0;
   for (int k = 0; k < STOP_ROWS / 4; ++k) {
     const int i = r0 + wave * (STOP_ROWS / 4) + k;
     if (i >= rows) break;
-    const float* row = x + (size_t)i * a.d;
-    float s = 0.0f;
-    for (int c = lane; c < a.d; c += 64) s = fmaf(row[c], a.w[c], s);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    below += einx_sigmoidf(s + b0) < a.thr ? 1 : 0;
+    const float s = wave_row_dot(x + (size_t)i * t.d, t.tw, t.d, lane);
+    below += einx_sigmoidf(s + b0) < t.thr ? 1 : 0;
   }
   if (lane == 0) part[wave] = below;
   __syncthreads();
@@ -958,12 +966,12 @@ __global__ __launch_bounds__(256) void lg_stop_kernel(const StopArgs a) {
   __threadfence();
   const int total = atomicExch(&a.below[p], 0);
   atomicExch(&a.done[p], 0);
-  const int den = a.tot0 ? min(a.tot0[p], a.cap0) + min(a.tot1[p], a.cap1) : n + m;  // the reference divides by the ORIGINAL m + n (:635)
+  const int den = a.tot0 ? min(a.tot0[p], t.cap0) + min(a.tot1[p], t.cap1) : n + m;  // the reference divides by the ORIGINAL m + n (:635)
   const float r = 1.0f - (float)total / (float)den;
   if (r > a.depth) {
-    a.stop[p] = a.layer + 1;
-    a.act0[p] = 0;
-    a.act1[p] = 0;
+    t.stop[p] = t.layer + 1;
+    t.act[p] = 0;
+    t.act[t.B + p] = 0;
   }
 }
 
@@ -975,70 +983,60 @@ __global__ __launch_bounds__(256) void lg_stop_kernel(const StopArgs a) {
 // layers) and lg_prune_copyback_kernel.  Launch boundaries are the only synchronisation; no float atomics, no atomics at all.
 // ------------------------------------------------------------------------------------------
 struct PruneArgs {
-  float *x0, *x1;      // [B,cap0,d], [B,cap1,d]
+  TailArgs t;          // tw / tb null: no early stopping, no token term
   float *enc0, *enc1;  // [B,cap,2 dh]
   float *tx0, *tx1;    // where the gather puts x: the sides' ctx
   float *te0, *te1;    // ... and the encoding: the sides' h, rows packed at 2 dh floats from each entry's base
-  int32_t *act, *live, *prev;  // [2B] each: the layers' counts, the surviving rows, the surviving rows before this layer's step
-  int32_t *dst0, *dst1;        // [B,cap0], [B,cap1]: the keep flag, then the row's new position or -1
-  int64_t *kept0, *kept1;      // ind: position -> original index; -1 past the live count
+  int32_t *live, *prev;    // [2B] each: the surviving rows, the surviving rows before this layer's step
+  int32_t *dst0, *dst1;    // [B,cap0], [B,cap1]: the keep flag, then the row's new position or -1
+  int64_t *kept0, *kept1;  // ind: position -> original index; -1 past the live count
   float *prune0, *prune1;
-  int32_t* stop;
-  const int32_t *n, *m;        // the caller's counts
-  int cap0, cap1, d, dh2, B, layer, min_kpts, set_stop;
+  const int32_t *n, *m;  // the caller's counts
+  int dh2, min_kpts, set_stop;
   const float *mw, *mb;  // log_assignment[layer].matchability
-  const float *tw, *tb;  // token_confidence[layer].token[0], or null: no early stopping, no token term
-  float thr_w, thr_t;
+  float thr_w;
 };
 
 // ind = identity, prune = 1 for every original point (0 in the padding), live = prev = the clamped counts
 __global__ void lg_prune_init_kernel(const PruneArgs a) {
   const int e = blockIdx.y;
-  const bool side = e >= a.B;
-  const int p = side ? e - a.B : e;
-  const int cap = side ? a.cap1 : a.cap0;
-  const int cnt = max(0, min(side ? a.m[p] : a.n[p], cap));
+  const Entry en = entry_of(e, a.t.B, a.t.cap0, a.t.cap1);
+  const int p = en.p, cap = en.cap;
+  const int cnt = max(0, min(en.side ? a.m[p] : a.n[p], cap));
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t == 0) {
     a.live[e] = cnt;
     a.prev[e] = cnt;
   }
   if (t >= cap) return;
-  (side ? a.kept1 : a.kept0)[(size_t)p * cap + t] = t < cnt ? t : -1;
-  (side ? a.prune1 : a.prune0)[(size_t)p * cap + t] = t < cnt ? 1.0f : 0.0f;
+  (en.side ? a.kept1 : a.kept0)[(size_t)p * cap + t] = t < cnt ? t : -1;
+  (en.side ? a.prune1 : a.prune0)[(size_t)p * cap + t] = t < cnt ? 1.0f : 0.0f;
 }
 
-// keep = sigmoid(matchability(x)) > thr_w, or (early stopping on) sigmoid(token(x)) <= thr_t: the dot products in the order of
+// keep = sigmoid(matchability(x)) > thr_w, or (early stopping on) sigmoid(token(x)) <= thr: the dot products in the order of
 // lg_matchability_kernel, one wave per row; grid and entries as lg_stop_kernel.  Pairs that have stopped, and sides that do not
 // pass the gate (rows > min_kpts), are left alone.
 __global__ __launch_bounds__(256) void lg_keep_kernel(const PruneArgs a) {
-  const int e = blockIdx.y;
-  const bool side = e >= a.B;
-  const int p = side ? e - a.B : e;
-  const int n = min(a.act[p], a.cap0), m = min(a.act[a.B + p], a.cap1);
+  const TailArgs& t = a.t;
+  const Entry en = entry_of(blockIdx.y, t.B, t.cap0, t.cap1);
+  const int p = en.p, cap = en.cap;
+  const int n = min(t.act[p], t.cap0), m = min(t.act[t.B + p], t.cap1);
   if (n <= 0 || m <= 0) return;
-  const int rows = side ? m : n, cap = side ? a.cap1 : a.cap0;
+  const int rows = en.side ? m : n;
   if (rows <= a.min_kpts) return;
   const int r0 = (int)blockIdx.x * STOP_ROWS;
   if (r0 >= rows) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const float* x = (side ? a.x1 : a.x0) + (size_t)p * cap * a.d;
-  int32_t* dst = (side ? a.dst1 : a.dst0) + (size_t)p * cap;
+  const float* x = (en.side ? t.x1 : t.x0) + (size_t)p * cap * t.d;
+  int32_t* dst = (en.side ? a.dst1 : a.dst0) + (size_t)p * cap;
   for (int k = 0; k < STOP_ROWS / 4; ++k) {
     const int i = r0 + wave * (STOP_ROWS / 4) + k;
     if (i >= rows) break;
-    const float* row = x + (size_t)i * a.d;
-    float s = 0.0f;
-    for (int c = lane; c < a.d; c += 64) s = fmaf(row[c], a.mw[c], s);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    bool keep = einx_sigmoidf(s + a.mb[0]) > a.thr_w;
-    if (a.tw) {  // low-confidence points are never pruned (lightglue.py:728-729)
-      float t = 0.0f;
-      for (int c = lane; c < a.d; c += 64) t = fmaf(row[c], a.tw[c], t);
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
-      keep = keep || einx_sigmoidf(t + a.tb[0]) <= a.thr_t;
+    const float* row = x + (size_t)i * t.d;
+    bool keep = einx_sigmoidf(wave_row_dot(row, a.mw, t.d, lane) + a.mb[0]) > a.thr_w;
+    if (t.tw) {  // low-confidence points are never pruned (lightglue.py:728-729)
+      const float c = wave_row_dot(row, t.tw, t.d, lane);
+      keep = keep || einx_sigmoidf(c + t.tb[0]) <= t.thr;
     }
     if (lane == 0) dst[i] = keep ? 1 : 0;
   }
@@ -1052,15 +1050,15 @@ __global__ __launch_bounds__(256) void lg_keep_kernel(const PruneArgs a) {
 __global__ __launch_bounds__(256) void lg_prune_scan_kernel(const PruneArgs a) {
   __shared__ int wsum[4];
   const int p = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int n = min(a.act[p], a.cap0), m = min(a.act[a.B + p], a.cap1);
+  const int n = min(a.t.act[p], a.t.cap0), m = min(a.t.act[a.t.B + p], a.t.cap1);
   if (tid == 0) {
     a.prev[p] = a.live[p];
-    a.prev[a.B + p] = a.live[a.B + p];
+    a.prev[a.t.B + p] = a.live[a.t.B + p];
   }
   if (n <= 0 || m <= 0) return;  // stopped, finished or empty (uniform over the workgroup)
   int newc[2] = {n, m};
   for (int side = 0; side < 2; ++side) {
-    const int rows = side ? m : n, cap = side ? a.cap1 : a.cap0;
+    const int rows = side ? m : n, cap = side ? a.t.cap1 : a.t.cap0;
     if (rows <= a.min_kpts) continue;  // the gate: untouched at this layer, prune not incremented
     int32_t* dst = (side ? a.dst1 : a.dst0) + (size_t)p * cap;
     int64_t* kept = (side ? a.kept1 : a.kept0) + (size_t)p * cap;
@@ -1096,11 +1094,11 @@ __global__ __launch_bounds__(256) void lg_prune_scan_kernel(const PruneArgs a) {
   }
   if (tid != 0) return;
   a.live[p] = newc[0];
-  a.live[a.B + p] = newc[1];
+  a.live[a.t.B + p] = newc[1];
   const bool finished = newc[0] == 0 || newc[1] == 0;
-  a.act[p] = finished ? 0 : newc[0];
-  a.act[a.B + p] = finished ? 0 : newc[1];
-  if (finished && a.set_stop) a.stop[p] = a.layer + 1;
+  a.t.act[p] = finished ? 0 : newc[0];
+  a.t.act[a.t.B + p] = finished ? 0 : newc[1];
+  if (finished && a.set_stop) a.t.stop[p] = a.t.layer + 1;
 }
 
 // the rows that stay, of the sides that lost rows at this layer: x -> tx, enc -> te at the new position; one wave per row
@@ -1110,18 +1108,18 @@ __global__ __launch_bounds__(256) void lg_prune_gather_kernel(const PruneArgs a)
   if (a.live[e] == old) return;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= old) return;
-  const bool side = e >= a.B;
-  const int p = side ? e - a.B : e;
-  const int cap = side ? a.cap1 : a.cap0;
+  const Entry en = entry_of(e, a.t.B, a.t.cap0, a.t.cap1);
+  const bool side = en.side;
+  const int p = en.p, cap = en.cap;
   const int j = (side ? a.dst1 : a.dst0)[(size_t)p * cap + i];
   if (j < 0) return;
   const int lane = threadIdx.x & 63;
-  const size_t xb = (size_t)p * cap * a.d, eb = (size_t)p * cap * a.dh2;
-  const float* xs = (side ? a.x1 : a.x0) + xb + (size_t)i * a.d;
-  float* xd = (side ? a.tx1 : a.tx0) + xb + (size_t)j * a.d;
-  for (int c = lane * 4; c < a.d; c += 256) *reinterpret_cast<f32x4*>(xd + c) = *reinterpret_cast<const f32x4*>(xs + c);
+  const size_t xb = (size_t)p * cap * a.t.d, eb = (size_t)p * cap * a.dh2;
+  const float* xs = (side ? a.t.x1 : a.t.x0) + xb + (size_t)i * a.t.d;
+  float* xd = (side ? a.tx1 : a.tx0) + xb + (size_t)j * a.t.d;
+  for (int c = lane * 4; c < a.t.d; c += 256) *reinterpret_cast<f32x4*>(xd + c) = *reinterpret_cast<const f32x4*>(xs + c);
   const float* es = (side ? a.enc1 : a.enc0) + eb + (size_t)i * a.dh2;
-  float* ed = (side ? a.te1 : a.te0) + (size_t)p * cap * 2 * a.d + (size_t)j * a.dh2;
+  float* ed = (side ? a.te1 : a.te0) + (size_t)p * cap * 2 * a.t.d + (size_t)j * a.dh2;
   for (int c = lane * 4; c < a.dh2; c += 256) *reinterpret_cast<f32x4*>(ed + c) = *reinterpret_cast<const f32x4*>(es + c);
 }
 
@@ -1130,22 +1128,26 @@ __global__ __launch_bounds__(256) void lg_prune_copyback_kernel(const PruneArgs 
   const int e = blockIdx.y;
   const int nw = a.live[e];
   if (nw == a.prev[e]) return;
-  const bool side = e >= a.B;
-  const int p = side ? e - a.B : e;
-  const int cap = side ? a.cap1 : a.cap0;
+  const Entry en = entry_of(e, a.t.B, a.t.cap0, a.t.cap1);
+  const bool side = en.side;
+  const int p = en.p, cap = en.cap;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t xq = (size_t)cap * (a.d / 4), eq = (size_t)cap * (a.dh2 / 4);
+  const size_t xq = (size_t)cap * (a.t.d / 4), eq = (size_t)cap * (a.dh2 / 4);
   if (t < xq) {
-    if (t >= (size_t)nw * (a.d / 4)) return;
-    const size_t o = (size_t)p * cap * a.d + t * 4;
-    *reinterpret_cast<f32x4*>((side ? a.x1 : a.x0) + o) = *reinterpret_cast<const f32x4*>((side ? a.tx1 : a.tx0) + o);
+    if (t >= (size_t)nw * (a.t.d / 4)) return;
+    const size_t o = (size_t)p * cap * a.t.d + t * 4;
+    *reinterpret_cast<f32x4*>((side ? a.t.x1 : a.t.x0) + o) = *reinterpret_cast<const f32x4*>((side ? a.tx1 : a.tx0) + o);
   } else if (t - xq < eq) {
     const size_t u = t - xq;
     if (u >= (size_t)nw * (a.dh2 / 4)) return;
     *reinterpret_cast<f32x4*>((side ? a.enc1 : a.enc0) + (size_t)p * cap * a.dh2 + u * 4) =
-        *reinterpret_cast<const f32x4*>((side ? a.te1 : a.te0) + (size_t)p * cap * 2 * a.d + u * 4);
+        *reinterpret_cast<const f32x4*>((side ? a.te1 : a.te0) + (size_t)p * cap * 2 * a.t.d + u * 4);
   }
 }
+
+// a packed arg-max key (pack_key, match_tiles.h) back into its index and its value
+__device__ __forceinline__ int key_index(unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); }
+__device__ __forceinline__ float key_value(unsigned long long k) { return einx_ordered_unkey((unsigned)(k >> 32)); }
 
 // filter_matches (lightglue.py:402-418) from the packed arg-max keys of the assignment scores
 __global__ void lg_finalize_kernel(const unsigned long long* rowkey, const unsigned long long* colkey, const int32_t* nn, const int32_t* mm,
@@ -1155,15 +1157,13 @@ __global__ void lg_finalize_kernel(const unsigned long long* rowkey, const unsig
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long* rk = rowkey + (size_t)b * cap0;
   const unsigned long long* ck = colkey + (size_t)b * cap1;
-  auto idx_of = [](unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); };
-  auto val_of = [](unsigned long long k) { return einx_ordered_unkey((unsigned)(k >> 32)); };
   if (t < cap0) {
     int64_t r = -1;
     float sc = 0.0f;
     if (t < n && m > 0) {
-      const int j = idx_of(rk[t]);
-      const bool mutual = idx_of(ck[j]) == t;
-      sc = mutual ? einx_expf(val_of(rk[t])) : 0.0f;
+      const int j = key_index(rk[t]);
+      const bool mutual = key_index(ck[j]) == t;
+      sc = mutual ? einx_expf(key_value(rk[t])) : 0.0f;
       if (mutual && sc > th) r = j;
     }
     m0[(size_t)b * cap0 + t] = r;
@@ -1173,12 +1173,12 @@ __global__ void lg_finalize_kernel(const unsigned long long* rowkey, const unsig
     int64_t r = -1;
     float sc = 0.0f;
     if (t < m && n > 0) {
-      const int i = idx_of(ck[t]);
-      const int back = idx_of(rk[i]);
+      const int i = key_index(ck[t]);
+      const int back = key_index(rk[i]);
       const bool mutual1 = back == t;
       // mscores1 = mscores0[m1] where mutual1; mscores0[i] is non-zero only if i is mutual too,
       // which is the same condition (back == t  <=>  i's best is t and t's best is i)
-      const float ms0 = mutual1 ? einx_expf(val_of(rk[i])) : 0.0f;
+      const float ms0 = mutual1 ? einx_expf(key_value(rk[i])) : 0.0f;
       sc = ms0;
       if (mutual1 && ms0 > th) r = i;
     }
@@ -1212,19 +1212,17 @@ __global__ __launch_bounds__(256) void lg_finalize_scatter_kernel(const unsigned
   const unsigned long long* ck = colkey + (size_t)b * cap1;
   const int64_t* i0 = kept0 + (size_t)b * cap0;
   const int64_t* i1 = kept1 + (size_t)b * cap1;
-  auto idx_of = [](unsigned long long k) { return (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)); };
-  auto val_of = [](unsigned long long k) { return einx_ordered_unkey((unsigned)(k >> 32)); };
   for (int t = tid; t < n; t += 256) {
-    const int j = idx_of(rk[t]);
-    const bool mutual = idx_of(ck[j]) == t;
-    const float sc = mutual ? einx_expf(val_of(rk[t])) : 0.0f;
+    const int j = key_index(rk[t]);
+    const bool mutual = key_index(ck[j]) == t;
+    const float sc = mutual ? einx_expf(key_value(rk[t])) : 0.0f;
     m0[i0[t]] = (mutual && sc > th) ? i1[j] : -1;
     s0[i0[t]] = sc;
   }
   for (int t = tid; t < m; t += 256) {
-    const int i = idx_of(ck[t]);
-    const bool mutual1 = idx_of(rk[i]) == t;
-    const float ms0 = mutual1 ? einx_expf(val_of(rk[i])) : 0.0f;
+    const int i = key_index(ck[t]);
+    const bool mutual1 = key_index(rk[i]) == t;
+    const float ms0 = mutual1 ? einx_expf(key_value(rk[i])) : 0.0f;
     m1[i1[t]] = (mutual1 && ms0 > th) ? i0[i] : -1;
     s1[i1[t]] = ms0;
   }
@@ -1257,69 +1255,77 @@ struct Side {
   float *x, *enc, *q, *k, *v, *ctx, *msg, *h, *cert, *dust;
 };
 
-// einx_lightglue's workspace (einx_lg_ws_bytes_heads walks it from a null base); d: descriptor_dim, dh: head dim.  Per side the
-// buffers [tokens, d] (x, q, k, v, ctx, msg), [tokens, 2 dh] (enc), [tokens, 2 d] (h), [tokens] (cert, dust); then the stacked
-// counts, the assignment stage's MNN workspace (match_tiles.h) and 1024 bytes of slack.  Stacked (equal capacities): every buffer
-// is ONE array [2B, cap, width], side 0 = entries 0..B-1, side 1 = entries B..2B-1.  LightGlue applies the same weights to both
-// sides, so every per-side launch becomes one launch over 2B entries (cross attention reaches the partner entry B entries on);
-// s0 / s1 stay views of the halves.  The array lies in the two regions that its halves would take apart, side 1 directly behind
-// side 0's last element: rounding each half up never gives less than the whole needs, so the size does not depend on `stacked`.
-void carve(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, bool stacked, int B, int cap0, int cap1, int d, int dh) {
+// The three entries share one driver (lg_run): einx_lightglue, einx_lightglue_early_stop and
+// einx_lightglue_adaptive (8j: point pruning, with or without the stop decision).  Each mode's workspace is the one before it
+// plus a block of its own.
+enum LgMode { LG_PLAIN = 0, LG_EARLY_STOP = 1, LG_ADAPTIVE = 2 };
+
+struct LgShape {
+  int B, cap0, cap1, d, dh, n_layers;  // d: descriptor_dim, dh: head dim
+  // equal capacities (every shipped configuration): the two sides are stacked and every layer runs ONCE over 2B entries --
+  // half the launches, and at small batch twice the workgroups per launch (a single pair: 8.0 -> see profiles/r03_notes.md)
+  bool stacked() const { return cap0 == cap1; }
+};
+
+struct LgWs {
+  Side s[2];
+  int32_t* cnt2;  // the caller's counts of both sides as [2B] (written when stacked, or by the early-stop init)
+  MnnArgs mnn;
+  // early stopping
+  const float** heads;          // [4 n_layers] device table
+  int32_t *act, *below, *done;  // private active counts [2B]; the decision's counters [B] each
+  // point pruning
+  int32_t *dst0, *dst1;  // [B,cap0], [B,cap1]
+  int32_t *prev, *stop;  // [2B]; [B], used when the caller passes no stop
+};
+
+// The workspace of all three entries (their size queries walk it from a null base).  Per side the buffers [tokens, d] (x, q, k,
+// v, ctx, msg), [tokens, 2 dh] (enc), [tokens, 2 d] (h), [tokens] (cert, dust); then the stacked counts, the assignment stage's
+// MNN workspace (match_tiles.h) and 1024 bytes of slack; then the early-stop block, then the pruning block, 256 bytes of slack
+// each.  Stacked (equal capacities): every buffer is ONE array [2B, cap, width], side 0 = entries 0..B-1, side 1 = entries
+// B..2B-1.  LightGlue applies the same weights to both sides, so every per-side launch becomes one launch over 2B entries (cross
+// attention reaches the partner entry B entries on); s[0] / s[1] stay views of the halves.  The array lies in the two regions
+// that its halves would take apart, side 1 directly behind side 0's last element: rounding each half up never gives less than the
+// whole needs, so the size does not depend on `stacked`.
+void carve(WsCarver& c, LgWs& w, LgMode mode, const LgShape& sh) {
+  const size_t B = (size_t)sh.B, d = (size_t)sh.d;
   const struct {
     float* Side::*buf;
     size_t width;  // floats per token
-  } bufs[] = {{&Side::x, (size_t)d},   {&Side::enc, (size_t)2 * dh}, {&Side::q, (size_t)d},     {&Side::k, (size_t)d}, {&Side::v, (size_t)d},
-              {&Side::ctx, (size_t)d}, {&Side::msg, (size_t)d},      {&Side::h, (size_t)2 * d}, {&Side::cert, 1},      {&Side::dust, 1}};
-  if (stacked) {
+  } bufs[] = {{&Side::x, d},   {&Side::enc, (size_t)2 * sh.dh}, {&Side::q, d},     {&Side::k, d},     {&Side::v, d},
+              {&Side::ctx, d}, {&Side::msg, d},                 {&Side::h, 2 * d}, {&Side::cert, 1}, {&Side::dust, 1}};
+  if (sh.stacked()) {
     for (const auto& b : bufs) {
-      const size_t n = (size_t)B * cap0 * b.width;
+      const size_t n = B * sh.cap0 * b.width;
       float* both = c.take<float>(n);
       c.take<float>(n);
-      s0.*b.buf = both;
-      s1.*b.buf = both ? both + n : nullptr;
+      w.s[0].*b.buf = both;
+      w.s[1].*b.buf = both ? both + n : nullptr;
     }
   } else {
-    for (const auto& b : bufs) s0.*b.buf = c.take<float>((size_t)B * cap0 * b.width);
-    for (const auto& b : bufs) s1.*b.buf = c.take<float>((size_t)B * cap1 * b.width);
+    for (const auto& b : bufs) w.s[0].*b.buf = c.take<float>(B * sh.cap0 * b.width);
+    for (const auto& b : bufs) w.s[1].*b.buf = c.take<float>(B * sh.cap1 * b.width);
   }
-  cnt2 = c.take<int32_t>((size_t)2 * B);  // the counts of both sides as [2B] (stacked only)
-  einx_match::carve(c, a, B, cap0, cap1);
+  w.cnt2 = c.take<int32_t>(2 * B);
+  einx_match::carve(c, w.mnn, sh.B, sh.cap0, sh.cap1);
   c.slack(1024);
+  if (mode == LG_PLAIN) return;
+  w.heads = c.take<const float*>((size_t)4 * sh.n_layers);
+  w.act = c.take<int32_t>(2 * B);
+  w.below = c.take<int32_t>(B);
+  w.done = c.take<int32_t>(B);
+  c.slack(256);
+  if (mode == LG_EARLY_STOP) return;
+  w.dst0 = c.take<int32_t>(B * sh.cap0);
+  w.dst1 = c.take<int32_t>(B * sh.cap1);
+  w.prev = c.take<int32_t>(2 * B);
+  w.stop = c.take<int32_t>(B);
+  c.slack(256);
 }
 
 __global__ void lg_stack_counts_kernel(const int32_t* n, const int32_t* m, int B, int32_t* out) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < 2 * B) out[t] = t < B ? n[t] : m[t - B];
-}
-
-// what early stopping adds behind carve()'s regions (einx_lightglue_early_stop_ws_bytes walks the same function)
-struct EsWs {
-  const float** heads;  // [4 n_layers] device table
-  int32_t *act, *below, *done;  // private active counts [2B]; the decision's counters [B] each
-};
-void carve_es(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, EsWs& e, bool stacked, int B, int cap0, int cap1, int d, int dh,
-              int n_layers) {
-  carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, d, dh);
-  e.heads = c.take<const float*>((size_t)4 * n_layers);
-  e.act = c.take<int32_t>((size_t)2 * B);
-  e.below = c.take<int32_t>((size_t)B);
-  e.done = c.take<int32_t>((size_t)B);
-  c.slack(256);
-}
-
-// what point pruning adds behind carve_es()'s regions (einx_lightglue_adaptive_ws_bytes walks the same function)
-struct AdWs {
-  int32_t *dst0, *dst1;  // [B,cap0], [B,cap1]
-  int32_t *prev, *stop;  // [2B]; [B], used when the caller passes no stop
-};
-void carve_ad(WsCarver& c, Side& s0, Side& s1, int32_t*& cnt2, MnnArgs& a, EsWs& e, AdWs& p, bool stacked, int B, int cap0, int cap1, int d, int dh,
-              int n_layers) {
-  carve_es(c, s0, s1, cnt2, a, e, stacked, B, cap0, cap1, d, dh, n_layers);
-  p.dst0 = c.take<int32_t>((size_t)B * cap0);
-  p.dst1 = c.take<int32_t>((size_t)B * cap1);
-  p.prev = c.take<int32_t>((size_t)2 * B);
-  p.stop = c.take<int32_t>((size_t)B);
-  c.slack(256);
 }
 
 // persistent launch size: resident workgroups of the tile kernels on this device (a multiple of
@@ -1396,7 +1402,7 @@ struct Dims {
 // fused Wqkv projection + rotary split: X [B,cap,d] -> q, k (rotary applied), v, each [B,cap,d]
 int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const float* X, const float* Wqkv, const float* bqkv, float* q, float* k,
                   float* v) {
-  const int D = dm.d;  // (shadows the file-level constant)
+  const int d = dm.d;
   GemmArgs g{};
   g.X = X;
   g.X2 = nullptr;
@@ -1405,12 +1411,12 @@ int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const fl
   g.Y = nullptr;
   g.cnt = s.cnt;
   g.cap = s.cap;
-  g.ldx = D;
+  g.ldx = d;
   g.ldx2 = 0;
   g.Ksplit = 0x7fffffff;
-  g.K = D;
-  g.N = 3 * D;
-  g.ldy = D;
+  g.K = d;
+  g.N = 3 * d;
+  g.ldy = d;
   g.div = 1.0f;
   g.B = B;
   g.enc = s.enc;
@@ -1419,9 +1425,9 @@ int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const fl
   g.Yv = v;
   g.d = dm.d;
   g.dh = dm.dh;
-  const int tiles = 3 * einx_cdiv(D, BN) * einx_cdiv(s.cap, BM) * B;  // three blocks (q | k | v) of whole tiles each
-  if (tiles < 256 && D % SBN == 0 && D % SBK == 0) {  // as small_grid()
-    const dim3 sg((unsigned)(3 * D / SBN), (unsigned)einx_cdiv(s.cap, SBM), (unsigned)B);
+  const int tiles = 3 * einx_cdiv(d, BN) * einx_cdiv(s.cap, BM) * B;  // three blocks (q | k | v) of whole tiles each
+  if (tiles < 256 && d % SBN == 0 && d % SBK == 0) {  // as small_grid()
+    const dim3 sg((unsigned)(3 * d / SBN), (unsigned)einx_cdiv(s.cap, SBM), (unsigned)B);
     EINX_PROF("lg_gemm_small_kernel", st);
     if (dm.shipped()) hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_ROPE>, sg, dim3(256), 0, st, g);
     else hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_ROPE_ANY>, sg, dim3(256), 0, st, g);
@@ -1476,17 +1482,17 @@ int attn(hipStream_t st, int B, const Dims& dm, const float* Q, const int32_t* n
 // ffn(cat[x,msg]) + residual, in place on s.x
 int ffn(hipStream_t st, const Side& s, int B, const Dims& dm, const float* msg, const float* w0, const float* b0, const float* g, const float* be,
         const float* w3, const float* b3) {
-  const int D = dm.d;  // (shadows the file-level constant)
+  const int d = dm.d;
   // (one fused launch for ffn.0 + LayerNorm + GELU was measured in round 3 and is slower: tools/experiments/lg_ffn0_ln_gelu_kernel.hip.txt)
-  if (gemm(st, EPI_BIAS, s, B, s.x, D, msg, D, D, 2 * D, w0, b0, 2 * D, s.h, 2 * D)) return -1;
+  if (gemm(st, EPI_BIAS, s, B, s.x, d, msg, d, d, 2 * d, w0, b0, 2 * d, s.h, 2 * d)) return -1;
   {
     EINX_PROF("lg_ln_gelu_kernel", st);
     const dim3 lg((unsigned)einx_cdiv(s.cap, 4), (unsigned)B);
-    if (2 * D == 512) hipLaunchKernelGGL(lg_ln_gelu_kernel, lg, dim3(256), 0, st, s.h, s.cnt, s.cap, g, be);
-    else hipLaunchKernelGGL(lg_ln_gelu_any_kernel, lg, dim3(256), 0, st, s.h, s.cnt, s.cap, 2 * D, g, be);
+    if (2 * d == 512) hipLaunchKernelGGL(lg_ln_gelu_kernel, lg, dim3(256), 0, st, s.h, s.cnt, s.cap, g, be);
+    else hipLaunchKernelGGL(lg_ln_gelu_any_kernel, lg, dim3(256), 0, st, s.h, s.cnt, s.cap, 2 * d, g, be);
   }
   if (hipGetLastError() != hipSuccess) return -1;
-  return gemm(st, EPI_RESID, s, B, s.h, 2 * D, nullptr, 0, 0x7fffffff, 2 * D, w3, b3, D, s.x, D);
+  return gemm(st, EPI_RESID, s, B, s.h, 2 * d, nullptr, 0, 0x7fffffff, 2 * d, w3, b3, d, s.x, d);
 }
 
 }  // namespace
@@ -1540,20 +1546,41 @@ bool dims_of(int d, int heads, Dims& dm) {
 }
 }  // namespace
 
-EINX_EXPORT size_t einx_lg_ws_bytes_heads(int B, int cap0, int cap1, int d, int heads, int input_dim) {
+namespace {
+// the one launch check of this file; `entry`: the exported function the error is reported under
+#define LG_CHECK(entry, expr)                                         \
+  do {                                                                \
+    if ((expr) != 0 || hipGetLastError() != hipSuccess) {             \
+      einx_set_error("%s: kernel launch failed at %s", entry, #expr); \
+      return EINX_ERR_LAUNCH;                                         \
+    }                                                                 \
+  } while (0)
+constexpr const char* LG = "einx_lightglue";  // all three modes report under it
+
+size_t lg_ws_bytes(LgMode mode, int B, int cap0, int cap1, int d, int heads, int n_layers) {
   Dims dm;
   if (B <= 0 || cap0 <= 0 || cap1 <= 0 || !dims_of(d, heads, dm)) return 0;
-  (void)input_dim;
-  Side s0, s1;
-  int32_t* cnt2;
-  MnnArgs a;
+  if (mode != LG_PLAIN && (n_layers < 1 || n_layers > LG_MAX_HEADS)) return 0;
+  LgWs w;
   WsCarver c{nullptr};
-  carve(c, s0, s1, cnt2, a, cap0 == cap1, B, cap0, cap1, d, dm.dh);
+  carve(c, w, mode, {B, cap0, cap1, d, dm.dh, n_layers});
   return c.bytes;
 }
+}  // namespace
+
+// (input_dim: part of the ABI; the descriptors are projected in place, so no region depends on it)
+EINX_EXPORT size_t einx_lg_ws_bytes_heads(int B, int cap0, int cap1, int d, int heads, int) { return lg_ws_bytes(LG_PLAIN, B, cap0, cap1, d, heads, 0); }
 
 EINX_EXPORT size_t einx_lg_ws_bytes(int B, int cap0, int cap1, int d, int input_dim) {  // 64-wide heads (the LightGlue default)
   return d > 0 && d % 64 == 0 ? einx_lg_ws_bytes_heads(B, cap0, cap1, d, d / 64, input_dim) : 0;
+}
+
+EINX_EXPORT size_t einx_lightglue_early_stop_ws_bytes(int B, int cap0, int cap1, int d, int heads, int, int n_layers) {
+  return lg_ws_bytes(LG_EARLY_STOP, B, cap0, cap1, d, heads, n_layers);
+}
+
+EINX_EXPORT size_t einx_lightglue_adaptive_ws_bytes(int B, int cap0, int cap1, int d, int heads, int, int n_layers) {
+  return lg_ws_bytes(LG_ADAPTIVE, B, cap0, cap1, d, heads, n_layers);
 }
 
 namespace {
@@ -1572,286 +1599,377 @@ struct EarlyStop {
   const Adaptive* ad;      // null: einx_lightglue_early_stop
 };
 
+// A set of keypoint counts: side 0 [B], side 1 [B], and the two as one [2B] array (what a launch over stacked sides reads)
+struct Counts {
+  const int32_t *c0, *c1, *both;
+};
+
+// the sides as a shared-weight stage iterates over them: one view of 2B entries (stacked), or two of B
+struct Views {
+  Side s[2];
+  int n, entries;
+};
+
+struct LgCtx {
+  hipStream_t st;
+  const einx_lg_weights* w;
+  Dims dm;
+  LgShape sh;
+  LgMode mode;
+  const EarlyStop* es;  // null: LG_PLAIN
+  const Adaptive* ad;   // null unless LG_ADAPTIVE
+  bool decide;          // the stop decision runs (LG_ADAPTIVE: only with depth_confidence > 0)
+  int32_t* stop;        // the caller's, or the workspace's; null: LG_PLAIN
+  LgWs ws;
+  Counts caller, layers, heads;  // see lg_run
+  float size[2][2];              // the images' (h, w)
+  int64_t* matches[2];
+  float *scores[2], *la, *ref[2];
+  bool all_layers;  // ref holds every layer's descriptors (training-mode output)
+};
+
+Views views(const LgCtx& c, const Counts& cnt, bool stacked) {
+  Views v{{c.ws.s[0], c.ws.s[1]}, stacked ? 1 : 2, stacked ? 2 * c.sh.B : c.sh.B};
+  v.s[0].cnt = stacked ? cnt.both : cnt.c0;
+  v.s[1].cnt = cnt.c1;
+  return v;
+}
+
+// confidence_threshold of a layer (lightglue.py:718-722): in double, rounded to float32 once
+float confidence_threshold(int li, int n_layers) {
+  const double thr = 0.8 + 0.1 * exp(-4.0 * li / n_layers);
+  return (float)(thr < 0.0 ? 0.0 : thr > 1.0 ? 1.0 : thr);
+}
+
+// li < 0: the init launch, which reads no field of a layer
+TailArgs tail_args(const LgCtx& c, int li) {
+  TailArgs t{};
+  t.x0 = c.ws.s[0].x, t.x1 = c.ws.s[1].x;
+  t.act = c.ws.act;
+  t.stop = c.stop;
+  t.cap0 = c.sh.cap0, t.cap1 = c.sh.cap1, t.d = c.sh.d, t.B = c.sh.B;
+  if (li < 0) return t;
+  t.layer = li;
+  if (c.decide) t.tw = c.es->heads[li].token_w, t.tb = c.es->heads[li].token_b;
+  t.thr = confidence_threshold(li, c.w->n_layers);
+  return t;
+}
+
+PruneArgs prune_args(const LgCtx& c, int li) {
+  const Side* s = c.ws.s;
+  PruneArgs a{};
+  a.t = tail_args(c, li);
+  a.enc0 = s[0].enc, a.enc1 = s[1].enc;
+  a.tx0 = s[0].ctx, a.tx1 = s[1].ctx, a.te0 = s[0].h, a.te1 = s[1].h;
+  a.live = c.ad->live, a.prev = c.ws.prev;
+  a.dst0 = c.ws.dst0, a.dst1 = c.ws.dst1;
+  a.kept0 = c.ad->kept0, a.kept1 = c.ad->kept1, a.prune0 = c.ad->prune0, a.prune1 = c.ad->prune1;
+  a.n = c.caller.c0, a.m = c.caller.c1;
+  a.dh2 = 2 * c.sh.dh;
+  a.min_kpts = c.ad->min_kpts;
+  a.set_stop = c.decide ? 1 : 0;
+  a.thr_w = c.ad->thr_w;
+  if (li >= 0) a.mw = c.es->heads[li].match_w, a.mb = c.es->heads[li].match_b;
+  return a;
+}
+
+// the grid of a launch over 2B entries that gives every workgroup `rows` rows of the longer side
+dim3 tail_grid(const LgShape& sh, int rows) { return dim3((unsigned)einx_cdiv(sh.cap0 > sh.cap1 ? sh.cap0 : sh.cap1, rows), (unsigned)(2 * sh.B)); }
+
+template <typename... Src>  // the arguments of a match_head()
+void launch_matchability(hipStream_t st, const Side& s, const float* x, int entries, int d, Src... src) {
+  hipLaunchKernelGGL(lg_matchability_kernel<Src...>, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)entries), dim3(256), 0, st, x, s.cnt, s.cap, d, src...,
+                     s.cert, s.dust);
+}
+
+// ---- what has to be on the device before the first layer.  Early stopping: the heads' table, the [2B] counts, the private
+// counts, stop and the counters in one launch; point pruning: its outputs' start values.  Otherwise the [2B] counts when the
+// stacked layers will read them; plain and unstacked: no launch.
+int lg_setup(const LgCtx& c) {
+  const LgShape& sh = c.sh;
+  if (c.es) {
+    HeadTable t;
+    for (int i = 0; i < sh.n_layers; ++i) {
+      t.p[4 * i + 0] = c.es->heads[i].proj_w;
+      t.p[4 * i + 1] = c.es->heads[i].proj_b;
+      t.p[4 * i + 2] = c.es->heads[i].match_w;
+      t.p[4 * i + 3] = c.es->heads[i].match_b;
+    }
+    const int items = 4 * sh.n_layers > 2 * sh.B ? 4 * sh.n_layers : 2 * sh.B;
+    hipLaunchKernelGGL(lg_es_init_kernel, dim3((unsigned)einx_cdiv(items, 256)), dim3(256), 0, c.st, t, sh.n_layers, c.ws.heads, c.caller.c0, c.caller.c1,
+                       sh.B, sh.cap0, sh.cap1, c.ws.cnt2, c.ws.act, c.stop, c.ws.below, c.ws.done);
+    if (c.ad) hipLaunchKernelGGL(lg_prune_init_kernel, tail_grid(sh, 256), dim3(256), 0, c.st, prune_args(c, -1));
+  } else if (sh.stacked()) {
+    hipLaunchKernelGGL(lg_stack_counts_kernel, dim3((unsigned)einx_cdiv(2 * sh.B, 256)), dim3(256), 0, c.st, c.caller.c0, c.caller.c1, sh.B, c.ws.cnt2);
+  }
+  LG_CHECK(LG, 0);
+  return EINX_OK;
+}
+
+// ---- input projection (or copy) + positional encodings (per side: own inputs, own image size)
+int lg_input(const LgCtx& c) {
+  const einx_lg_weights* w = c.w;
+  const int B = c.sh.B, d = c.sh.d, dh = c.sh.dh;
+  const Views v = views(c, c.caller, false);
+  for (int sd = 0; sd < 2; ++sd) {
+    const Side& s = v.s[sd];
+    if (w->in_w) {
+      LG_CHECK(LG, gemm(c.st, EPI_BIAS, s, B, s.desc, w->input_dim, nullptr, 0, 0x7fffffff, w->input_dim, w->in_w, w->in_b, d, s.x, d));
+    } else {
+      const size_t per = (size_t)s.cap * d;
+      hipLaunchKernelGGL(lg_copy_rows_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, c.st, s.desc, s.x, s.cnt, s.cap, d, per);
+      LG_CHECK(LG, 0);
+    }
+    hipLaunchKernelGGL(lg_posenc_kernel, dim3((unsigned)einx_cdiv(s.cap * (dh / 2), 256), (unsigned)B), dim3(256), 0, c.st, s.kpts, s.cnt, s.cap,
+                       c.size[sd][0], c.size[sd][1], w->Wr, s.enc, dh);
+    LG_CHECK(LG, 0);
+  }
+  return EINX_OK;
+}
+
+// ---- one transformer layer: SelfBlock, then CrossBlock
+int lg_layer(const LgCtx& c, int li) {
+  const einx_lg_layer& L = c.w->layers[li];
+  const Dims& dm = c.dm;
+  hipStream_t st = c.st;
+  const int B = c.sh.B, d = c.sh.d;
+  const Views v = views(c, c.layers, c.sh.stacked());
+  const int E = v.entries;
+  for (int sd = 0; sd < v.n; ++sd) {
+    const Side& s = v.s[sd];
+    LG_CHECK(LG, gemm_qkv_rope(st, s, E, dm, s.x, L.Wqkv, L.bqkv, s.q, s.k, s.v));
+    LG_CHECK(LG, attn(st, E, dm, s.q, s.cnt, s.cap, s.k, s.v, s.cnt, s.cap, s.ctx));
+    if (L.Wo) {
+      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.ctx, d, nullptr, 0, 0x7fffffff, d, L.Wo, L.bo, d, s.msg, d));
+      LG_CHECK(LG, ffn(st, s, E, dm, s.msg, L.sf0_w, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_b));
+    } else {  // out_proj folded into the FFN's first Linear at load time: message = context
+      LG_CHECK(LG, ffn(st, s, E, dm, s.ctx, L.sf0_w, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_b));
+    }
+  }
+  // to_qk and to_v read the same rows: with the merged weight image [Wqk; Wv] (shipped widths) they are ONE launch writing
+  // qk | v side by side into the FFN's hidden buffer (free until ffn.0 runs), and the attention reads them at row stride 2 d --
+  // the same k-ordered chain and bias per output, one launch less per layer
+  const bool merged = L.Wqk_v && L.bqk_v && dm.shipped();
+  for (int sd = 0; sd < v.n; ++sd) {
+    const Side& s = v.s[sd];
+    if (merged) {
+      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wqk_v, L.bqk_v, 2 * d, s.h, 2 * d));
+    } else {
+      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wqk, L.bqk, d, s.q, d));
+      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wv, L.bv, d, s.v, d));
+    }
+  }
+  const Side &r0 = v.s[0], &r1 = v.s[1];
+  if (v.n == 1) {  // stacked: entry b attends to the keys / values of its partner entry (b + B) mod 2B
+    if (merged) LG_CHECK(LG, attn(st, E, dm, r0.h, r0.cnt, r0.cap, r0.h, r0.h + d, r0.cnt, r0.cap, r0.ctx, B, true));
+    else LG_CHECK(LG, attn(st, E, dm, r0.q, r0.cnt, r0.cap, r0.q, r0.v, r0.cnt, r0.cap, r0.ctx, B));
+  } else if (merged) {
+    LG_CHECK(LG, attn(st, B, dm, r0.h, r0.cnt, r0.cap, r1.h, r1.h + d, r1.cnt, r1.cap, r0.ctx, 0, true));
+    LG_CHECK(LG, attn(st, B, dm, r1.h, r1.cnt, r1.cap, r0.h, r0.h + d, r0.cnt, r0.cap, r1.ctx, 0, true));
+  } else {
+    LG_CHECK(LG, attn(st, B, dm, r0.q, r0.cnt, r0.cap, r1.q, r1.v, r1.cnt, r1.cap, r0.ctx));
+    LG_CHECK(LG, attn(st, B, dm, r1.q, r1.cnt, r1.cap, r0.q, r0.v, r0.cnt, r0.cap, r1.ctx));
+  }
+  for (int sd = 0; sd < v.n; ++sd) {
+    const Side& s = v.s[sd];
+    if (L.Wco) {
+      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.ctx, d, nullptr, 0, 0x7fffffff, d, L.Wco, L.bco, d, s.msg, d));
+      LG_CHECK(LG, ffn(st, s, E, dm, s.msg, L.cf0_w, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_b));
+    } else {
+      LG_CHECK(LG, ffn(st, s, E, dm, s.ctx, L.cf0_w, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_b));
+    }
+  }
+  return EINX_OK;
+}
+
+// ---- ref_descriptors: x of both sides, rows below `cnt`, into slot `slot` of `slots` per pair (lightglue.py:626-629)
+int lg_ref_copy(const LgCtx& c, const Counts& cnt, int slot, int slots) {
+  const Views v = views(c, cnt, false);
+  for (int sd = 0; sd < 2; ++sd) {
+    const Side& s = v.s[sd];
+    if (!c.ref[sd]) continue;
+    const size_t per = (size_t)s.cap * c.sh.d;
+    hipLaunchKernelGGL(lg_copy_rows_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)c.sh.B), dim3(256), 0, c.st, s.x, c.ref[sd] + (size_t)slot * per,
+                       s.cnt, s.cap, c.sh.d, per * (size_t)slots);
+    LG_CHECK(LG, 0);
+  }
+  return EINX_OK;
+}
+
+// ---- the pairs still running decide whether layer li was their last
+int lg_stop(const LgCtx& c, int li) {
+  StopArgs a{};
+  a.t = tail_args(c, li);
+  a.depth = c.es->depth_confidence;
+  a.below = c.ws.below;
+  a.done = c.ws.done;
+  if (c.ad) a.tot0 = c.caller.c0, a.tot1 = c.caller.c1;
+  EINX_PROF("lg_stop_kernel", c.st);
+  hipLaunchKernelGGL(lg_stop_kernel, tail_grid(c.sh, STOP_ROWS), dim3(256), 0, c.st, a);
+  LG_CHECK(LG, 0);
+  return EINX_OK;
+}
+
+// ---- point pruning behind layer li, after the stop decision (lightglue.py:632-652): a pair that has just stopped is not pruned
+int lg_prune(const LgCtx& c, int li) {
+  const LgShape& sh = c.sh;
+  const PruneArgs a = prune_args(c, li);
+  EINX_PROF("lg_prune (keep + scan + gather + copy back)", c.st);
+  hipLaunchKernelGGL(lg_keep_kernel, tail_grid(sh, STOP_ROWS), dim3(256), 0, c.st, a);
+  LG_CHECK(LG, 0);
+  hipLaunchKernelGGL(lg_prune_scan_kernel, dim3((unsigned)sh.B), dim3(256), 0, c.st, a);
+  LG_CHECK(LG, 0);
+  hipLaunchKernelGGL(lg_prune_gather_kernel, tail_grid(sh, 4), dim3(256), 0, c.st, a);
+  LG_CHECK(LG, 0);
+  const size_t quads = (size_t)(sh.cap0 > sh.cap1 ? sh.cap0 : sh.cap1) * ((sh.d + 2 * sh.dh) / 4);
+  hipLaunchKernelGGL(lg_prune_copyback_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)(2 * sh.B)), dim3(256), 0, c.st, a);
+  LG_CHECK(LG, 0);
+  return EINX_OK;
+}
+
+// ---- MatchAssignment's inputs (lightglue.py:365-377): final_proj / d^(1/4) and the matchability terms.  Early stopping, route
+// (a): one stage over every pair's own rows, each pair with the head it stopped at (x frozen since then)
+int lg_assign_heads(const LgCtx& c) {
+  const einx_lg_weights* w = c.w;
+  const int d = c.sh.d;
+  const float div = sqrtf(sqrtf((float)d));
+  const Views v = views(c, c.heads, c.sh.stacked());
+  for (int sd = 0; sd < v.n; ++sd) {
+    const Side& s = v.s[sd];
+    if (c.es) {
+      LG_CHECK(LG, gemm(c.st, EPI_DIV_HEAD, s, v.entries, s.x, d, nullptr, 0, 0x7fffffff, d, nullptr, nullptr, d, s.q, d, div, c.ws.heads, c.stop,
+                        c.sh.B, c.sh.n_layers));
+      launch_matchability(c.st, s, s.x, v.entries, d, c.ws.heads, c.stop, c.sh.B, c.sh.n_layers);
+    } else {
+      LG_CHECK(LG, gemm(c.st, EPI_DIV, s, v.entries, s.x, d, nullptr, 0, 0x7fffffff, d, w->proj_w, w->proj_b, d, s.q, d, div));
+      launch_matchability(c.st, s, s.x, v.entries, d, w->match_w, w->match_b);
+    }
+    LG_CHECK(LG, 0);
+  }
+  return EINX_OK;
+}
+
+dim3 assign_grid(const MnnArgs& a, int B) { return dim3((unsigned)einx_cdiv(a.cap1, BN), (unsigned)einx_cdiv(a.cap0, BM), (unsigned)B); }
+
+// The first half of every assignment: the MNN argument block from the two sides (q, cert, dust) and a pair of counts, then the
+// softmax statistics (first tile pass) and their reduction.  The caller opens the profile scope and runs its own second pass.
+int assign_prologue(const char* entry, hipStream_t st, MnnArgs& a, const Side& s0, const Side& s1, const int32_t* n, const int32_t* m, int B, int d,
+                    float* la) {
+  a.d0 = s0.q;
+  a.d1 = s1.q;
+  a.n = n;
+  a.m = m;
+  a.cap0 = s0.cap;
+  a.cap1 = s1.cap;
+  a.D = d;
+  a.la = la;
+  a.cert0 = s0.cert;
+  a.cert1 = s1.cert;
+  a.dust0 = s0.dust;
+  a.dust1 = s1.dust;
+  const int mx = a.cap0 > a.cap1 ? a.cap0 : a.cap1;
+  hipLaunchKernelGGL((mnn_tile_kernel<1, false>), assign_grid(a, B), dim3(THREADS), 0, st, a);
+  LG_CHECK(entry, 0);
+  hipLaunchKernelGGL(mnn_lse_kernel, dim3((unsigned)einx_cdiv(mx + 1, 256), (unsigned)B), dim3(256), 0, st, a);
+  LG_CHECK(entry, 0);
+  return EINX_OK;
+}
+
+// ---- assignment scores, their arg-max keys, filter_matches
+int lg_assign(const LgCtx& c) {
+  const LgShape& sh = c.sh;
+  hipStream_t st = c.st;
+  MnnArgs a = c.ws.mnn;
+  if (hipMemsetAsync(a.rowkey, 0, (char*)a.rowstat - (char*)a.rowkey, st) != hipSuccess) {  // rowkey | colkey
+    einx_set_error("einx_lightglue: memset failed");
+    return EINX_ERR_LAUNCH;
+  }
+  EINX_PROF("lg_assignment (3 tile passes + lse + finalize)", st);
+  if (const int rc = assign_prologue(LG, st, a, c.ws.s[0], c.ws.s[1], c.heads.c0, c.heads.c1, sh.B, sh.d, c.la)) return rc;
+  if (c.la) hipLaunchKernelGGL((mnn_tile_kernel<6, true>), assign_grid(a, sh.B), dim3(THREADS), 0, st, a);  // arg-max + log_assignment write in one visit
+  else hipLaunchKernelGGL((mnn_tile_kernel<0, true>), assign_grid(a, sh.B), dim3(THREADS), 0, st, a);
+  LG_CHECK(LG, 0);
+  if (c.ad) {  // the keys are those of the live rows: back to original indexing
+    hipLaunchKernelGGL(lg_finalize_scatter_kernel, dim3((unsigned)sh.B), dim3(256), 0, st, a.rowkey, a.colkey, c.heads.both, sh.B, c.ad->kept0,
+                       c.ad->kept1, sh.cap0, sh.cap1, c.w->filter_threshold, c.matches[0], c.matches[1], c.scores[0], c.scores[1]);
+  } else {
+    const int mx = sh.cap0 > sh.cap1 ? sh.cap0 : sh.cap1;
+    hipLaunchKernelGGL(lg_finalize_kernel, dim3((unsigned)einx_cdiv(mx, 256), (unsigned)sh.B), dim3(256), 0, st, a.rowkey, a.colkey, c.heads.c0, c.heads.c1,
+                       sh.cap0, sh.cap1, c.w->filter_threshold, c.matches[0], c.matches[1], c.scores[0], c.scores[1]);
+  }
+  LG_CHECK(LG, 0);
+  return EINX_OK;
+}
+
 int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
            const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws, int64_t* matches0,
            int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0, float* ref1, int ref_layers, void* stream) {
   EINX_CHECK_ARG(w && kpts0 && desc0 && n && kpts1 && desc1 && m && ws && matches0 && matches1 && scores0 && scores1, "null pointer");
   Dims dm;
   EINX_CHECK_ARG(dims_of(w->d, w->heads, dm), "descriptor_dim must be num_heads x head_dim with head_dim a multiple of 4, at most 256");
-  const int D = dm.d;  // (shadows the file-level constant: every width below is the model's)
   EINX_CHECK_ARG(w->struct_size == sizeof(einx_lg_weights) && w->layer_size == sizeof(einx_lg_layer),
                  "einx_lg_weights::struct_size / layer_size do not match this library (header / library ABI mismatch)");
   EINX_CHECK_ARG(w->n_layers >= 1 && w->layers, "no layers");
   EINX_CHECK_ARG(B > 0 && cap0 > 0 && cap1 > 0, "bad shape");
   EINX_CHECK_ARG(w->input_dim % 4 == 0 && w->input_dim > 0, "input_dim must be a multiple of 4");
-  EINX_CHECK_ARG((w->input_dim == D) == (w->in_w == nullptr), "input_proj must be given exactly when input_dim != d");
+  EINX_CHECK_ARG((w->input_dim == dm.d) == (w->in_w == nullptr), "input_proj must be given exactly when input_dim != d");
   EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1 || ref_layers == w->n_layers, "ref_layers must be 0/1 (last layer) or n_layers");
-  const bool all_layers = ref_layers > 1;
-  hipStream_t st = (hipStream_t)stream;
-  Side s0{}, s1{};
-  s0.kpts = kpts0;
-  s0.desc = desc0;
-  s0.cnt = n;
-  s0.cap = cap0;
-  s1.kpts = kpts1;
-  s1.desc = desc1;
-  s1.cnt = m;
-  s1.cap = cap1;
-  // equal capacities (every shipped configuration): the two sides are stacked and every layer runs ONCE over 2B entries --
-  // half the launches, and at small batch twice the workgroups per launch (a single pair: 8.0 -> see profiles/r03_notes.md)
-  const bool stacked = cap0 == cap1;
-  int32_t* cnt2;
-  MnnArgs a;
-  EsWs ew{};
-  AdWs aw{};
-  const Adaptive* ad = es ? es->ad : nullptr;
-  WsCarver c{(char*)ws};
-  if (ad) carve_ad(c, s0, s1, cnt2, a, ew, aw, stacked, B, cap0, cap1, D, dm.dh, w->n_layers);
-  else if (es) carve_es(c, s0, s1, cnt2, a, ew, stacked, B, cap0, cap1, D, dm.dh, w->n_layers);
-  else carve(c, s0, s1, cnt2, a, stacked, B, cap0, cap1, D, dm.dh);
-  // r0 / r1: the sides as the LAYERS see them.  Early stopping: on the private active counts (ew.act = n | m, zeroed per pair as
-  // it stops); the input stage, ref_descriptors and the assignment keep the caller's counts.  sa: the stacked view of those.
-  // Point pruning: the layers still run on ew.act, which shrinks with the rows kept; ref_descriptors and the assignment run on
-  // the LIVE counts (what survived, also of a pair that has stopped), and the input stage alone keeps the caller's counts.
-  Side sb{}, sa{}, r0 = s0, r1 = s1;
-  int32_t* const stop = es ? (es->stop ? es->stop : aw.stop) : nullptr;
-  const bool decide = es && (!ad || es->depth_confidence > 0.0f);
-  PruneArgs pa{};
-  if (es) {
-    HeadTable t;
-    for (int i = 0; i < w->n_layers; ++i) {
-      t.p[4 * i + 0] = es->heads[i].proj_w;
-      t.p[4 * i + 1] = es->heads[i].proj_b;
-      t.p[4 * i + 2] = es->heads[i].match_w;
-      t.p[4 * i + 3] = es->heads[i].match_b;
-    }
-    const int items = 4 * w->n_layers > 2 * B ? 4 * w->n_layers : 2 * B;
-    hipLaunchKernelGGL(lg_es_init_kernel, dim3((unsigned)einx_cdiv(items, 256)), dim3(256), 0, st, t, (int)w->n_layers, ew.heads, n, m, B, cap0, cap1,
-                       cnt2, ew.act, stop, ew.below, ew.done);
-    r0.cnt = ew.act;
-    r1.cnt = ew.act + B;
-    if (ad) {
-      pa.x0 = s0.x, pa.x1 = s1.x, pa.enc0 = s0.enc, pa.enc1 = s1.enc;
-      pa.tx0 = s0.ctx, pa.tx1 = s1.ctx, pa.te0 = s0.h, pa.te1 = s1.h;
-      pa.act = ew.act, pa.live = ad->live, pa.prev = aw.prev;
-      pa.dst0 = aw.dst0, pa.dst1 = aw.dst1;
-      pa.kept0 = ad->kept0, pa.kept1 = ad->kept1, pa.prune0 = ad->prune0, pa.prune1 = ad->prune1;
-      pa.stop = stop;
-      pa.n = n, pa.m = m;
-      pa.cap0 = cap0, pa.cap1 = cap1, pa.d = D, pa.dh2 = 2 * dm.dh, pa.B = B;
-      pa.min_kpts = ad->min_kpts;
-      pa.set_stop = decide ? 1 : 0;
-      pa.thr_w = ad->thr_w;
-      const int mxc = cap0 > cap1 ? cap0 : cap1;
-      hipLaunchKernelGGL(lg_prune_init_kernel, dim3((unsigned)einx_cdiv(mxc, 256), (unsigned)(2 * B)), dim3(256), 0, st, pa);
-    }
-  } else if (stacked) {
-    hipLaunchKernelGGL(lg_stack_counts_kernel, dim3((unsigned)einx_cdiv(2 * B, 256)), dim3(256), 0, st, n, m, B, cnt2);
+  LgCtx c{};
+  c.st = (hipStream_t)stream;
+  c.w = w;
+  c.dm = dm;
+  c.sh = {B, cap0, cap1, dm.d, dm.dh, w->n_layers};
+  c.es = es;
+  if (es) c.ad = es->ad;
+  c.mode = LG_PLAIN;
+  if (es) c.mode = c.ad ? LG_ADAPTIVE : LG_EARLY_STOP;
+  WsCarver wc{(char*)ws};
+  carve(wc, c.ws, c.mode, c.sh);
+  c.ws.s[0].kpts = kpts0, c.ws.s[0].desc = desc0, c.ws.s[0].cap = cap0;
+  c.ws.s[1].kpts = kpts1, c.ws.s[1].desc = desc1, c.ws.s[1].cap = cap1;
+  // caller: the input stage and the all-layers ref copy; with pruning also the stop ratio's denominator
+  // layers: the transformer layers; the stop decision zeroes a pair's, the pruning step shrinks them with the rows kept
+  // heads:  the assignment heads, the last-layer ref copy, the assignment and filter_matches: what survived, also of a stopped pair
+  c.caller = {n, m, c.ws.cnt2};
+  c.layers = c.heads = c.caller;
+  if (es) c.layers = {c.ws.act, c.ws.act + B, c.ws.act};
+  if (c.ad) c.heads = {c.ad->live, c.ad->live + B, c.ad->live};
+  if (es) c.stop = es->stop ? es->stop : c.ws.stop;
+  c.decide = es && (!c.ad || es->depth_confidence > 0.0f);
+  c.size[0][0] = h0, c.size[0][1] = w0, c.size[1][0] = h1, c.size[1][1] = w1;
+  c.matches[0] = matches0, c.matches[1] = matches1, c.scores[0] = scores0, c.scores[1] = scores1;
+  c.la = la, c.ref[0] = ref0, c.ref[1] = ref1;
+  c.all_layers = ref_layers > 1;
+
+  int rc = lg_setup(c);
+  if (!rc) rc = lg_input(c);
+  for (int li = 0; li < w->n_layers && !rc; ++li) {
+    const bool last = li == w->n_layers - 1;
+    rc = lg_layer(c, li);
+    if (!rc && c.all_layers) rc = lg_ref_copy(c, c.caller, li, w->n_layers);
+    if (!rc && c.decide && !last) rc = lg_stop(c, li);
+    if (!rc && c.ad && !last) rc = lg_prune(c, li);
   }
-  if (stacked) {
-    sa = s0;
-    sa.cnt = cnt2;
-    sb = s0;
-    sb.cnt = es ? ew.act : cnt2;
+  if (!rc) rc = lg_assign_heads(c);
+  if (!rc && !c.all_layers) rc = lg_ref_copy(c, c.heads, 0, 1);
+  if (!rc) rc = lg_assign(c);
+  return rc;
+}
+
+// What is wrong with the heads of an early-stop or adaptive call, or null; in the order the entries have always checked: the
+// struct's size, the layer count, the entry's complaint about its own scalars (`own`, or null), every layer's heads.  token_msg:
+// the complaint about a missing token_confidence head, or null when none is needed.
+const char* heads_error(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, const char* layers_msg, const char* own,
+                        const char* token_msg) {
+  if (head_size != sizeof(einx_lg_head)) return "head_size does not match this library's einx_lg_head (header / library ABI mismatch)";
+  if (w->n_layers < 1 || w->n_layers > LG_MAX_HEADS) return layers_msg;
+  if (own) return own;
+  for (int i = 0; i < w->n_layers; ++i) {
+    const einx_lg_head& h = heads[i];
+    if (!(h.proj_w && h.proj_b && h.match_w && h.match_b)) return "every layer needs its log_assignment head";
+    if (token_msg && i < w->n_layers - 1 && !(h.token_w && h.token_b)) return token_msg;
   }
-  Side* sides[2] = {&s0, &s1};
-  Side* run[2] = {stacked ? &sb : &r0, &r1};  // what the shared-weight stages iterate over
-  Side l0 = s0, l1 = s1;  // the sides at their live counts (point pruning)
-  if (ad) {
-    sa.cnt = ad->live;
-    l0.cnt = ad->live;
-    l1.cnt = ad->live + B;
-  }
-  Side* asg[2] = {stacked ? &sa : ad ? &l0 : &s0, ad ? &l1 : &s1};  // the assignment's projections: every pair's own rows
-  Side* outs[2] = {ad ? &l0 : &s0, ad ? &l1 : &s1};                // ... and ref_descriptors
-  const int nrun = stacked ? 1 : 2, Br = stacked ? 2 * B : B;
-  const float sz[2][2] = {{h0, w0}, {h1, w1}};
-#define LG_CHECK(expr)                                                    \
-  do {                                                                    \
-    if ((expr) != 0 || hipGetLastError() != hipSuccess) {                 \
-      einx_set_error("einx_lightglue: kernel launch failed at %s", #expr); \
-      return EINX_ERR_LAUNCH;                                             \
-    }                                                                     \
-  } while (0)
-  LG_CHECK(0);
-  // ---- input projection (or copy) + positional encodings (per side: own inputs, own image size) --------
-  for (int sd = 0; sd < 2; ++sd) {
-    Side& s = *sides[sd];
-    if (w->in_w) {
-      LG_CHECK(gemm(st, EPI_BIAS, s, B, s.desc, w->input_dim, nullptr, 0, 0x7fffffff, w->input_dim, w->in_w, w->in_b, D, s.x, D));
-    } else {
-      const size_t per = (size_t)s.cap * D;
-      hipLaunchKernelGGL(lg_copy_rows_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, st, s.desc, s.x, s.cnt, s.cap, D, per);
-      LG_CHECK(0);
-    }
-    hipLaunchKernelGGL(lg_posenc_kernel, dim3((unsigned)einx_cdiv(s.cap * (dm.dh / 2), 256), (unsigned)B), dim3(256), 0, st, s.kpts, s.cnt, s.cap,
-                       sz[sd][0], sz[sd][1], w->Wr, s.enc, dm.dh);
-    LG_CHECK(0);
-  }
-  // ---- transformer layers --------------------------------------------------------------------
-  for (int li = 0; li < w->n_layers; ++li) {
-    const einx_lg_layer& L = w->layers[li];
-    for (int sd = 0; sd < nrun; ++sd) {
-      Side& s = *run[sd];
-      LG_CHECK(gemm_qkv_rope(st, s, Br, dm, s.x, L.Wqkv, L.bqkv, s.q, s.k, s.v));
-      LG_CHECK(attn(st, Br, dm, s.q, s.cnt, s.cap, s.k, s.v, s.cnt, s.cap, s.ctx));
-      if (L.Wo) {
-        LG_CHECK(gemm(st, EPI_BIAS, s, Br, s.ctx, D, nullptr, 0, 0x7fffffff, D, L.Wo, L.bo, D, s.msg, D));
-        LG_CHECK(ffn(st, s, Br, dm, s.msg, L.sf0_w, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_b));
-      } else {  // out_proj folded into the FFN's first Linear at load time: message = context
-        LG_CHECK(ffn(st, s, Br, dm, s.ctx, L.sf0_w, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_b));
-      }
-    }
-    // to_qk and to_v read the same rows: with the merged weight image [Wqk; Wv] (shipped widths) they are ONE launch writing
-    // qk | v side by side into the FFN's hidden buffer (free until ffn.0 runs), and the attention reads them at row stride 2 d --
-    // the same k-ordered chain and bias per output, one launch less per layer
-    const bool merged = L.Wqk_v && L.bqk_v && dm.shipped();
-    for (int sd = 0; sd < nrun; ++sd) {
-      Side& s = *run[sd];
-      if (merged) {
-        LG_CHECK(gemm(st, EPI_BIAS, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, L.Wqk_v, L.bqk_v, 2 * D, s.h, 2 * D));
-      } else {
-        LG_CHECK(gemm(st, EPI_BIAS, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, L.Wqk, L.bqk, D, s.q, D));
-        LG_CHECK(gemm(st, EPI_BIAS, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, L.Wv, L.bv, D, s.v, D));
-      }
-    }
-    if (stacked) {  // entry b attends to the keys / values of its partner entry (b + B) mod 2B
-      if (merged) LG_CHECK(attn(st, Br, dm, sb.h, sb.cnt, sb.cap, sb.h, sb.h + D, sb.cnt, sb.cap, sb.ctx, B, true));
-      else LG_CHECK(attn(st, Br, dm, sb.q, sb.cnt, sb.cap, sb.q, sb.v, sb.cnt, sb.cap, sb.ctx, B));
-    } else if (merged) {
-      LG_CHECK(attn(st, B, dm, r0.h, r0.cnt, r0.cap, r1.h, r1.h + D, r1.cnt, r1.cap, r0.ctx, 0, true));
-      LG_CHECK(attn(st, B, dm, r1.h, r1.cnt, r1.cap, r0.h, r0.h + D, r0.cnt, r0.cap, r1.ctx, 0, true));
-    } else {
-      LG_CHECK(attn(st, B, dm, r0.q, r0.cnt, r0.cap, r1.q, r1.v, r1.cnt, r1.cap, r0.ctx));
-      LG_CHECK(attn(st, B, dm, r1.q, r1.cnt, r1.cap, r0.q, r0.v, r0.cnt, r0.cap, r1.ctx));
-    }
-    for (int sd = 0; sd < nrun; ++sd) {
-      Side& s = *run[sd];
-      if (L.Wco) {
-        LG_CHECK(gemm(st, EPI_BIAS, s, Br, s.ctx, D, nullptr, 0, 0x7fffffff, D, L.Wco, L.bco, D, s.msg, D));
-        LG_CHECK(ffn(st, s, Br, dm, s.msg, L.cf0_w, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_b));
-      } else {
-        LG_CHECK(ffn(st, s, Br, dm, s.ctx, L.cf0_w, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_b));
-      }
-    }
-    for (int sd = 0; sd < 2; ++sd) {
-      Side& s = *sides[sd];
-      float* ref = sd == 0 ? ref0 : ref1;
-      if (ref && all_layers) {  // training-mode output: every layer's descriptors (lightglue.py:626-629)
-        const size_t per = (size_t)s.cap * D;
-        hipLaunchKernelGGL(lg_copy_rows_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, st, s.x, ref + (size_t)li * per,
-                           s.cnt, s.cap, D, per * (size_t)w->n_layers);
-        LG_CHECK(0);
-      }
-    }
-    if (decide && li < w->n_layers - 1) {  // the pairs still running decide whether this was their last layer
-      StopArgs sa_;
-      sa_.x0 = s0.x;
-      sa_.x1 = s1.x;
-      sa_.act0 = ew.act;
-      sa_.act1 = ew.act + B;
-      sa_.cap0 = cap0;
-      sa_.cap1 = cap1;
-      sa_.d = D;
-      sa_.B = B;
-      sa_.layer = li;
-      sa_.w = es->heads[li].token_w;
-      sa_.bias = es->heads[li].token_b;
-      const double thr = 0.8 + 0.1 * exp(-4.0 * li / w->n_layers);  // confidence_threshold (lightglue.py:718-722), rounded to float32 once
-      sa_.thr = (float)(thr < 0.0 ? 0.0 : thr > 1.0 ? 1.0 : thr);
-      sa_.depth = es->depth_confidence;
-      sa_.below = ew.below;
-      sa_.done = ew.done;
-      sa_.stop = stop;
-      sa_.tot0 = ad ? n : nullptr;
-      sa_.tot1 = ad ? m : nullptr;
-      const int mxr = cap0 > cap1 ? cap0 : cap1;
-      EINX_PROF("lg_stop_kernel", st);
-      hipLaunchKernelGGL(lg_stop_kernel, dim3((unsigned)einx_cdiv(mxr, STOP_ROWS), (unsigned)(2 * B)), dim3(256), 0, st, sa_);
-      LG_CHECK(0);
-    }
-    if (ad && li < w->n_layers - 1) {  // after the stop decision (lightglue.py:632-652): a pair that has just stopped is not pruned
-      pa.layer = li;
-      pa.mw = es->heads[li].match_w;
-      pa.mb = es->heads[li].match_b;
-      pa.tw = decide ? es->heads[li].token_w : nullptr;
-      pa.tb = decide ? es->heads[li].token_b : nullptr;
-      const double thr = 0.8 + 0.1 * exp(-4.0 * li / w->n_layers);
-      pa.thr_t = (float)(thr < 0.0 ? 0.0 : thr > 1.0 ? 1.0 : thr);
-      const int mxr = cap0 > cap1 ? cap0 : cap1;
-      EINX_PROF("lg_prune (keep + scan + gather + copy back)", st);
-      hipLaunchKernelGGL(lg_keep_kernel, dim3((unsigned)einx_cdiv(mxr, STOP_ROWS), (unsigned)(2 * B)), dim3(256), 0, st, pa);
-      LG_CHECK(0);
-      hipLaunchKernelGGL(lg_prune_scan_kernel, dim3((unsigned)B), dim3(256), 0, st, pa);
-      LG_CHECK(0);
-      hipLaunchKernelGGL(lg_prune_gather_kernel, dim3((unsigned)einx_cdiv(mxr, 4), (unsigned)(2 * B)), dim3(256), 0, st, pa);
-      LG_CHECK(0);
-      const size_t quads = (size_t)mxr * ((D + 2 * dm.dh) / 4);
-      hipLaunchKernelGGL(lg_prune_copyback_kernel, dim3((unsigned)((quads + 255) / 256), (unsigned)(2 * B)), dim3(256), 0, st, pa);
-      LG_CHECK(0);
-    }
-  }
-  // ---- assignment ------------------------------------------------------------------------------
-  for (int sd = 0; sd < nrun; ++sd) {
-    Side& s = *asg[sd];
-    if (es) {  // route (a): one stage over every pair's own rows, each pair with the head it stopped at (x frozen since then)
-      LG_CHECK(gemm(st, EPI_DIV_HEAD, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, nullptr, nullptr, D, s.q, D, sqrtf(sqrtf((float)D)), ew.heads,
-                    stop, B, w->n_layers));
-      hipLaunchKernelGGL(lg_matchability_heads_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)Br), dim3(256), 0, st, s.x, s.cnt, s.cap, D,
-                         ew.heads, stop, B, (int)w->n_layers, s.cert, s.dust);
-      LG_CHECK(0);
-      continue;
-    }
-    LG_CHECK(gemm(st, EPI_DIV, s, Br, s.x, D, nullptr, 0, 0x7fffffff, D, w->proj_w, w->proj_b, D, s.q, D, sqrtf(sqrtf((float)D))));
-    hipLaunchKernelGGL(lg_matchability_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)Br), dim3(256), 0, st, s.x, s.cnt, s.cap, D, w->match_w,
-                       w->match_b, s.cert, s.dust);
-    LG_CHECK(0);
-  }
-  for (int sd = 0; sd < 2; ++sd) {
-    Side& s = *outs[sd];
-    float* ref = sd == 0 ? ref0 : ref1;
-    if (ref && !all_layers) {
-      const size_t per = (size_t)s.cap * D;
-      hipLaunchKernelGGL(lg_copy_rows_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)B), dim3(256), 0, st, s.x, ref, s.cnt, s.cap, D,
-                         per);
-      LG_CHECK(0);
-    }
-  }
-  a.d0 = s0.q;
-  a.d1 = s1.q;
-  a.n = ad ? ad->live : n;
-  a.m = ad ? ad->live + B : m;
-  a.cap0 = cap0;
-  a.cap1 = cap1;
-  a.D = D;
-  a.la = la;
-  a.cert0 = s0.cert;
-  a.cert1 = s1.cert;
-  a.dust0 = s0.dust;
-  a.dust1 = s1.dust;
-  if (hipMemsetAsync(a.rowkey, 0, (char*)a.rowstat - (char*)a.rowkey, st) != hipSuccess) {  // rowkey | colkey
-    einx_set_error("einx_lightglue: memset failed");
-    return EINX_ERR_LAUNCH;
-  }
-  const dim3 grid((unsigned)einx_cdiv(cap1, BN), (unsigned)einx_cdiv(cap0, BM), (unsigned)B);
-  const int mx = cap0 > cap1 ? cap0 : cap1;
-  EINX_PROF("lg_assignment (3 tile passes + lse + finalize)", st);
-  hipLaunchKernelGGL((mnn_tile_kernel<1, false>), grid, dim3(THREADS), 0, st, a);
-  LG_CHECK(0);
-  hipLaunchKernelGGL(mnn_lse_kernel, dim3((unsigned)einx_cdiv(mx + 1, 256), (unsigned)B), dim3(256), 0, st, a);
-  LG_CHECK(0);
-  if (la) hipLaunchKernelGGL((mnn_tile_kernel<6, true>), grid, dim3(THREADS), 0, st, a);  // arg-max + log_assignment write in one visit
-  else hipLaunchKernelGGL((mnn_tile_kernel<0, true>), grid, dim3(THREADS), 0, st, a);
-  LG_CHECK(0);
-  if (ad)
-    hipLaunchKernelGGL(lg_finalize_scatter_kernel, dim3((unsigned)B), dim3(256), 0, st, a.rowkey, a.colkey, ad->live, B, ad->kept0, ad->kept1, cap0,
-                       cap1, w->filter_threshold, matches0, matches1, scores0, scores1);
-  else
-    hipLaunchKernelGGL(lg_finalize_kernel, dim3((unsigned)einx_cdiv(mx, 256), (unsigned)B), dim3(256), 0, st, a.rowkey, a.colkey, n, m, cap0, cap1,
-                       w->filter_threshold, matches0, matches1, scores0, scores1);
-  LG_CHECK(0);
-#undef LG_CHECK
-  return EINX_OK;
+  return nullptr;
 }
 }  // namespace
 
@@ -1863,49 +1981,18 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
                 ref1, ref_layers, stream);
 }
 
-EINX_EXPORT size_t einx_lightglue_early_stop_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers) {
-  Dims dm;
-  if (B <= 0 || cap0 <= 0 || cap1 <= 0 || n_layers < 1 || n_layers > LG_MAX_HEADS || !dims_of(d, heads, dm)) return 0;
-  (void)input_dim;
-  Side s0, s1;
-  int32_t* cnt2;
-  MnnArgs a;
-  EsWs e;
-  WsCarver c{nullptr};
-  carve_es(c, s0, s1, cnt2, a, e, cap0 == cap1, B, cap0, cap1, d, dm.dh, n_layers);
-  return c.bytes;
-}
-
 EINX_EXPORT int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
                                           const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
                                           const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
                                           int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
                                           float* ref1, int32_t* stop, void* stream) {
   EINX_CHECK_ARG(w && heads && stop, "null pointer");
-  EINX_CHECK_ARG(head_size == sizeof(einx_lg_head), "head_size does not match this library's einx_lg_head (header / library ABI mismatch)");
-  EINX_CHECK_ARG(w->n_layers >= 1 && w->n_layers <= LG_MAX_HEADS, "early stopping takes 1..32 layers");
-  for (int i = 0; i < w->n_layers; ++i) {
-    const einx_lg_head& h = heads[i];
-    EINX_CHECK_ARG(h.proj_w && h.proj_b && h.match_w && h.match_b, "every layer needs its log_assignment head");
-    EINX_CHECK_ARG(i == w->n_layers - 1 || (h.token_w && h.token_b), "every layer but the last needs its token_confidence head");
-  }
+  const char* bad =
+      heads_error(w, heads, head_size, "early stopping takes 1..32 layers", nullptr, "every layer but the last needs its token_confidence head");
+  EINX_CHECK_ARG(!bad, bad);
   const EarlyStop es{heads, depth_confidence, stop, nullptr};
   return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
                 1, stream);
-}
-
-EINX_EXPORT size_t einx_lightglue_adaptive_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers) {
-  Dims dm;
-  if (B <= 0 || cap0 <= 0 || cap1 <= 0 || n_layers < 1 || n_layers > LG_MAX_HEADS || !dims_of(d, heads, dm)) return 0;
-  (void)input_dim;
-  Side s0, s1;
-  int32_t* cnt2;
-  MnnArgs a;
-  EsWs e;
-  AdWs p;
-  WsCarver c{nullptr};
-  carve_ad(c, s0, s1, cnt2, a, e, p, cap0 == cap1, B, cap0, cap1, d, dm.dh, n_layers);
-  return c.bytes;
 }
 
 EINX_EXPORT int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
@@ -1915,16 +2002,12 @@ EINX_EXPORT int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_
                                         float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
                                         int32_t* live, void* stream) {
   EINX_CHECK_ARG(w && heads && prune0 && prune1 && kept0 && kept1 && live, "null pointer");
-  EINX_CHECK_ARG(head_size == sizeof(einx_lg_head), "head_size does not match this library's einx_lg_head (header / library ABI mismatch)");
-  EINX_CHECK_ARG(w->n_layers >= 1 && w->n_layers <= LG_MAX_HEADS, "point pruning takes 1..32 layers");
-  EINX_CHECK_ARG(width_confidence > 0.0 && width_confidence <= 1.0, "width_confidence must be in (0, 1]");
-  EINX_CHECK_ARG(la == nullptr, "log_assignment is not produced with point pruning (DESIGN.md 8j): la must be null");
-  for (int i = 0; i < w->n_layers; ++i) {
-    const einx_lg_head& h = heads[i];
-    EINX_CHECK_ARG(h.proj_w && h.proj_b && h.match_w && h.match_b, "every layer needs its log_assignment head");
-    EINX_CHECK_ARG(depth_confidence <= 0.0f || i == w->n_layers - 1 || (h.token_w && h.token_b),
-                   "with depth_confidence > 0 every layer but the last needs its token_confidence head");
-  }
+  const char* own = nullptr;
+  if (la) own = "log_assignment is not produced with point pruning (DESIGN.md 8j): la must be null";
+  if (!(width_confidence > 0.0 && width_confidence <= 1.0)) own = "width_confidence must be in (0, 1]";
+  const char* token_msg = depth_confidence <= 0.0f ? nullptr : "with depth_confidence > 0 every layer but the last needs its token_confidence head";
+  const char* bad = heads_error(w, heads, head_size, "point pruning takes 1..32 layers", own, token_msg);
+  EINX_CHECK_ARG(!bad, bad);
   const Adaptive ad{(float)(1.0 - width_confidence), min_kpts, prune0, prune1, kept0, kept1, live};
   const EarlyStop es{heads, depth_confidence, stop, &ad};
   return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, nullptr, ref0,
@@ -2028,6 +2111,7 @@ EINX_EXPORT int einx_lg_assign_nll(const float* proj_w, const float* proj_b, con
   EINX_CHECK_ARG((pos0 != nullptr) != (assignment != nullptr), "give the positives as pos0 or as a dense assignment, not both");
   EINX_CHECK_ARG(B > 0 && cap0 > 0 && cap1 > 0 && d > 0 && d % 4 == 0, "bad shape (d must be a multiple of 4)");
   hipStream_t st = (hipStream_t)stream;
+  const char* const entry = __func__;
   NllWs w{};
   MnnArgs a{};
   WsCarver c{(char*)ws};
@@ -2037,50 +2121,24 @@ EINX_EXPORT int einx_lg_assign_nll(const float* proj_w, const float* proj_b, con
   w.s1.cnt = m;
   w.s1.cap = cap1;
   const float* x[2] = {x0, x1};
-  Side* sides[2] = {&w.s0, &w.s1};
-#define NLL_CHECK(expr)                                                       \
-  do {                                                                        \
-    if ((expr) != 0 || hipGetLastError() != hipSuccess) {                     \
-      einx_set_error("einx_lg_assign_nll: kernel launch failed at %s", #expr); \
-      return EINX_ERR_LAUNCH;                                                 \
-    }                                                                         \
-  } while (0)
-  NLL_CHECK(0);
+  const Side* sides[2] = {&w.s0, &w.s1};
+  LG_CHECK(entry, 0);
   for (int sd = 0; sd < 2; ++sd) {  // MatchAssignment (lightglue.py:365-377): final_proj / d^(1/4) and the matchability terms
-    Side& s = *sides[sd];
-    NLL_CHECK(gemm(st, EPI_DIV, s, B, x[sd], d, nullptr, 0, 0x7fffffff, d, proj_w, proj_b, d, s.q, d, sqrtf(sqrtf((float)d))));
-    hipLaunchKernelGGL(lg_matchability_kernel, dim3((unsigned)einx_cdiv(s.cap, 4), (unsigned)B), dim3(256), 0, st, x[sd], s.cnt, s.cap, d, match_w,
-                       match_b, s.cert, s.dust);
-    NLL_CHECK(0);
+    const Side& s = *sides[sd];
+    LG_CHECK(entry, gemm(st, EPI_DIV, s, B, x[sd], d, nullptr, 0, 0x7fffffff, d, proj_w, proj_b, d, s.q, d, sqrtf(sqrtf((float)d))));
+    launch_matchability(st, s, x[sd], B, d, match_w, match_b);
+    LG_CHECK(entry, 0);
   }
-  a.d0 = w.s0.q;
-  a.d1 = w.s1.q;
-  a.n = n;
-  a.m = m;
-  a.cap0 = cap0;
-  a.cap1 = cap1;
-  a.D = d;
-  a.la = nullptr;
-  a.cert0 = w.s0.cert;
-  a.cert1 = w.s1.cert;
-  a.dust0 = w.s0.dust;
-  a.dust1 = w.s1.dust;
   a.pos0 = pos0;
   a.assign = assignment;
   a.as_b = as_b;
   a.as_i = as_i;
   a.as_j = as_j;
-  const dim3 grid((unsigned)einx_cdiv(cap1, BN), (unsigned)einx_cdiv(cap0, BM), (unsigned)B);
-  const int mx = cap0 > cap1 ? cap0 : cap1;
   EINX_PROF("lg_assign_nll (2 tile passes + lse + finish)", st);
-  hipLaunchKernelGGL((mnn_tile_kernel<1, false>), grid, dim3(THREADS), 0, st, a);
-  NLL_CHECK(0);
-  hipLaunchKernelGGL(mnn_lse_kernel, dim3((unsigned)einx_cdiv(mx + 1, 256), (unsigned)B), dim3(256), 0, st, a);
-  NLL_CHECK(0);
-  hipLaunchKernelGGL((mnn_tile_kernel<7, true>), grid, dim3(THREADS), 0, st, a);
-  NLL_CHECK(0);
+  if (const int rc = assign_prologue(entry, st, a, w.s0, w.s1, n, m, B, d, nullptr)) return rc;
+  hipLaunchKernelGGL((mnn_tile_kernel<7, true>), assign_grid(a, B), dim3(THREADS), 0, st, a);
+  LG_CHECK(entry, 0);
   hipLaunchKernelGGL(lg_nll_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, a, gt_matches0, gt_matches1, out);
-  NLL_CHECK(0);
-#undef NLL_CHECK
+  LG_CHECK(entry, 0);
   return EINX_OK;
 }

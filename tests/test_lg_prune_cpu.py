@@ -229,3 +229,44 @@ def test_c_abi_argument_checks_and_size_queries():
         h.proj_w = h.proj_b = h.match_w = h.match_b = p
     assert rc(depth=0.5) == -1 and b"token_confidence" in L.einx_last_error()
     assert rc() == -1 and b"null pointer" in L.einx_last_error()  # heads complete: the shared body's own checks (kpts0 is null)
+
+
+# (B, cap0, cap1, d, heads, input_dim, n_layers) -> einx_lg_ws_bytes_heads, einx_lightglue_early_stop_ws_bytes,
+# einx_lightglue_adaptive_ws_bytes, recorded from the library BEFORE the three carve functions became one (callers allocate by these
+# figures, and the regions' offsets follow from the same walk): the shapes of the test above, unequal capacities both ways round,
+# a single keypoint, 2 heads with an input projection, 1 and 32 layers, a head width that is no power of two, one 256-wide head.
+WS_BYTES = {
+    (1, 5, 33, 256, 4, 256, 9): (335872, 337408, 338688),
+    (5, 130, 130, 256, 4, 256, 9): (11396608, 11398144, 11404544),
+    (64, 2048, 2048, 256, 4, 256, 9): (2389706240, 2389708032, 2390757632),
+    (3, 40, 48, 128, 2, 128, 3): (1229568, 1230848, 1232896),
+    (2, 130, 70, 256, 4, 256, 9): (3506176, 3507712, 3510528),
+    (2, 70, 130, 256, 4, 256, 9): (3506176, 3507712, 3510528),
+    (1, 1, 1, 256, 4, 256, 9): (21760, 23296, 24576),
+    (3, 130, 130, 128, 2, 64, 3): (3644672, 3645952, 3650304),
+    (2, 64, 64, 256, 4, 256, 1): (2239744, 2241024, 2242816),
+    (2, 64, 64, 256, 4, 256, 32): (2239744, 2241792, 2243584),
+    (2, 64, 48, 256, 4, 256, 1): (1960192, 1961472, 1963264),
+    (2, 64, 48, 256, 4, 256, 32): (1960192, 1962240, 1964032),
+    (2, 64, 64, 96, 3, 96, 4): (863488, 864768, 866560),
+    (1, 7, 7, 1024, 4, 1024, 2): (491776, 493056, 494336),
+}
+# every argument that makes all three queries return 0 ...
+WS_ZERO = ((0, 64, 64, 256, 4, 256, 9), (-1, 64, 64, 256, 4, 256, 9), (2, 0, 64, 256, 4, 256, 9), (2, 64, 0, 256, 4, 256, 9),
+           (2, 64, 64, 0, 4, 256, 9), (2, 64, 64, 256, 0, 256, 9), (2, 64, 64, 250, 4, 256, 9), (2, 64, 64, 256, 3, 256, 9),
+           (2, 64, 64, 2048, 4, 256, 9), (2, 64, 64, 24, 4, 24, 9))
+# ... and the layer counts that only the early-stop and adaptive queries refuse (the plain query takes no layer count)
+WS_ZERO_LAYERS = ((2, 64, 64, 256, 4, 256, 0), (2, 64, 64, 256, 4, 256, -1), (2, 64, 64, 256, 4, 256, 33))
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    def q(shape):
+        return (L.einx_lg_ws_bytes_heads(*shape[:6]), L.einx_lightglue_early_stop_ws_bytes(*shape), L.einx_lightglue_adaptive_ws_bytes(*shape))
+
+    for shape, want in WS_BYTES.items():
+        assert q(shape) == want, shape
+    for shape in WS_ZERO:
+        assert q(shape) == (0, 0, 0), shape
+    for shape in WS_ZERO_LAYERS:
+        assert q(shape) == (2239744, 0, 0), shape
+    assert q((2, 64, 64, 256, 4, 8, 9)) == q((2, 64, 64, 256, 4, 256, 9))  # input_dim is part of the ABI and of no region
