@@ -201,6 +201,11 @@ SIGNATURES = {
     "einx_lightglue_adaptive": (c_int, [ctypes.POINTER(LgWeights), ctypes.POINTER(LgHead), c_size_t, c_float, ctypes.c_double, c_int, c_void_p,
                                         c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float]
                                 + [c_void_p] * 15),
+    "einx_lightglue_flash_ws_bytes": (c_size_t, [c_int] * 7),
+    "einx_lightglue_flash": (c_int, [ctypes.POINTER(LgWeights), ctypes.POINTER(LgHead), c_size_t, c_float, ctypes.c_double, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float]
+                             + [c_void_p] * 8 + [c_int] + [c_void_p] * 7),
+    "einx_lg_attention_f16": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
     "einx_lg_assign_nll_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "einx_lg_assign_nll": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p,

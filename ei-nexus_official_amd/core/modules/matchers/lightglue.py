@@ -175,7 +175,12 @@ class LightGlue(nn.Module):
     (einx_lightglue_adaptive): after every non-final layer a side with more than `pruning_min_kpts(device)` rows
     drops the rows its matchability head calls unmatchable.  matches / scores stay in original indexing, prune0/1 hold the real
     counts, outputs gain kept0/1 (the survivors' original indices), ref_descriptors hold the survivors' rows, and
-    "log_assignment" is absent.  A side pruned to zero rows finishes its pair without matches (upstream raises there)."""
+    "log_assignment" is absent.  A side pruned to zero rows finishes its pair without matches (upstream raises there).
+
+    Half-precision attention.  `flash: True` is honoured as the reference honours it on a GPU (:206-230, :293-314): q, k, v of every
+    self and cross attention are rounded to binary16, the attention runs on the f16 matrix-core instruction with fp32 accumulation
+    and its context is rounded to binary16 again; everything else stays fp32 (einx_lightglue_flash).
+    `attention_mode` reads "fp16" then; the default `flash: False` runs the fp32 kernels, unchanged.  `mp` is not honoured."""
     default_conf = {
         "name": "lightglue", "input_dim": 256, "add_scale_ori": False, "descriptor_dim": 256, "n_layers": 9, "num_heads": 4,
         "flash": False, "mp": False, "depth_confidence": -1, "width_confidence": -1, "filter_threshold": 0.0,
@@ -252,9 +257,18 @@ class LightGlue(nn.Module):
         return bool(self.point_pruning) and not self.training and float(self.conf.width_confidence) > 0
 
     def pruning_min_kpts(self, device):
-        """the gate (lightglue.py:745-749): a side is pruned only while it has more rows than this.  `flash` is not honoured here,
-        so its entry is never chosen."""
-        return self.pruning_keypoint_thresholds[torch.device(device).type]
+        """the gate (lightglue.py:745-749): a side is pruned only while it has more rows than this; with conf.flash on a GPU the
+        "flash" entry, as the reference chooses"""
+        kind = torch.device(device).type
+        if self.conf.flash and kind == "cuda":
+            return self.pruning_keypoint_thresholds["flash"]
+        return self.pruning_keypoint_thresholds[kind]
+
+    @property
+    def attention_mode(self):
+        """ "fp16": conf.flash is set and every attention of a device forward rounds q, k, v and its context to binary16 and runs
+        on the f16 matrix-core instruction (einx_lightglue_flash); "fp32" (the default): the fp32 kernels"""
+        return "fp16" if self.conf.flash else "fp32"
 
     def get_pruning_mask(self, confidences, scores, layer_index):
         """which points stay (lightglue.py:723-730), in the float32 arithmetic of DESIGN.md 8j: the restatement of what the
@@ -374,7 +388,8 @@ class LightGlue(nn.Module):
         pr = None
         if self.point_pruning_active():
             pr = (self._pack()[3], float(self.conf.width_confidence), int(self.pruning_min_kpts(pb0.desc.device)))
-        r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers, early_stop=es, pruning=pr)
+        r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers, early_stop=es, pruning=pr,
+                        flash=bool(self.conf.flash))
         r.stale = stale
         return N.gather_matches(r, pb0.kpts, pb1.kpts, pb0.counts, 2)
 

@@ -1,4 +1,5 @@
-// lightglue.hip -- LightGlue inference on gfx950 (fp32 end to end, fp32 matrix cores).
+// lightglue.hip -- LightGlue inference on gfx950 (fp32 end to end, fp32 matrix cores; with the opt-in `flash: True` the attention
+// alone runs in fp16 on the f16 matrix-core instruction: lg_attn_f16_kernel).
 //
 // Per layer: SelfBlock (Wqkv GEMM -> rotary -> fused softmax(QK^T/8)V -> out_proj GEMM ->
 // concat-free FFN GEMM -> LayerNorm+GELU -> FFN GEMM + residual) on both sides, then CrossBlock
@@ -782,6 +783,203 @@ __global__ __launch_bounds__(512) void lg_attn16_kernel(const AttnArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// `flash: True` (reference lightglue.py:206-230, :293-314): the same fused attention with q, k, v rounded to binary16
+// (round to nearest even, v_cvt_f16_f32: what tensor.half() does, overflow -> inf), both products on v_mfma_f32_32x32x16_f16 with
+// fp32 accumulation, the context rounded to binary16 and widened again.  Same work split, tails and orientation as lg_attn_kernel
+// (one workgroup = 128 queries of one (pair, head), a wave = 32 queries, S^T = K Q^T with the query on the MFMA column, online
+// softmax in base 2 per lane); what differs:
+//   * Q / K / V are fp32 in memory and converted on the way in: Q into 8-element fp16 fragments in registers (k-step t of the first
+//     product = head dims 16 t + 8 (lane >> 5) + j), K / V into LDS as fp16, 64 keys per round (the bytes of 32 fp32 keys).
+//   * K rows [key][dim] with a pitch of HD + 8 halves: a lane's fragment is one 16-byte read, the pitch in words is 4 (mod 8), so
+//     the rows of 16 consecutive lanes start on 16 distinct 4-bank groups: conflict-free.
+//   * The 16 accumulator registers of S^T hold the keys (r & 3) + 8 (r >> 2) + 4 (lane >> 5); registers 8 s .. 8 s + 7, rounded to
+//     fp16, are the B fragment of k-step s of O^T = V^T P^T, whose element j then stands for key 16 s + 8 (j >> 2) + 4 (lane >> 5)
+//     + (j & 3) of the 32-key block.  CHOSEN: V is staged TRANSPOSED, Vt[dim][key], with the keys of a block stored in that order
+//     (position = key with bits 2 and 3 exchanged), so that V^T's A fragment is one 16-byte read as well -- no transposing read, no
+//     exchange of P between lanes.  Reads: pitch AKF + 8 halves = 36 words, 4 (mod 8): conflict-free like K.  Writes: a thread
+//     packs (key, key + 1) of one dim into a word, four words per float4 pair; a wave's 64 words of one store go to 16 dim rows x 4
+//     key pairs whose rows are 144 words apart (16 mod 64): 16 distinct banks, a 4-way conflict on 32 stores per round and
+//     workgroup (estimated at about 1 % of a round, not measured; the K store is 2-way on four banks).
+//   * The probabilities are summed in fp32 before they are rounded for the second product; o / l in fp32 (correctly rounded
+//     division), then binary16, then stored as fp32.
+// <64, 256>: 137 VGPRs, 18432 bytes of LDS, three workgroups per CU, no scratch in any instantiation (DESIGN.md 8k has the table).
+// Measured at 128 stacked entries of 1024 x 1024 keys: 252 us per launch against lg_attn_kernel's 1068 us (profiles/lg_flash_bench.txt).
+// ------------------------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+struct AttnF16Args : AttnArgs {
+  int ld;  // row stride of Q / K / V when the kernel's DD and LD are 0 (>= d, a multiple of 4)
+};
+
+constexpr int AKF = 64;  // keys staged per round
+template <int HD, int DD, int LD = 0>
+__global__ __launch_bounds__(256) void lg_attn_f16_kernel(const AttnF16Args a) {
+  constexpr int KP = HD + 8;   // halves per K row
+  constexpr int VP = AKF + 8;  // halves per Vt row
+  constexpr int DH = HD;       // (shadows the file-level constant)
+  __shared__ __attribute__((aligned(16))) _Float16 Ks[AKF * KP];
+  __shared__ __attribute__((aligned(16))) _Float16 Vt[DH * VP];
+  const int D = DD ? DD : a.d;
+  const int DL = LD ? LD : (DD ? DD : a.ld);  // row stride of Q / K / V
+  const int gx = (int)gridDim.x, gy = (int)gridDim.y;
+  int item = xcd_contiguous((int)(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z)), gx * gy * (int)gridDim.z);
+  const int qb = item % gx;
+  item /= gx;
+  const int h = item % gy, b = item / gy;
+  const int bk = a.kv_shift ? (b + a.kv_shift) % a.Btot : b;
+  const int nq = min(a.nq[b], a.capq), nk = min(a.nk[bk], a.capk);
+  const int q0 = qb * 128;
+  if (q0 >= nq || nk <= 0) return;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+  const int q = q0 + wave * 32 + l31;
+  const bool qv = q < nq;
+  const int dhr = DD ? DH : a.dh;  // the head's real width; dims dhr .. HD - 1 read as zero and are not stored
+  constexpr int KS = DH / 16;      // k-steps of the first product
+  f16x8 qf[KS];
+  {
+    const float* Qrow = a.Q + ((size_t)b * a.capq + (qv ? q : nq - 1)) * DL + h * dhr + 8 * half;
+#pragma unroll
+    for (int t = 0; t < KS; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int dim = 16 * t + 8 * half + 4 * u;
+        const f32x4 v = (DD || dim < dhr) ? *reinterpret_cast<const f32x4*>(Qrow + 16 * t + 4 * u) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) qf[t][4 * u + e] = (_Float16)v[e];
+      }
+  }
+  const float* Kb = a.K + (size_t)bk * a.capk * DL + h * dhr;
+  const float* Vb = a.V + (size_t)bk * a.capk * DL + h * dhr;
+  constexpr int OT = DH / 32;  // 32-wide blocks of the output row
+  f32x16 o[OT];
+#pragma unroll
+  for (int mt = 0; mt < OT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[mt][r] = 0.0f;
+  const float NEG = -einx_u2f(0x7f800000u);
+  const float sl2 = a.scale * 1.44269504088896341f;  // the 1/sqrt(dh) of SDPA on the fp32 product; softmax in base 2
+  float m_run = NEG, l_run = 0.0f;
+
+  // staging through registers, one round ahead.  K: float4 = 4 dims of one key.  V: the same float4 of keys 2 p and 2 p + 1
+  constexpr int R4 = DH / 4;             // float4 per K / V row
+  constexpr int KST = AKF * R4 / 256;    // K float4 per thread and round
+  constexpr int VST = KST / 2;           // V key pairs per thread and round
+  static_assert(VST >= 1 && DH % 32 == 0, "head dim 32, 64, 128 or 256");
+  f32x4 rk[KST], rv[VST][2];
+  auto issue = [&](int kb0) {
+#pragma unroll
+    for (int i = 0; i < KST; ++i) {
+      const int fidx = tid + i * 256;
+      const int row = fidx / R4, c4 = fidx % R4;
+      const int key = min(kb0 + row, nk - 1);  // clamped: rows past nk are masked after the first product
+      rk[i] = (DD || c4 * 4 < dhr) ? *reinterpret_cast<const f32x4*>(Kb + (size_t)key * DL + c4 * 4) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+#pragma unroll
+    for (int i = 0; i < VST; ++i) {
+      const int fidx = tid + i * 256;
+      const int kp = fidx / R4, c4 = fidx % R4;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int key = min(kb0 + 2 * kp + e, nk - 1);
+        rv[i][e] = (DD || c4 * 4 < dhr) ? *reinterpret_cast<const f32x4*>(Vb + (size_t)key * DL + c4 * 4) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      }
+    }
+  };
+  auto commit = [&]() {
+#pragma unroll
+    for (int i = 0; i < KST; ++i) {
+      const int fidx = tid + i * 256;
+      const int row = fidx / R4, c4 = fidx % R4;
+      const f16x4 v = {(_Float16)rk[i][0], (_Float16)rk[i][1], (_Float16)rk[i][2], (_Float16)rk[i][3]};
+      *reinterpret_cast<f16x4*>(Ks + row * KP + c4 * 4) = v;
+    }
+#pragma unroll
+    for (int i = 0; i < VST; ++i) {
+      const int fidx = tid + i * 256;
+      const int kp = fidx / R4, c4 = fidx % R4;
+      const int key = 2 * kp;  // position of a key in its Vt row: bits 2 and 3 exchanged (see above); key + 1 sits next to it
+      const int pos = (key & ~12) | ((key & 4) << 1) | ((key & 8) >> 1);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const f16x2 v = {(_Float16)rv[i][0][e], (_Float16)rv[i][1][e]};
+        *reinterpret_cast<f16x2*>(Vt + (c4 * 4 + e) * VP + pos) = v;
+      }
+    }
+  };
+  issue(0);
+  for (int kb0 = 0; kb0 < nk; kb0 += AKF) {
+    __syncthreads();
+    commit();
+    __syncthreads();
+    if (kb0 + AKF < nk) issue(kb0 + AKF);
+#pragma unroll
+    for (int sub = 0; sub < AKF / 32; ++sub) {
+      const int kbase = kb0 + sub * 32;
+      if (kbase >= nk) break;
+      f32x16 s;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = 0.0f;
+      const _Float16* krow = Ks + (sub * 32 + l31) * KP + 8 * half;
+#pragma unroll
+      for (int t = 0; t < KS; ++t) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(krow + 16 * t), qf[t], s, 0, 0, 0);
+      float mx = NEG;
+      if (kbase + 32 <= nk) {  // whole block (uniform): no key mask
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          s[r] = s[r] * sl2;
+          mx = fmaxf(mx, s[r]);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = kbase + crow(r, half);
+          s[r] = key < nk ? s[r] * sl2 : NEG;
+          mx = fmaxf(mx, s[r]);
+        }
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run, mx);
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);  // 2^(-inf) = 0: masked keys and the first block
+      float psum = 0.0f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s[r] = __builtin_amdgcn_exp2f(s[r] - m_new);
+        psum += s[r];
+      }
+      l_run = l_run * alpha + psum;
+      m_run = m_new;
+      if (__any(alpha != 1.0f)) {  // (wave-uniform; x * 1.0f == x)
+#pragma unroll
+        for (int mt = 0; mt < OT; ++mt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) o[mt][r] *= alpha;
+      }
+      const _Float16* vrow = Vt + l31 * VP + sub * 32 + 8 * half;
+#pragma unroll
+      for (int st = 0; st < 2; ++st) {
+        f16x8 pf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pf[j] = (_Float16)s[8 * st + j];
+#pragma unroll
+        for (int mt = 0; mt < OT; ++mt)
+          o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(vrow + 32 * mt * VP + 16 * st), pf, o[mt], 0, 0, 0);
+      }
+    }
+  }
+  const float l = l_run + __shfl_xor(l_run, 32, 64);
+  if (qv) {
+    float* orow = a.O + ((size_t)b * a.capq + q) * D + h * dhr;
+#pragma unroll
+    for (int mt = 0; mt < OT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (DD || mt * 32 + crow(r, half) < dhr) orow[mt * 32 + crow(r, half)] = (float)(_Float16)(o[mt][r] / l);
+  }
+}
+
 // LayerNorm(512, eps 1e-5, biased variance) + exact GELU, in place; one wave per token
 __global__ __launch_bounds__(256) void lg_ln_gelu_kernel(float* hbuf, const int32_t* cnt, int cap, const float* g, const float* be) {
   const int b = blockIdx.y;
@@ -1396,6 +1594,7 @@ int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx,
 // the model's widths, as the launchers need them
 struct Dims {
   int d, heads, dh;
+  bool flash = false;  // attention in fp16 on the matrix cores (conf.flash)
   bool shipped() const { return d == D && dh == DH; }
 };
 
@@ -1440,6 +1639,22 @@ int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const fl
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// conf.flash: one kernel for every grid size (no fp16 twin of lg_attn16_kernel); ld: row stride of Q / K / V
+int attn_f16(hipStream_t st, dim3 grid, const Dims& dm, const AttnArgs& base, int ld) {
+  AttnF16Args a;
+  static_cast<AttnArgs&>(a) = base;
+  a.ld = ld;
+  EINX_PROF("lg_attn_f16_kernel", st);
+  if (dm.shipped() && ld == 2 * D) hipLaunchKernelGGL((lg_attn_f16_kernel<64, D, 2 * D>), grid, dim3(256), 0, st, a);
+  else if (dm.shipped() && ld == D) hipLaunchKernelGGL((lg_attn_f16_kernel<64, D>), grid, dim3(256), 0, st, a);
+  else if (dm.dh <= 32) hipLaunchKernelGGL((lg_attn_f16_kernel<32, 0>), grid, dim3(256), 0, st, a);  // (narrower heads: zero padded)
+  else if (dm.dh <= 64) hipLaunchKernelGGL((lg_attn_f16_kernel<64, 0>), grid, dim3(256), 0, st, a);
+  else if (dm.dh <= 128) hipLaunchKernelGGL((lg_attn_f16_kernel<128, 0>), grid, dim3(256), 0, st, a);
+  else if (dm.dh <= 256) hipLaunchKernelGGL((lg_attn_f16_kernel<256, 0>), grid, dim3(256), 0, st, a);
+  else return -1;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // merged: Q, K, V are column blocks of a [.., 2 d] buffer (row stride 512; shipped widths only)
 int attn(hipStream_t st, int B, const Dims& dm, const float* Q, const int32_t* nq, int capq, const float* K, const float* V, const int32_t* nk,
          int capk, float* O, int kv_shift = 0, bool merged = false) {
@@ -1458,6 +1673,7 @@ int attn(hipStream_t st, int B, const Dims& dm, const float* Q, const int32_t* n
   a.dh = dm.dh;
   a.scale = 1.0f / sqrtf((float)dm.dh);  // SDPA scale (self) = (dh^-1/4)^2 (cross, lightglue.py:316); 64-wide heads: exactly 0.125
   const dim3 grid((unsigned)einx_cdiv(capq, 128), (unsigned)dm.heads, (unsigned)B);
+  if (dm.flash) return attn_f16(st, grid, dm, a, merged ? 2 * dm.d : dm.d);
   EINX_PROF("lg_attn_kernel", st);
   // the latency form (same bits) while ITS grid fits the chip twice: fewer wide workgroups than CUs alone is not enough -- three
   // pairs of 1024 keypoints (768 latency-form workgroups of eight waves, 1.5 rounds) ran 3.67 instead of 3.26 ms; one pair
@@ -1901,7 +2117,7 @@ int lg_assign(const LgCtx& c) {
   return EINX_OK;
 }
 
-int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
+int lg_run(const einx_lg_weights* w, const EarlyStop* es, bool flash, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
            const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws, int64_t* matches0,
            int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0, float* ref1, int ref_layers, void* stream) {
   EINX_CHECK_ARG(w && kpts0 && desc0 && n && kpts1 && desc1 && m && ws && matches0 && matches1 && scores0 && scores1, "null pointer");
@@ -1918,6 +2134,7 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, const float* kpts0, co
   c.st = (hipStream_t)stream;
   c.w = w;
   c.dm = dm;
+  c.dm.flash = flash;
   c.sh = {B, cap0, cap1, dm.d, dm.dh, w->n_layers};
   c.es = es;
   if (es) c.ad = es->ad;
@@ -1977,22 +2194,61 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
                                const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
                                float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
                                float* ref0, float* ref1, int ref_layers, void* stream) {
-  return lg_run(w, nullptr, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
+  return lg_run(w, nullptr, false, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
                 ref1, ref_layers, stream);
 }
+
+namespace {
+// the bodies of the early-stop and adaptive entries; entry: the exported function an argument error is reported under; flash: the
+// attention of einx_lightglue_flash
+#define LG_CHECK_ARG(cond, msg)                \
+  do {                                         \
+    if (!(cond)) {                             \
+      einx_set_error("%s: %s", entry, msg);    \
+      return EINX_ERR_ARG;                     \
+    }                                          \
+  } while (0)
+int lg_early_stop(const char* entry, bool flash, const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                                          const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
+                                          const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
+                                          int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
+                                          float* ref1, int32_t* stop, void* stream) {
+  LG_CHECK_ARG(w && heads && stop, "null pointer");
+  const char* bad =
+      heads_error(w, heads, head_size, "early stopping takes 1..32 layers", nullptr, "every layer but the last needs its token_confidence head");
+  LG_CHECK_ARG(!bad, bad);
+  const EarlyStop es{heads, depth_confidence, stop, nullptr};
+  return lg_run(w, &es, flash, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
+                1, stream);
+}
+
+int lg_adaptive(const char* entry, bool flash, const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                                        double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                                        const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
+                                        float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
+                                        float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
+                                        int32_t* live, void* stream) {
+  LG_CHECK_ARG(w && heads && prune0 && prune1 && kept0 && kept1 && live, "null pointer");
+  const char* own = nullptr;
+  if (la) own = "log_assignment is not produced with point pruning (DESIGN.md 8j): la must be null";
+  if (!(width_confidence > 0.0 && width_confidence <= 1.0)) own = "width_confidence must be in (0, 1]";
+  const char* token_msg = depth_confidence <= 0.0f ? nullptr : "with depth_confidence > 0 every layer but the last needs its token_confidence head";
+  const char* bad = heads_error(w, heads, head_size, "point pruning takes 1..32 layers", own, token_msg);
+  LG_CHECK_ARG(!bad, bad);
+  const Adaptive ad{(float)(1.0 - width_confidence), min_kpts, prune0, prune1, kept0, kept1, live};
+  const EarlyStop es{heads, depth_confidence, stop, &ad};
+  return lg_run(w, &es, flash, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, nullptr, ref0,
+                ref1, 1, stream);
+}
+}  // namespace
 
 EINX_EXPORT int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
                                           const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
                                           const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
                                           int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
                                           float* ref1, int32_t* stop, void* stream) {
-  EINX_CHECK_ARG(w && heads && stop, "null pointer");
-  const char* bad =
-      heads_error(w, heads, head_size, "early stopping takes 1..32 layers", nullptr, "every layer but the last needs its token_confidence head");
-  EINX_CHECK_ARG(!bad, bad);
-  const EarlyStop es{heads, depth_confidence, stop, nullptr};
-  return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
-                1, stream);
+  return lg_early_stop(__func__, false, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0,
+                       matches1, scores0, scores1, la, ref0, ref1, stop, stream);
 }
 
 EINX_EXPORT int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
@@ -2001,17 +2257,60 @@ EINX_EXPORT int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_
                                         float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
                                         float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
                                         int32_t* live, void* stream) {
-  EINX_CHECK_ARG(w && heads && prune0 && prune1 && kept0 && kept1 && live, "null pointer");
-  const char* own = nullptr;
-  if (la) own = "log_assignment is not produced with point pruning (DESIGN.md 8j): la must be null";
-  if (!(width_confidence > 0.0 && width_confidence <= 1.0)) own = "width_confidence must be in (0, 1]";
-  const char* token_msg = depth_confidence <= 0.0f ? nullptr : "with depth_confidence > 0 every layer but the last needs its token_confidence head";
-  const char* bad = heads_error(w, heads, head_size, "point pruning takes 1..32 layers", own, token_msg);
-  EINX_CHECK_ARG(!bad, bad);
-  const Adaptive ad{(float)(1.0 - width_confidence), min_kpts, prune0, prune1, kept0, kept1, live};
-  const EarlyStop es{heads, depth_confidence, stop, &ad};
-  return lg_run(w, &es, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, nullptr, ref0,
-                ref1, 1, stream);
+  return lg_adaptive(__func__, false, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0,
+                     w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1, stop, prune0, prune1, kept0, kept1, live, stream);
+}
+
+// conf.flash: the three runs above with every attention in fp16 on the matrix cores.  width_confidence > 0: the
+// adaptive run; else depth_confidence > 0: the early-stop run; else the plain run (heads, stop and the pruning outputs unread).
+EINX_EXPORT size_t einx_lightglue_flash_ws_bytes(int B, int cap0, int cap1, int d, int heads, int, int n_layers) {
+  // the kernel needs no region of its own: the largest carve of the three runs; a layer count only the plain run takes: its carve
+  const size_t adaptive = lg_ws_bytes(LG_ADAPTIVE, B, cap0, cap1, d, heads, n_layers);
+  return adaptive ? adaptive : lg_ws_bytes(LG_PLAIN, B, cap0, cap1, d, heads, 0);
+}
+
+EINX_EXPORT int einx_lightglue_flash(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                                     double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                                     const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
+                                     float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
+                                     float* ref0, float* ref1, int ref_layers, int32_t* stop, float* prune0, float* prune1, int64_t* kept0,
+                                     int64_t* kept1, int32_t* live, void* stream) {
+  if (width_confidence > 0.0) {
+    EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1, "point pruning returns the surviving rows, not every layer's: ref_layers must be 0 or 1");
+    return lg_adaptive(__func__, true, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0,
+                       w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1, stop, prune0, prune1, kept0, kept1, live, stream);
+  }
+  if (depth_confidence > 0.0f) {
+    EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1, "early stopping returns the rows the stopping head read: ref_layers must be 0 or 1");
+    return lg_early_stop(__func__, true, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0,
+                         matches1, scores0, scores1, la, ref0, ref1, stop, stream);
+  }
+  return lg_run(w, nullptr, true, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
+                ref1, ref_layers, stream);
+}
+
+// The attention of conf.flash alone (a test hook): O[b, q, h dh ..] = RN16(softmax_j(RN16(Q_h[q]) . RN16(K_h[j]) / sqrt(dh)) RN16(V_h[j]))
+// for the first nq[b] rows of entry b over the first nk[bk] keys of entry bk = (b + kv_shift) mod B.  Q / K / V: fp32 [B, cap, ld]
+// (the heads' columns start at 0; ld >= heads * dh, a multiple of 4), O: fp32 [B, capq, heads * dh]; rows past nq are not written.
+EINX_EXPORT int einx_lg_attention_f16(const float* Q, const float* K, const float* V, float* O, const int32_t* nq, const int32_t* nk, int capq,
+                                      int capk, int B, int heads, int dh, int ld, int kv_shift, void* stream) {
+  EINX_CHECK_ARG(Q && K && V && O && nq && nk, "null pointer");
+  EINX_CHECK_ARG(B > 0 && capq > 0 && capk > 0, "bad shape");
+  Dims dm;
+  EINX_CHECK_ARG(heads > 0 && dh > 0 && dims_of(heads * dh, heads, dm), "head_dim must be a multiple of 4, at most 256");
+  EINX_CHECK_ARG(ld >= dm.d && ld % 4 == 0, "ld must be a multiple of 4, at least heads x head_dim");
+  EINX_CHECK_ARG(kv_shift >= 0 && kv_shift < B, "kv_shift must be in [0, B)");
+  AttnArgs a;
+  a.Q = Q, a.K = K, a.V = V, a.O = O, a.nq = nq, a.nk = nk;
+  a.capq = capq, a.capk = capk;
+  a.scale = 1.0f / sqrtf((float)dm.dh);
+  a.kv_shift = kv_shift, a.Btot = B, a.d = dm.d, a.dh = dm.dh;
+  const dim3 grid((unsigned)einx_cdiv(capq, 128), (unsigned)dm.heads, (unsigned)B);
+  if (attn_f16((hipStream_t)stream, grid, dm, a, ld) != 0) {
+    einx_set_error("einx_lg_attention_f16: kernel launch failed");
+    return EINX_ERR_LAUNCH;
+  }
+  return EINX_OK;
 }
 
 // ------------------------------------------------------------------------------------------

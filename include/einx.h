@@ -389,6 +389,32 @@ int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_head* heads,
                             float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
                             int32_t* live, void* stream);
 
+/* LightGlue's `flash: True` (lightglue.py:206-230, :293-314): the three runs above with every attention, self and
+ * cross, in half precision on the matrix cores.  Per (pair, head): q, k, v are rounded to IEEE binary16 (round to nearest even,
+ * overflow to infinity; q and k after the rotary step, the cross block's qk unscaled), softmax(q . k^T / sqrt(head_dim)) v is
+ * accumulated in fp32 (probabilities rounded to binary16 before the second product), and the context is rounded to binary16 and
+ * widened to fp32.  Projections, FFN, heads and every decision stay fp32.  The entries above are unchanged and never take this path.
+ * The argument list is einx_lightglue_adaptive's plus ref_layers (as in einx_lightglue):
+ *   width_confidence > 0: einx_lightglue_adaptive's run and rules (la NULL, ref_layers 0 / 1);
+ *   else depth_confidence > 0: einx_lightglue_early_stop's (stop required, ref_layers 0 / 1; prune0 .. live unread);
+ *   else: einx_lightglue's (heads, stop, prune0 .. live unread and may be NULL).
+ * ws: einx_lightglue_flash_ws_bytes(...) bytes = einx_lightglue_adaptive_ws_bytes(...): the kernel needs no region of its own (for
+ * a layer count that only the plain run takes, more than 32: einx_lg_ws_bytes_heads(...); 0 = unsupported widths). */
+size_t einx_lightglue_flash_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers);
+int einx_lightglue_flash(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                         double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                         const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
+                         float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
+                         float* ref0, float* ref1, int ref_layers, int32_t* stop, float* prune0, float* prune1, int64_t* kept0,
+                         int64_t* kept1, int32_t* live, void* stream);
+
+/* The attention of einx_lightglue_flash alone (a test hook).  Q / K / V: fp32 [B,cap,ld], head h in columns h dh .. (h + 1) dh - 1
+ * (ld >= heads * dh, a multiple of 4; dh a multiple of 4, at most 256); O: fp32 [B,capq,heads * dh].  Entry b: its first
+ * min(nq[b], capq) query rows over the first min(nk[bk], capk) keys of entry bk = (b + kv_shift) mod B; rows past nq[b], and every
+ * row of an entry without queries or keys, are not written.  Every value written is binary16-representable. */
+int einx_lg_attention_f16(const float* Q, const float* K, const float* V, float* O, const int32_t* nq, const int32_t* nk, int capq, int capk,
+                          int B, int heads, int dh, int ld, int kv_shift, void* stream);
+
 /* Assignment NLL of ONE MatchAssignment head (lightglue.py:66-133 NLLLoss / weight_loss, :751-769 LightGlue.loss in eval mode): the
  * sums behind nll_pos / nll_neg / row_norm, without a log_assignment matrix or any other B x n x m buffer.
  * proj_w [d,d], proj_b [d]: the head's final_proj; match_w [d], match_b [1]: its matchability; d a multiple of 4.
