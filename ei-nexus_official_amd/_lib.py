@@ -74,7 +74,8 @@ class EventArrays(ctypes.Structure):
 
 class LgLayer(ctypes.Structure):
     _names = ("Wqkv", "bqkv", "Wo", "bo", "sf0_w", "sf0_b", "sln_g", "sln_b", "sf3_w", "sf3_b",
-              "Wqk", "bqk", "Wv", "bv", "Wco", "bco", "cf0_w", "cf0_b", "cln_g", "cln_b", "cf3_w", "cf3_b", "Wqk_v", "bqk_v")
+              "Wqk", "bqk", "Wv", "bv", "Wco", "bco", "cf0_w", "cf0_b", "cln_g", "cln_b", "cf3_w", "cf3_b", "Wqk_v", "bqk_v",
+              "Wqkv_h", "Wo_h", "sf0_h", "sf3_h", "Wqk_h", "Wv_h", "Wco_h", "cf0_h", "cf3_h", "Wqk_v_h")  # *_h: binary16 images (conf.mp)
     _fields_ = [(n, c_void_p) for n in _names]
 
 
@@ -206,6 +207,12 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float]
                              + [c_void_p] * 8 + [c_int] + [c_void_p] * 7),
     "einx_lg_attention_f16": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
+    "einx_lightglue_mp_ws_bytes": (c_size_t, [c_int] * 7),
+    "einx_lightglue_mp": (c_int, [ctypes.POINTER(LgWeights), ctypes.POINTER(LgHead), c_size_t, c_float, ctypes.c_double, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float, c_float]
+                          + [c_void_p] * 8 + [c_int] + [c_void_p] * 6 + [c_int, c_void_p]),
+    "einx_lg_linear_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                   c_int, c_void_p]),
     "einx_lg_assign_nll_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "einx_lg_assign_nll": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p,

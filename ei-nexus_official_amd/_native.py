@@ -402,14 +402,19 @@ def compact_matches(r):
     return r
 
 
-def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False, early_stop=None, pruning=None, flash=False):
+LG_ATTN_F16, LG_LIN_F16 = 1, 2  # the mode bits of einx_lightglue_mp (einx.h: EINX_LG_ATTN_F16, EINX_LG_LIN_F16)
+
+
+def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False, early_stop=None, pruning=None, flash=False, mp=False):
     """weights: _lib.LgWeights; pb0/pb1: PairBatch (kpts [B,cap,3], desc [B,cap,Din], counts).
     all_layers: ref0/ref1 are [B,n_layers,cap,d] (training-mode ref_descriptors) instead of [B,cap,d].
     early_stop = (heads, depth_confidence): einx_lightglue_early_stop with the _lib.LgHead array of every layer's heads; r.stop
     [B] int32 is the number of layers each pair ran.
     pruning = (heads, width_confidence, min_kpts): einx_lightglue_adaptive, with `early_stop` or without; r.prune0/1,
     r.kept0/1 and r.live are set, r.la is None whatever want_la says, ref0 / ref1 hold the survivors' rows (zeros behind them).
-    flash: the same run through einx_lightglue_flash, every attention in fp16 on the matrix cores."""
+    flash: the same run through einx_lightglue_flash, every attention in fp16 on the matrix cores.
+    mp: the same run through einx_lightglue_mp, the layers' linears in fp16 on the matrix cores, with `flash` or
+    without; `weights` must then be the unfolded pack with the binary16 images (LightGlue._pack(mp=True))."""
     _dev_check(pb0.kpts, pb0.desc, pb1.kpts, pb1.desc)
     _dev_check(pb0.counts, pb1.counts, dt=I32)
     B, cap0, cap1 = pb0.B, pb0.cap, pb1.cap
@@ -431,7 +436,9 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False,
         nbytes = L.einx_lg_ws_bytes_heads(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim))
     if not nbytes:
         raise NotImplementedError("einx LightGlue: descriptor_dim must be num_heads x head_dim with head_dim a multiple of 4, at most 256")
-    if flash and nbytes:
+    if mp:
+        nbytes = L.einx_lightglue_mp_ws_bytes(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim), int(weights.n_layers))
+    elif flash:
         nbytes = L.einx_lightglue_flash_ws_bytes(B, cap0, cap1, d, int(weights.heads), int(weights.input_dim), int(weights.n_layers))
     ws = _workspace(nbytes, dev)
     r = MatchResult()
@@ -451,12 +458,16 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False,
     ref_layers = nl if (want_ref and all_layers) else 1
 
     def flash_call(heads, depth, width, min_kpts):
-        check(L.einx_lightglue_flash(ctypes.byref(weights), heads, ctypes.sizeof(_lib.LgHead), float(depth), float(width), int(min_kpts),
-                                     _ptr(pb0.kpts), _ptr(pb0.desc), _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc), _ptr(pb1.counts),
-                                     cap1, B, float(h0), float(w0), float(h1), float(w1), _ptr(ws), _ptr(r.matches0), _ptr(r.matches1),
-                                     _ptr(r.scores0), _ptr(r.scores1), _ptr(r.la), _ptr(r.ref0), _ptr(r.ref1), ref_layers, _ptr(r.stop),
-                                     _ptr(r.prune0), _ptr(r.prune1), _ptr(r.kept0), _ptr(r.kept1), _ptr(r.live), _stream(pb0.desc)),
-              "einx_lightglue_flash")
+        """einx_lightglue_flash, or with `mp` einx_lightglue_mp: one argument list, the mode bits before the stream"""
+        args = (ctypes.byref(weights), heads, ctypes.sizeof(_lib.LgHead), float(depth), float(width), int(min_kpts),
+                _ptr(pb0.kpts), _ptr(pb0.desc), _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc), _ptr(pb1.counts),
+                cap1, B, float(h0), float(w0), float(h1), float(w1), _ptr(ws), _ptr(r.matches0), _ptr(r.matches1),
+                _ptr(r.scores0), _ptr(r.scores1), _ptr(r.la), _ptr(r.ref0), _ptr(r.ref1), ref_layers, _ptr(r.stop),
+                _ptr(r.prune0), _ptr(r.prune1), _ptr(r.kept0), _ptr(r.kept1), _ptr(r.live))
+        if mp:
+            check(L.einx_lightglue_mp(*args, LG_LIN_F16 | (LG_ATTN_F16 if flash else 0), _stream(pb0.desc)), "einx_lightglue_mp")
+        else:
+            check(L.einx_lightglue_flash(*args, _stream(pb0.desc)), "einx_lightglue_flash")
         return r
 
     if pruning is not None:
@@ -472,7 +483,7 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False,
         r.kept0 = torch.empty((B, cap0), dtype=I64, device=dev)
         r.kept1 = torch.empty((B, cap1), dtype=I64, device=dev)
         r.live = torch.empty((2 * B,), dtype=I32, device=dev)
-        if flash:
+        if flash or mp:
             return flash_call(heads, depth, width, min_kpts)
         check(L.einx_lightglue_adaptive(ctypes.byref(weights), heads, ctypes.sizeof(heads._type_), depth, float(width), int(min_kpts),
                                         _ptr(pb0.kpts), _ptr(pb0.desc), _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc), _ptr(pb1.counts),
@@ -484,7 +495,7 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False,
     if early_stop is not None:
         heads, depth = early_stop
         r.stop = torch.empty((B,), dtype=torch.int32, device=dev)
-        if flash:
+        if flash or mp:
             return flash_call(heads, depth, -1.0, 0)
         check(L.einx_lightglue_early_stop(ctypes.byref(weights), heads, ctypes.sizeof(heads._type_), float(depth), _ptr(pb0.kpts), _ptr(pb0.desc),
                                           _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc), _ptr(pb1.counts), cap1, B, float(h0), float(w0),
@@ -492,7 +503,7 @@ def lightglue(weights, pb0, pb1, want_la=True, want_ref=False, all_layers=False,
                                           _ptr(r.la), _ptr(r.ref0), _ptr(r.ref1), _ptr(r.stop), _stream(pb0.desc)),
               "einx_lightglue_early_stop")
         return r
-    if flash:
+    if flash or mp:
         return flash_call(None, -1.0, -1.0, 0)
     check(L.einx_lightglue(ctypes.byref(weights), _ptr(pb0.kpts), _ptr(pb0.desc), _ptr(pb0.counts), cap0, _ptr(pb1.kpts), _ptr(pb1.desc),
                            _ptr(pb1.counts), cap1, B, float(h0), float(w0), float(h1), float(w1), _ptr(ws), _ptr(r.matches0),

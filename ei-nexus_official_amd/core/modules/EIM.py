@@ -335,7 +335,8 @@ class EIM(nn.Module):
             + (repr(getattr(getattr(m, "conf", None), "filter_threshold", None)),) \
             + (repr(getattr(m, "early_stop", None)), repr(getattr(getattr(m, "conf", None), "depth_confidence", None))) \
             + (repr(getattr(m, "point_pruning", None)), repr(getattr(getattr(m, "conf", None), "width_confidence", None)),
-               repr(getattr(m, "pruning_keypoint_thresholds", None)), repr(getattr(m, "attention_mode", None)))  # baked into a capture
+               repr(getattr(m, "pruning_keypoint_thresholds", None)), repr(getattr(m, "attention_mode", None)),
+               repr(getattr(m, "linear_mode", None)))  # baked into a capture
         return (ext(self.event_extractor.extractor), ext(self.image_extractor.extractor), mk, bool(getattr(self, "overlap_extractors", True)))
 
     @on_input_device

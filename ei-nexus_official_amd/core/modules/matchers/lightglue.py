@@ -180,7 +180,16 @@ class LightGlue(nn.Module):
     Half-precision attention.  `flash: True` is honoured as the reference honours it on a GPU (:206-230, :293-314): q, k, v of every
     self and cross attention are rounded to binary16, the attention runs on the f16 matrix-core instruction with fp32 accumulation
     and its context is rounded to binary16 again; everything else stays fp32 (einx_lightglue_flash).
-    `attention_mode` reads "fp16" then; the default `flash: False` runs the fp32 kernels, unchanged.  `mp` is not honoured."""
+    `attention_mode` reads "fp16" then; the default `flash: False` runs the fp32 kernels, unchanged.
+
+    Half-precision linears.  The reference declares `mp` (:430) and its forward never reads it: upstream's
+    torch.autocast(enabled=conf.mp) is gone, only `if torch.is_autocast_enabled(): desc0 = desc0.half()` is left (:568-570).  This
+    class does the same by default.  `mixed_precision = True` (with conf.mp true, in eval mode, on a GPU) runs the nine nn.Linear of
+    every transformer layer on the f16 matrix-core instruction (einx_lightglue_mp): inputs and weights rounded to
+    binary16, products accumulated in fp32, fp32 bias, fp32 result.  Unlike autocast no output is rounded and the residual stream
+    stays fp32; input_proj, rotary, LayerNorm, GELU, the heads, every decision and (unless `flash`) the attention stay fp32.  The
+    weights are then packed without the out_proj / to_out fold, whatever `fold_message_projection` says, so that each weight is
+    rounded as written.  `linear_mode` reads "fp16" then.  Independent of `flash`, early stopping and point pruning."""
     default_conf = {
         "name": "lightglue", "input_dim": 256, "add_scale_ori": False, "descriptor_dim": 256, "n_layers": 9, "num_heads": 4,
         "flash": False, "mp": False, "depth_confidence": -1, "width_confidence": -1, "filter_threshold": 0.0,
@@ -221,21 +230,22 @@ class LightGlue(nn.Module):
         self.confidence_thresholds = [self.confidence_threshold(i) for i in range(conf.n_layers)]
         self.early_stop = False  # opt-in: the reference ignores depth_confidence (see the class docstring)
         self.point_pruning = False  # opt-in: the reference ignores width_confidence (see the class docstring)
+        self.mixed_precision = False  # opt-in: the reference ignores mp (see the class docstring)
         # what the reference's pruning_min_kpts reads and never creates (:745-749): upstream LightGlue's published values, quoted
         # (upstream is not at hand to check them against).  A side is pruned only while it has MORE rows than this.
         self.pruning_keypoint_thresholds = {"cpu": -1, "mps": -1, "cuda": 1024, "flash": 1536}
-        self._packed = None
+        self._packed = self._packed_mp = self._watch = None
         self._sig = None
         self._sig_tensors = None
         # also reached when a parent module's load_state_dict recurses into this one
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.refresh())
 
     def _apply(self, fn, *a, **k):
-        self._packed = self._sig_tensors = None
+        self._packed = self._packed_mp = self._watch = self._sig_tensors = None
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
-        self._packed = self._sig_tensors = None
+        self._packed = self._packed_mp = self._watch = self._sig_tensors = None
         return super().load_state_dict(*a, **k)
 
     def confidence_threshold(self, layer_index):
@@ -270,6 +280,21 @@ class LightGlue(nn.Module):
         on the f16 matrix-core instruction (einx_lightglue_flash); "fp32" (the default): the fp32 kernels"""
         return "fp16" if self.conf.flash else "fp32"
 
+    def mixed_precision_active(self):
+        """whether the next forward runs the layers' linears in fp16: the attribute, conf.mp (read at every call, like
+        depth_confidence), eval mode, and the parameters on a GPU (the kernels take inputs and parameters on one HIP device, so
+        that is where the inputs are); a model on the CPU reports "fp32"."""
+        if not (bool(self.mixed_precision) and not self.training and bool(self.conf.mp)):
+            return False
+        return self.posenc.Wr.weight.device.type == "cuda"
+
+    @property
+    def linear_mode(self):
+        """ "fp16": `mixed_precision` and conf.mp are set and the nine linears of every layer of an eval-mode device forward round
+        their inputs and weights to binary16 and run on the f16 matrix-core instruction with fp32 accumulation (einx_lightglue_mp,
+        DESIGN.md 8l); "fp32" (the default): the fp32 kernels"""
+        return "fp16" if self.mixed_precision_active() else "fp32"
+
     def get_pruning_mask(self, confidences, scores, layer_index):
         """which points stay (lightglue.py:723-730), in the float32 arithmetic of DESIGN.md 8j: the restatement of what the
         device decides, on tensors of sigmoid outputs"""
@@ -281,17 +306,20 @@ class LightGlue(nn.Module):
     def refresh(self):
         """Drop the packed / folded weight images.  REQUIRED after edits through `p.data` (an alias with its own version
         counter: `p._version`, which `_pack` keys on, does not move) or after replacing Parameter objects."""
-        self._packed = self._sig_tensors = None
+        self._packed = self._packed_mp = self._watch = self._sig_tensors = None
 
-    def _pack(self):
-        """ctypes image of the parameter pointers (weights stay in their nn.Parameter storage)."""
+    def _pack(self, mp=False):
+        """ctypes image of the parameter pointers (weights stay in their nn.Parameter storage).  mp: the image einx_lightglue_mp
+        reads under EINX_LG_LIN_F16 -- no out_proj / to_out fold, and the binary16 image `w.half()` of each layer's nine weights
+        (DESIGN.md 8l); kept beside the fp32 image and dropped with it."""
         if self._sig_tensors is None:
             self._sig_tensors = list(self.parameters())
         sig = tuple((t.data_ptr(), t._version) for t in self._sig_tensors)
         if sig != self._sig:  # in-place parameter edits and moves drop the folded weight images too
-            self._packed, self._sig = None, sig
-        if self._packed is not None:
-            return self._packed
+            self._packed, self._packed_mp, self._watch, self._sig = None, None, None, sig
+        cached = self._packed_mp if mp else self._packed
+        if cached is not None:
+            return cached
         c = self.conf
         keep = []
 
@@ -299,6 +327,12 @@ class LightGlue(nn.Module):
             t = t.detach()
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda":
                 raise RuntimeError("einx LightGlue: parameters must be contiguous fp32 tensors on a HIP device")
+            keep.append(t)
+            return t.data_ptr()
+
+        def half(t):
+            """the contract's rounding of a weight: IEEE binary16, round to nearest even (made once, on the device)"""
+            t = t.detach().half().contiguous()
             keep.append(t)
             return t.data_ptr()
 
@@ -326,7 +360,12 @@ class LightGlue(nn.Module):
                 L.bqk_v = p(torch.cat([x.to_qk.bias.detach(), x.to_v.bias.detach()], 0).contiguous())
             else:
                 L.Wqk_v, L.bqk_v = None, None
-            if self.fold_message_projection:
+            if mp:
+                L.Wqkv_h, L.Wo_h, L.sf0_h, L.sf3_h = half(s.Wqkv.weight), half(s.out_proj.weight), half(s.ffn[0].weight), half(s.ffn[3].weight)
+                L.Wqk_h, L.Wv_h, L.Wco_h = half(x.to_qk.weight), half(x.to_v.weight), half(x.to_out.weight)
+                L.cf0_h, L.cf3_h = half(x.ffn[0].weight), half(x.ffn[3].weight)
+                L.Wqk_v_h = half(torch.cat([x.to_qk.weight.detach(), x.to_v.weight.detach()], 0)) if L.Wqk_v else None
+            if self.fold_message_projection and not mp:
                 sw, sb = fold(s.ffn[0], s.out_proj)
                 xw, xb = fold(x.ffn[0], x.to_out)
                 L.Wo, L.bo, L.Wco, L.bco = None, None, None, None
@@ -360,9 +399,18 @@ class LightGlue(nn.Module):
                 hd.token_w, hd.token_b = p(tok.weight), p(tok.bias)
             else:
                 hd.token_w, hd.token_b = None, None
-        self._watch = N.ParamWatch(self._sig_tensors)  # `.data` edits are seen by content at the next forward (round 4)
-        self._packed = (w, layers, keep, heads)
-        return self._packed
+        # `.data` edits are seen by content at the next forward (round 4).  ONE watch per set of images: it is built with the first
+        # image after a drop and takes its reference then; the other mode's image, packed later, is judged against that same
+        # reference, so an edit made between the two packs raises the flag and drops both.  It also keeps the
+        # buffers a captured graph of the first mode reads alive while the second mode packs.
+        if self._watch is None:
+            self._watch = N.ParamWatch(self._sig_tensors)
+        packed = (w, layers, keep, heads)
+        if mp:
+            self._packed_mp = packed
+        else:
+            self._packed = packed
+        return packed
 
     def _add_scale_ori_error(self, feats0):
         """What the reference's forward raises with add_scale_ori=True (recorded from the reference, tests/golden/lgcfg.json): the
@@ -381,15 +429,16 @@ class LightGlue(nn.Module):
             raise RuntimeError("einx LightGlue: add_scale_ori=True has no working forward in the reference (lightglue.py:540-565)")
         if pb0.desc.shape[-1] != self.conf.input_dim or pb1.desc.shape[-1] != self.conf.input_dim:
             raise AssertionError("descriptor dimension does not match conf.input_dim")
-        w = self._pack()[0]
+        mp = self.mixed_precision_active()  # read at every call
+        w, _, _, heads = self._pack(mp)
         w.filter_threshold = float(self.conf.filter_threshold)  # read at every call like the reference's filter_matches call (lightglue.py:656)
         stale = self._watch.check()
-        es = (self._pack()[3], float(self.conf.depth_confidence)) if self.early_stop_active() else None
+        es = (heads, float(self.conf.depth_confidence)) if self.early_stop_active() else None
         pr = None
         if self.point_pruning_active():
-            pr = (self._pack()[3], float(self.conf.width_confidence), int(self.pruning_min_kpts(pb0.desc.device)))
+            pr = (heads, float(self.conf.width_confidence), int(self.pruning_min_kpts(pb0.desc.device)))
         r = N.lightglue(w, pb0, pb1, want_la=self.want_log_assignment, want_ref=True, all_layers=all_layers, early_stop=es, pruning=pr,
-                        flash=bool(self.conf.flash))
+                        flash=bool(self.conf.flash), mp=mp)
         r.stale = stale
         return N.gather_matches(r, pb0.kpts, pb1.kpts, pb0.counts, 2)
 

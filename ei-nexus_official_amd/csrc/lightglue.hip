@@ -1,5 +1,6 @@
 // lightglue.hip -- LightGlue inference on gfx950 (fp32 end to end, fp32 matrix cores; with the opt-in `flash: True` the attention
-// alone runs in fp16 on the f16 matrix-core instruction: lg_attn_f16_kernel).
+// alone runs in fp16 on the f16 matrix-core instruction: lg_attn_f16_kernel; with the opt-in `mp: True` the layers'
+// linears run on it too, lg_gemm_kernel on the f16 tile engine of gemm_tile_f16.h).
 //
 // Per layer: SelfBlock (Wqkv GEMM -> rotary -> fused softmax(QK^T/8)V -> out_proj GEMM ->
 // concat-free FFN GEMM -> LayerNorm+GELU -> FFN GEMM + residual) on both sides, then CrossBlock
@@ -18,6 +19,7 @@
 // (assignment + filter_matches), :522-716 (forward).
 #include <stdlib.h>
 
+#include "gemm_tile_f16.h"
 #include "match_tiles.h"
 
 using namespace einx_gemm;
@@ -98,9 +100,38 @@ __device__ __forceinline__ int head_of(const int32_t* stop, int pairs, int nhead
 // the same 128 rows of X are computed on one XCD at about the same time and X is fetched into that
 // L2 once.  The next tile's first K-slab is requested during the current tile's last K-slab, so its
 // latency and the epilogue's stores overlap instead of serialising per tile.
-template <int EPI>
+//
+// Eng: the tile engine.  EngF32 (gemm_tile.h, the default: every fp32 launch) or EngF16 (gemm_tile_f16.h: X rounded to binary16 on
+// the way into LDS, W read as binary16 through g.W, fp32 accumulation; LightGlue's `mp: True`).  Both fill the same
+// Frag with the same (wave, lane, register) -> (row, column) map, so the tile walk and the epilogues below serve both.
+struct EngF32 {
+  using WT = float;
+  using Src = einx_gemm::Src;
+  using Stage = einx_gemm::Stage;
+  static constexpr int LDS_FLOATS = einx_gemm::LDS_FLOATS;
+  static __device__ __forceinline__ void issue(const Src& s, int k0, int K, int Ksplit, Stage& st) { einx_gemm::issue_slab(s, k0, K, Ksplit, st); }
+  static __device__ __forceinline__ void run(const Src& cur, int K, int Ksplit, float* lds, Frag& f, Stage& st, const Src& next, bool has_next) {
+    einx_gemm::tile_nt_run(cur, K, Ksplit, lds, f, st, next, has_next);
+  }
+};
+struct EngF16 {
+  using WT = _Float16;
+  using Src = einx_gemm16::Src;
+  using Stage = einx_gemm16::Stage;
+  static constexpr int LDS_FLOATS = einx_gemm16::LDS_HALVES / 2;
+  static __device__ __forceinline__ void issue(const Src& s, int k0, int K, int Ksplit, Stage& st) { einx_gemm16::issue_slab(s, k0, K, Ksplit, st); }
+  static __device__ __forceinline__ void run(const Src& cur, int K, int Ksplit, float* lds, Frag& f, Stage& st, const Src& next, bool has_next) {
+    einx_gemm16::tile_nt_run(cur, K, Ksplit, reinterpret_cast<_Float16*>(lds), f, st, next, has_next);
+  }
+};
+
+template <int EPI, typename Eng = EngF32>
 __global__ __launch_bounds__(THREADS, 2 * THREADS / 256) void lg_gemm_kernel(const GemmArgs g) {  // registers for two resident workgroups per CU
-  __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+  using Src = typename Eng::Src;
+  using Stage = typename Eng::Stage;
+  using WT = typename Eng::WT;
+  __shared__ __attribute__((aligned(16))) float lds[Eng::LDS_FLOATS];
+  const WT* const W = reinterpret_cast<const WT*>(g.W);  // (EngF16: the binary16 image of the weight)
   constexpr bool ROPE = EPI == EPI_ROPE || EPI == EPI_ROPE_ANY;
   const int rd = EPI == EPI_ROPE ? D : g.d;              // width of the q | k | v blocks (ROPE only)
   const int rdh = EPI == EPI_ROPE ? DH : g.dh;
@@ -124,12 +155,12 @@ __global__ __launch_bounds__(THREADS, 2 * THREADS / 256) void lg_gemm_kernel(con
     s.Mvalid = n;
     if (ROPE) {  // tile tj: block t = tj / tpb of (q, k, v), columns hc0.. of that block = W rows (hc0 + r) * 3 + t
       const int tj = L % tilesN;
-      s.B = g.W + (size_t)(tj / tpb) * g.K;
+      s.B = W + (size_t)(tj / tpb) * g.K;
       s.ldb = 3 * g.K;
       s.j0 = (tj % tpb) * BN;
       s.Nvalid = rd;
     } else {
-      s.B = EPI == EPI_DIV_HEAD ? g.heads[4 * head_of(g.stop, g.pairs, g.nheads, b)] : g.W;
+      s.B = EPI == EPI_DIV_HEAD ? reinterpret_cast<const WT*>(g.heads[4 * head_of(g.stop, g.pairs, g.nheads, b)]) : W;
       s.ldb = g.K;
       s.j0 = (L % tilesN) * BN;
       s.Nvalid = g.N;
@@ -144,16 +175,16 @@ __global__ __launch_bounds__(THREADS, 2 * THREADS / 256) void lg_gemm_kernel(con
   while (L < local_tiles && !locate(L, cur, b, n)) L += slots;
   if (L >= local_tiles) return;
   Stage st;
-  issue_slab(cur, 0, g.K, g.Ksplit, st);
+  Eng::issue(cur, 0, g.K, g.Ksplit, st);
   for (;;) {
     int Ln = L + slots;
     while (Ln < local_tiles && !locate(Ln, nxt, nb, nn)) Ln += slots;
     const bool more = Ln < local_tiles;
     Frag f;
-    tile_nt_run(cur, g.K, g.Ksplit, lds, f, st, nxt, more);
+    Eng::run(cur, g.K, g.Ksplit, lds, f, st, nxt, more);
     const int i0 = cur.i0, j0 = cur.j0;
     if (ROPE) {
-      const int t = (int)((cur.B - g.W) / g.K);  // 0: q, 1: k, 2: v
+      const int t = (int)((cur.B - W) / g.K);  // 0: q, 1: k, 2: v
       float* Yt = (t == 0 ? g.Yq : t == 1 ? g.Yk : g.Yv) + (size_t)b * g.cap * rd;
       const float* encb = g.enc + (size_t)b * g.cap * (2 * rdh);
       const bool odd = threadIdx.x & 1;  // column parity == lane parity (col_of(nt) = 64*wn + 32*nt + lane%32)
@@ -1528,13 +1559,14 @@ __global__ void lg_stack_counts_kernel(const int32_t* n, const int32_t* m, int B
 
 // persistent launch size: resident workgroups of the tile kernels on this device (a multiple of
 // 8 so that every XCD gets the same number of slots), never more than the tiles there are
+template <typename Eng = EngF32>
 unsigned gemm_grid(int tiles) {
-  static int resident = 0;
+  static int resident = 0;  // (one per engine)
   if (resident == 0) {
     int dev = 0, cus = 256, per_cu = 2;
     if (hipGetDevice(&dev) == hipSuccess) {
       if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lg_gemm_kernel<EPI_BIAS>, THREADS, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lg_gemm_kernel<EPI_BIAS, Eng>, THREADS, 0) != hipSuccess || per_cu < 1) per_cu = 2;
     }
     resident = (cus * per_cu) & ~7;
     if (resident < 8) resident = 8;
@@ -1550,9 +1582,11 @@ bool small_grid(int N, int cap, int B, int K, int Ksplit) {
   return tiles < max_tiles && K % SBK == 0 && N % SBN == 0 && (Ksplit >= K || Ksplit % SBK == 0);
 }
 
+// W16: null, or the binary16 image of W: the launch then runs the f16 tile engine (`mp: True`; EPI_BIAS / EPI_RESID
+// only, one kernel for every grid size -- no f16 twin of lg_gemm_small_kernel)
 int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx, const float* X2, int ldx2, int Ksplit, int K, const float* W,
          const float* bias, int N, float* Y, int ldy, float div = 1.0f, const float* const* heads = nullptr, const int32_t* stop = nullptr,
-         int pairs = 0, int nheads = 0) {
+         int pairs = 0, int nheads = 0, const uint16_t* W16 = nullptr) {
   GemmArgs g;
   g.heads = heads;
   g.stop = stop;
@@ -1573,6 +1607,15 @@ int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx,
   g.ldy = ldy;
   g.div = div;
   g.B = B;
+  if (W16) {
+    if (epi != EPI_BIAS && epi != EPI_RESID) return -1;
+    g.W = reinterpret_cast<const float*>(W16);
+    const dim3 grid(gemm_grid<EngF16>(einx_cdiv(N, BN) * einx_cdiv(s.cap, BM) * B));
+    EINX_PROF("lg_gemm_kernel (f16)", st);
+    if (epi == EPI_BIAS) hipLaunchKernelGGL((lg_gemm_kernel<EPI_BIAS, EngF16>), grid, dim3(THREADS), 0, st, g);
+    else hipLaunchKernelGGL((lg_gemm_kernel<EPI_RESID, EngF16>), grid, dim3(THREADS), 0, st, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
   if (small_grid(N, s.cap, B, K, Ksplit)) {
     const dim3 sg((unsigned)(N / SBN), (unsigned)einx_cdiv(s.cap, SBM), (unsigned)B);
     EINX_PROF("lg_gemm_small_kernel", st);
@@ -1582,7 +1625,7 @@ int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx,
     else hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_RESID>, sg, dim3(256), 0, st, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  const dim3 grid(gemm_grid(einx_cdiv(N, BN) * einx_cdiv(s.cap, BM) * B));
+  const dim3 grid(gemm_grid<>(einx_cdiv(N, BN) * einx_cdiv(s.cap, BM) * B));
   EINX_PROF("lg_gemm_kernel", st);
   if (epi == EPI_BIAS) hipLaunchKernelGGL(lg_gemm_kernel<EPI_BIAS>, grid, dim3(THREADS), 0, st, g);
   else if (epi == EPI_DIV) hipLaunchKernelGGL(lg_gemm_kernel<EPI_DIV>, grid, dim3(THREADS), 0, st, g);
@@ -1591,16 +1634,20 @@ int gemm(hipStream_t st, int epi, const Side& s, int B, const float* X, int ldx,
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// the model's widths, as the launchers need them
+// the mode bits of einx_lightglue_mp (einx.h: EINX_LG_ATTN_F16, EINX_LG_LIN_F16)
+enum { LG_ATTN_F16 = 1, LG_LIN_F16 = 2 };
+
+// the model's widths and precision modes, as the launchers need them
 struct Dims {
   int d, heads, dh;
-  bool flash = false;  // attention in fp16 on the matrix cores (conf.flash)
+  bool flash = false;  // LG_ATTN_F16: attention in fp16 on the matrix cores (conf.flash)
+  bool lin16 = false;  // LG_LIN_F16: the layers' linears on the f16 tile engine (conf.mp)
   bool shipped() const { return d == D && dh == DH; }
 };
 
 // fused Wqkv projection + rotary split: X [B,cap,d] -> q, k (rotary applied), v, each [B,cap,d]
-int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const float* X, const float* Wqkv, const float* bqkv, float* q, float* k,
-                  float* v) {
+int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const float* X, const float* Wqkv, const uint16_t* Wqkv16, const float* bqkv,
+                  float* q, float* k, float* v) {
   const int d = dm.d;
   GemmArgs g{};
   g.X = X;
@@ -1625,6 +1672,15 @@ int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const fl
   g.d = dm.d;
   g.dh = dm.dh;
   const int tiles = 3 * einx_cdiv(d, BN) * einx_cdiv(s.cap, BM) * B;  // three blocks (q | k | v) of whole tiles each
+  if (dm.lin16) {
+    if (!Wqkv16) return -1;
+    g.W = reinterpret_cast<const float*>(Wqkv16);
+    const dim3 grid(gemm_grid<EngF16>(tiles));
+    EINX_PROF("lg_gemm_kernel (f16)", st);
+    if (dm.shipped()) hipLaunchKernelGGL((lg_gemm_kernel<EPI_ROPE, EngF16>), grid, dim3(THREADS), 0, st, g);
+    else hipLaunchKernelGGL((lg_gemm_kernel<EPI_ROPE_ANY, EngF16>), grid, dim3(THREADS), 0, st, g);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
   if (tiles < 256 && d % SBN == 0 && d % SBK == 0) {  // as small_grid()
     const dim3 sg((unsigned)(3 * d / SBN), (unsigned)einx_cdiv(s.cap, SBM), (unsigned)B);
     EINX_PROF("lg_gemm_small_kernel", st);
@@ -1632,7 +1688,7 @@ int gemm_qkv_rope(hipStream_t st, const Side& s, int B, const Dims& dm, const fl
     else hipLaunchKernelGGL(lg_gemm_small_kernel<EPI_ROPE_ANY>, sg, dim3(256), 0, st, g);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
-  const dim3 grid(gemm_grid(tiles));
+  const dim3 grid(gemm_grid<>(tiles));
   EINX_PROF("lg_gemm_kernel", st);
   if (dm.shipped()) hipLaunchKernelGGL(lg_gemm_kernel<EPI_ROPE>, grid, dim3(THREADS), 0, st, g);
   else hipLaunchKernelGGL(lg_gemm_kernel<EPI_ROPE_ANY>, grid, dim3(THREADS), 0, st, g);
@@ -1695,12 +1751,19 @@ int attn(hipStream_t st, int B, const Dims& dm, const float* Q, const int32_t* n
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// a layer's Linear: gemm() on the engine the mode asks for (the fp16 image is passed on only under LG_LIN_F16)
+int linear(hipStream_t st, int epi, const Side& s, int B, const Dims& dm, const float* X, int ldx, const float* X2, int ldx2, int Ksplit, int K,
+           const float* W, const uint16_t* W16, const float* bias, int N, float* Y, int ldy) {
+  if (dm.lin16 && !W16) return -1;
+  return gemm(st, epi, s, B, X, ldx, X2, ldx2, Ksplit, K, W, bias, N, Y, ldy, 1.0f, nullptr, nullptr, 0, 0, dm.lin16 ? W16 : nullptr);
+}
+
 // ffn(cat[x,msg]) + residual, in place on s.x
-int ffn(hipStream_t st, const Side& s, int B, const Dims& dm, const float* msg, const float* w0, const float* b0, const float* g, const float* be,
-        const float* w3, const float* b3) {
+int ffn(hipStream_t st, const Side& s, int B, const Dims& dm, const float* msg, const float* w0, const uint16_t* w0h, const float* b0, const float* g,
+        const float* be, const float* w3, const uint16_t* w3h, const float* b3) {
   const int d = dm.d;
   // (one fused launch for ffn.0 + LayerNorm + GELU was measured in round 3 and is slower: tools/experiments/lg_ffn0_ln_gelu_kernel.hip.txt)
-  if (gemm(st, EPI_BIAS, s, B, s.x, d, msg, d, d, 2 * d, w0, b0, 2 * d, s.h, 2 * d)) return -1;
+  if (linear(st, EPI_BIAS, s, B, dm, s.x, d, msg, d, d, 2 * d, w0, w0h, b0, 2 * d, s.h, 2 * d)) return -1;
   {
     EINX_PROF("lg_ln_gelu_kernel", st);
     const dim3 lg((unsigned)einx_cdiv(s.cap, 4), (unsigned)B);
@@ -1708,7 +1771,7 @@ int ffn(hipStream_t st, const Side& s, int B, const Dims& dm, const float* msg, 
     else hipLaunchKernelGGL(lg_ln_gelu_any_kernel, lg, dim3(256), 0, st, s.h, s.cnt, s.cap, 2 * d, g, be);
   }
   if (hipGetLastError() != hipSuccess) return -1;
-  return gemm(st, EPI_RESID, s, B, s.h, 2 * d, nullptr, 0, 0x7fffffff, 2 * d, w3, b3, d, s.x, d);
+  return linear(st, EPI_RESID, s, B, dm, s.h, 2 * d, nullptr, 0, 0x7fffffff, 2 * d, w3, w3h, b3, d, s.x, d);
 }
 
 }  // namespace
@@ -1732,7 +1795,7 @@ EINX_EXPORT int einx_linear(const float* x, int M, int K, const float* w, const 
   g.ldy = N;
   g.div = 1.0f;
   g.B = 1;
-  const dim3 grid(gemm_grid(einx_cdiv(N, BN) * einx_cdiv(M, BM)));
+  const dim3 grid(gemm_grid<>(einx_cdiv(N, BN) * einx_cdiv(M, BM)));
   if (accumulate) hipLaunchKernelGGL(lg_gemm_kernel<EPI_RESID>, grid, dim3(THREADS), 0, (hipStream_t)stream, g);
   else hipLaunchKernelGGL(lg_gemm_kernel<EPI_BIAS>, grid, dim3(THREADS), 0, (hipStream_t)stream, g);
   EINX_CHECK_LAUNCH();
@@ -1953,26 +2016,26 @@ int lg_layer(const LgCtx& c, int li) {
   const int E = v.entries;
   for (int sd = 0; sd < v.n; ++sd) {
     const Side& s = v.s[sd];
-    LG_CHECK(LG, gemm_qkv_rope(st, s, E, dm, s.x, L.Wqkv, L.bqkv, s.q, s.k, s.v));
+    LG_CHECK(LG, gemm_qkv_rope(st, s, E, dm, s.x, L.Wqkv, L.Wqkv_h, L.bqkv, s.q, s.k, s.v));
     LG_CHECK(LG, attn(st, E, dm, s.q, s.cnt, s.cap, s.k, s.v, s.cnt, s.cap, s.ctx));
     if (L.Wo) {
-      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.ctx, d, nullptr, 0, 0x7fffffff, d, L.Wo, L.bo, d, s.msg, d));
-      LG_CHECK(LG, ffn(st, s, E, dm, s.msg, L.sf0_w, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_b));
+      LG_CHECK(LG, linear(st, EPI_BIAS, s, E, dm, s.ctx, d, nullptr, 0, 0x7fffffff, d, L.Wo, L.Wo_h, L.bo, d, s.msg, d));
+      LG_CHECK(LG, ffn(st, s, E, dm, s.msg, L.sf0_w, L.sf0_h, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_h, L.sf3_b));
     } else {  // out_proj folded into the FFN's first Linear at load time: message = context
-      LG_CHECK(LG, ffn(st, s, E, dm, s.ctx, L.sf0_w, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_b));
+      LG_CHECK(LG, ffn(st, s, E, dm, s.ctx, L.sf0_w, L.sf0_h, L.sf0_b, L.sln_g, L.sln_b, L.sf3_w, L.sf3_h, L.sf3_b));
     }
   }
   // to_qk and to_v read the same rows: with the merged weight image [Wqk; Wv] (shipped widths) they are ONE launch writing
   // qk | v side by side into the FFN's hidden buffer (free until ffn.0 runs), and the attention reads them at row stride 2 d --
   // the same k-ordered chain and bias per output, one launch less per layer
-  const bool merged = L.Wqk_v && L.bqk_v && dm.shipped();
+  const bool merged = L.Wqk_v && L.bqk_v && dm.shipped() && (!dm.lin16 || L.Wqk_v_h);
   for (int sd = 0; sd < v.n; ++sd) {
     const Side& s = v.s[sd];
     if (merged) {
-      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wqk_v, L.bqk_v, 2 * d, s.h, 2 * d));
+      LG_CHECK(LG, linear(st, EPI_BIAS, s, E, dm, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wqk_v, L.Wqk_v_h, L.bqk_v, 2 * d, s.h, 2 * d));
     } else {
-      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wqk, L.bqk, d, s.q, d));
-      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wv, L.bv, d, s.v, d));
+      LG_CHECK(LG, linear(st, EPI_BIAS, s, E, dm, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wqk, L.Wqk_h, L.bqk, d, s.q, d));
+      LG_CHECK(LG, linear(st, EPI_BIAS, s, E, dm, s.x, d, nullptr, 0, 0x7fffffff, d, L.Wv, L.Wv_h, L.bv, d, s.v, d));
     }
   }
   const Side &r0 = v.s[0], &r1 = v.s[1];
@@ -1989,10 +2052,10 @@ int lg_layer(const LgCtx& c, int li) {
   for (int sd = 0; sd < v.n; ++sd) {
     const Side& s = v.s[sd];
     if (L.Wco) {
-      LG_CHECK(LG, gemm(st, EPI_BIAS, s, E, s.ctx, d, nullptr, 0, 0x7fffffff, d, L.Wco, L.bco, d, s.msg, d));
-      LG_CHECK(LG, ffn(st, s, E, dm, s.msg, L.cf0_w, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_b));
+      LG_CHECK(LG, linear(st, EPI_BIAS, s, E, dm, s.ctx, d, nullptr, 0, 0x7fffffff, d, L.Wco, L.Wco_h, L.bco, d, s.msg, d));
+      LG_CHECK(LG, ffn(st, s, E, dm, s.msg, L.cf0_w, L.cf0_h, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_h, L.cf3_b));
     } else {
-      LG_CHECK(LG, ffn(st, s, E, dm, s.ctx, L.cf0_w, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_b));
+      LG_CHECK(LG, ffn(st, s, E, dm, s.ctx, L.cf0_w, L.cf0_h, L.cf0_b, L.cln_g, L.cln_b, L.cf3_w, L.cf3_h, L.cf3_b));
     }
   }
   return EINX_OK;
@@ -2117,7 +2180,7 @@ int lg_assign(const LgCtx& c) {
   return EINX_OK;
 }
 
-int lg_run(const einx_lg_weights* w, const EarlyStop* es, bool flash, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
+int lg_run(const einx_lg_weights* w, const EarlyStop* es, unsigned mode, const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
            const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws, int64_t* matches0,
            int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0, float* ref1, int ref_layers, void* stream) {
   EINX_CHECK_ARG(w && kpts0 && desc0 && n && kpts1 && desc1 && m && ws && matches0 && matches1 && scores0 && scores1, "null pointer");
@@ -2134,7 +2197,8 @@ int lg_run(const einx_lg_weights* w, const EarlyStop* es, bool flash, const floa
   c.st = (hipStream_t)stream;
   c.w = w;
   c.dm = dm;
-  c.dm.flash = flash;
+  c.dm.flash = (mode & LG_ATTN_F16) != 0;
+  c.dm.lin16 = (mode & LG_LIN_F16) != 0;
   c.sh = {B, cap0, cap1, dm.d, dm.dh, w->n_layers};
   c.es = es;
   if (es) c.ad = es->ad;
@@ -2194,13 +2258,13 @@ EINX_EXPORT int einx_lightglue(const einx_lg_weights* w, const float* kpts0, con
                                const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
                                float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
                                float* ref0, float* ref1, int ref_layers, void* stream) {
-  return lg_run(w, nullptr, false, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
+  return lg_run(w, nullptr, 0, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
                 ref1, ref_layers, stream);
 }
 
 namespace {
-// the bodies of the early-stop and adaptive entries; entry: the exported function an argument error is reported under; flash: the
-// attention of einx_lightglue_flash
+// the bodies of the early-stop and adaptive entries; entry: the exported function an argument error is reported under; mode: the
+// precision bits (LG_ATTN_F16: the attention of einx_lightglue_flash, LG_LIN_F16: the linears of einx_lightglue_mp)
 #define LG_CHECK_ARG(cond, msg)                \
   do {                                         \
     if (!(cond)) {                             \
@@ -2208,7 +2272,7 @@ namespace {
       return EINX_ERR_ARG;                     \
     }                                          \
   } while (0)
-int lg_early_stop(const char* entry, bool flash, const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+int lg_early_stop(const char* entry, unsigned mode, const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
                                           const float* kpts0, const float* desc0, const int32_t* n, int cap0, const float* kpts1,
                                           const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
                                           int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
@@ -2218,11 +2282,11 @@ int lg_early_stop(const char* entry, bool flash, const einx_lg_weights* w, const
       heads_error(w, heads, head_size, "early stopping takes 1..32 layers", nullptr, "every layer but the last needs its token_confidence head");
   LG_CHECK_ARG(!bad, bad);
   const EarlyStop es{heads, depth_confidence, stop, nullptr};
-  return lg_run(w, &es, flash, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
+  return lg_run(w, &es, mode, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1,
                 1, stream);
 }
 
-int lg_adaptive(const char* entry, bool flash, const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+int lg_adaptive(const char* entry, unsigned mode, const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
                                         double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
                                         const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1,
                                         float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
@@ -2237,7 +2301,7 @@ int lg_adaptive(const char* entry, bool flash, const einx_lg_weights* w, const e
   LG_CHECK_ARG(!bad, bad);
   const Adaptive ad{(float)(1.0 - width_confidence), min_kpts, prune0, prune1, kept0, kept1, live};
   const EarlyStop es{heads, depth_confidence, stop, &ad};
-  return lg_run(w, &es, flash, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, nullptr, ref0,
+  return lg_run(w, &es, mode, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, nullptr, ref0,
                 ref1, 1, stream);
 }
 }  // namespace
@@ -2247,7 +2311,7 @@ EINX_EXPORT int einx_lightglue_early_stop(const einx_lg_weights* w, const einx_l
                                           const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1, void* ws,
                                           int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
                                           float* ref1, int32_t* stop, void* stream) {
-  return lg_early_stop(__func__, false, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0,
+  return lg_early_stop(__func__, 0, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0,
                        matches1, scores0, scores1, la, ref0, ref1, stop, stream);
 }
 
@@ -2257,7 +2321,7 @@ EINX_EXPORT int einx_lightglue_adaptive(const einx_lg_weights* w, const einx_lg_
                                         float w1, void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la,
                                         float* ref0, float* ref1, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
                                         int32_t* live, void* stream) {
-  return lg_adaptive(__func__, false, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0,
+  return lg_adaptive(__func__, 0, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0,
                      w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1, stop, prune0, prune1, kept0, kept1, live, stream);
 }
 
@@ -2277,16 +2341,79 @@ EINX_EXPORT int einx_lightglue_flash(const einx_lg_weights* w, const einx_lg_hea
                                      int64_t* kept1, int32_t* live, void* stream) {
   if (width_confidence > 0.0) {
     EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1, "point pruning returns the surviving rows, not every layer's: ref_layers must be 0 or 1");
-    return lg_adaptive(__func__, true, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0,
+    return lg_adaptive(__func__, LG_ATTN_F16, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0,
                        w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1, stop, prune0, prune1, kept0, kept1, live, stream);
   }
   if (depth_confidence > 0.0f) {
     EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1, "early stopping returns the rows the stopping head read: ref_layers must be 0 or 1");
-    return lg_early_stop(__func__, true, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0,
+    return lg_early_stop(__func__, LG_ATTN_F16, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0,
                          matches1, scores0, scores1, la, ref0, ref1, stop, stream);
   }
-  return lg_run(w, nullptr, true, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
+  return lg_run(w, nullptr, LG_ATTN_F16, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0,
                 ref1, ref_layers, stream);
+}
+
+// conf.mp: the same three runs with the precision modes as bits.  EINX_LG_LIN_F16: the nine linears of every layer on
+// the f16 tile engine (inputs and weights rounded to binary16, fp32 accumulation, fp32 bias, fp32 result); EINX_LG_ATTN_F16: the
+// attention of einx_lightglue_flash.  mode == 0 is einx_lightglue / _early_stop / _adaptive, mode == EINX_LG_ATTN_F16 is _flash.
+EINX_EXPORT size_t einx_lightglue_mp_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers) {
+  return einx_lightglue_flash_ws_bytes(B, cap0, cap1, d, heads, input_dim, n_layers);  // neither kernel needs a region of its own
+}
+
+EINX_EXPORT int einx_lightglue_mp(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                                  double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                                  const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1,
+                                  void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
+                                  float* ref1, int ref_layers, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
+                                  int32_t* live, int mode, void* stream) {
+  EINX_CHECK_ARG(w, "null pointer");
+  EINX_CHECK_ARG((mode & ~(LG_ATTN_F16 | LG_LIN_F16)) == 0, "mode takes EINX_LG_ATTN_F16 | EINX_LG_LIN_F16 only");
+  if (mode & LG_LIN_F16) {  // the contract rounds the weights as written: no folded out_proj / to_out, and every linear's fp16 image
+    EINX_CHECK_ARG(w->struct_size == sizeof(einx_lg_weights) && w->layer_size == sizeof(einx_lg_layer),
+                   "einx_lg_weights::struct_size / layer_size do not match this library (header / library ABI mismatch)");
+    EINX_CHECK_ARG(w->n_layers >= 1 && w->layers, "no layers");
+    for (int li = 0; li < w->n_layers; ++li) {
+      const einx_lg_layer& L = w->layers[li];
+      EINX_CHECK_ARG(L.Wo && L.bo && L.Wco && L.bco, "linears in fp16 take unfolded weights: every layer needs Wo / bo / Wco / bco");
+      EINX_CHECK_ARG(L.Wqkv_h && L.Wo_h && L.sf0_h && L.sf3_h && L.Wqk_h && L.Wv_h && L.Wco_h && L.cf0_h && L.cf3_h,
+                     "linears in fp16 need the binary16 image of every layer's nine weights");
+    }
+  }
+  if (width_confidence > 0.0) {
+    EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1, "point pruning returns the surviving rows, not every layer's: ref_layers must be 0 or 1");
+    return lg_adaptive(__func__, (unsigned)mode, w, heads, head_size, depth_confidence, width_confidence, min_kpts, kpts0, desc0, n, cap0, kpts1, desc1, m,
+                       cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la, ref0, ref1, stop, prune0, prune1, kept0, kept1, live, stream);
+  }
+  if (depth_confidence > 0.0f) {
+    EINX_CHECK_ARG(ref_layers == 0 || ref_layers == 1, "early stopping returns the rows the stopping head read: ref_layers must be 0 or 1");
+    return lg_early_stop(__func__, (unsigned)mode, w, heads, head_size, depth_confidence, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws,
+                         matches0, matches1, scores0, scores1, la, ref0, ref1, stop, stream);
+  }
+  return lg_run(w, nullptr, (unsigned)mode, kpts0, desc0, n, cap0, kpts1, desc1, m, cap1, B, h0, w0, h1, w1, ws, matches0, matches1, scores0, scores1, la,
+                ref0, ref1, ref_layers, stream);
+}
+
+// The linear of conf.mp alone (a test hook): Y[b, i, :] (+)= RN16(cat(X[b, i, :Ksplit], X2[b, i, :K - Ksplit])) @ W16^T + bias for the
+// first min(cnt[b], cap) rows of entry b (cnt null: cap rows); rows past the count are not written.
+EINX_EXPORT int einx_lg_linear_f16(const float* X, const float* X2, int Ksplit, int K, const uint16_t* W16, const float* bias, int N, float* Y, int ldy,
+                                   const float* resid, const int32_t* cnt, int cap, int B, int epi, void* stream) {
+  EINX_CHECK_ARG(X && W16 && bias && Y, "null pointer");
+  EINX_CHECK_ARG(B > 0 && cap > 0 && N > 0 && K > 0 && K % 4 == 0, "bad shape (K must be a multiple of 4)");
+  EINX_CHECK_ARG(ldy >= N, "ldy must be at least N");
+  EINX_CHECK_ARG(!X2 || (Ksplit > 0 && Ksplit < K && Ksplit % einx_gemm16::BK == 0), "Ksplit must be a multiple of the 32-deep K slab inside (0, K)");
+  EINX_CHECK_ARG(epi == 0 || epi == 1, "epi must be 0 (bias) or 1 (bias + residual)");
+  EINX_CHECK_ARG(epi == 1 || resid == nullptr, "resid is read by epi 1 only: with epi 0 it must be null");
+  EINX_CHECK_ARG(epi == 0 || resid == nullptr || resid == Y, "the residual is accumulated in place: resid must be Y (or null)");
+  Side s{};
+  s.cnt = cnt;
+  s.cap = cap;
+  const int k1 = X2 ? Ksplit : K;
+  if (gemm((hipStream_t)stream, epi ? EPI_RESID : EPI_BIAS, s, B, X, k1, X2, K - k1, X2 ? Ksplit : 0x7fffffff, K, nullptr, bias, N, Y, ldy, 1.0f, nullptr,
+           nullptr, 0, 0, W16) != 0) {
+    einx_set_error("einx_lg_linear_f16: kernel launch failed");
+    return EINX_ERR_LAUNCH;
+  }
+  return EINX_OK;
 }
 
 // The attention of conf.flash alone (a test hook): O[b, q, h dh ..] = RN16(softmax_j(RN16(Q_h[q]) . RN16(K_h[j]) / sqrt(dh)) RN16(V_h[j]))

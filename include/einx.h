@@ -297,6 +297,9 @@ typedef struct einx_lg_layer {
   /* optional (NULL: two launches): the rows of Wqk followed by the rows of Wv as ONE [2d, d] matrix, and [bqk | bv] -- to_qk and
    * to_v then run as one launch (d = 256 with 64-wide heads; same results) */
   const float *Wqk_v, *bqk_v;
+  /* optional (NULL unless einx_lightglue_mp runs with EINX_LG_LIN_F16): the IEEE binary16 image (round to nearest even) of the nine
+   * Linear weights above, same shapes, and of Wqk_v.  Wo / Wco must then be given (no fold): the weights are rounded as written. */
+  const uint16_t *Wqkv_h, *Wo_h, *sf0_h, *sf3_h, *Wqk_h, *Wv_h, *Wco_h, *cf0_h, *cf3_h, *Wqk_v_h;
 } einx_lg_layer;
 
 typedef struct einx_lg_weights {
@@ -414,6 +417,36 @@ int einx_lightglue_flash(const einx_lg_weights* w, const einx_lg_head* heads, si
  * row of an entry without queries or keys, are not written.  Every value written is binary16-representable. */
 int einx_lg_attention_f16(const float* Q, const float* K, const float* V, float* O, const int32_t* nq, const int32_t* nk, int capq, int capk,
                           int B, int heads, int dh, int ld, int kv_shift, void* stream);
+
+/* LightGlue's `mp: True` (lightglue.py:430; upstream's torch.autocast(enabled=conf.mp), which the reference's forward no longer
+ * has): the runs above with the precision modes as bits of `mode`.
+ *   EINX_LG_LIN_F16:  the nine nn.Linear of every transformer layer (SelfBlock Wqkv, out_proj, ffn.0, ffn.3; CrossBlock to_qk, to_v,
+ *                     to_out, ffn.0, ffn.3) on the f16 matrix-core instruction: every input element and every weight element
+ *                     rounded to IEEE binary16 (round to nearest even, overflow to infinity), exact products accumulated in fp32
+ *                     in an unspecified order, fp32 bias added in fp32, fp32 result (NOT rounded to binary16).  Operands whose
+ *                     rounded magnitude lies below 2^-14 are outside the contract.  Needs the *_h images of einx_lg_layer and
+ *                     unfolded Wo / Wco.  input_proj, rotary, residual, LayerNorm, GELU, the heads and every decision stay fp32.
+ *   EINX_LG_ATTN_F16: the attention of einx_lightglue_flash.
+ * mode 0 = the fp32 entries, EINX_LG_ATTN_F16 alone = einx_lightglue_flash.  Single pairs run the wide f16 GEMM kernel (no
+ * small-grid twin).  Arguments and rules otherwise as einx_lightglue_flash; ws: einx_lightglue_mp_ws_bytes(...) bytes (the same
+ * carve).  No allocation, no atomics, no host synchronisation: capturable. */
+#define EINX_LG_ATTN_F16 1
+#define EINX_LG_LIN_F16 2
+size_t einx_lightglue_mp_ws_bytes(int B, int cap0, int cap1, int d, int heads, int input_dim, int n_layers);
+int einx_lightglue_mp(const einx_lg_weights* w, const einx_lg_head* heads, size_t head_size, float depth_confidence,
+                      double width_confidence, int min_kpts, const float* kpts0, const float* desc0, const int32_t* n, int cap0,
+                      const float* kpts1, const float* desc1, const int32_t* m, int cap1, int B, float h0, float w0, float h1, float w1,
+                      void* ws, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, float* la, float* ref0,
+                      float* ref1, int ref_layers, int32_t* stop, float* prune0, float* prune1, int64_t* kept0, int64_t* kept1,
+                      int32_t* live, int mode, void* stream);
+
+/* The linear of EINX_LG_LIN_F16 alone (a test hook).  X: fp32 [B,cap,K], or with X2 the concatenation of X [B,cap,Ksplit] and X2
+ * [B,cap,K - Ksplit] (Ksplit a multiple of 32); W16: binary16 [N,K]; bias fp32 [N]; Y fp32 rows of stride ldy >= N.  epi 0:
+ * Y = RN16(X) W16^T + bias; epi 1: Y += the same (resid: NULL or Y, the residual is read in place; with epi 0 a non-NULL resid is refused).  The rotary
+ * epilogues of the Wqkv projection are reached through a forward only.  Entry b: its first
+ * min(cnt[b], cap) rows (cnt NULL: cap rows); rows past the count and columns past N are not written.  K a multiple of 4. */
+int einx_lg_linear_f16(const float* X, const float* X2, int Ksplit, int K, const uint16_t* W16, const float* bias, int N, float* Y, int ldy,
+                       const float* resid, const int32_t* cnt, int cap, int B, int epi, void* stream);
 
 /* Assignment NLL of ONE MatchAssignment head (lightglue.py:66-133 NLLLoss / weight_loss, :751-769 LightGlue.loss in eval mode): the
  * sums behind nll_pos / nll_neg / row_norm, without a log_assignment matrix or any other B x n x m buffer.
