@@ -308,9 +308,10 @@ class ExtractorEngine:
             except Exception:
                 pass
 
-    def handle(self, scale, dilate_mask, input_div):
-        """einx_extractor for this network (include/einx.h): rebuilt when a call-time parameter changes."""
-        key = (float(scale), bool(dilate_mask), float(input_div), self.top_k, self.radius, self.border, self.det_thr, self.ordering)
+    def handle(self, scale, dilate_mask, input_div, half=False):
+        """einx_extractor for this network (include/einx.h): rebuilt when a call-time parameter changes.  half: with the layers'
+        binary16 images set (einx_extractor_set_conv_f16)."""
+        key = (float(scale), bool(dilate_mask), float(input_div), self.top_k, self.radius, self.border, self.det_thr, self.ordering, bool(half))
         if self._handle is not None and self._handle_key == key:
             return self._handle
         L = N.lib()
@@ -326,6 +327,16 @@ class ExtractorEngine:
         h = L.einx_extractor_create(ctypes.byref(d))
         if not h:
             raise _lib.EinxError("einx_extractor_create failed: " + L.einx_last_error().decode(errors="replace"))
+        if half:
+            def arr16(layers):  # pointers parallel to the fp32 lists; None (NULL) leaves a layer on fp32: the first layer, cin % 8 != 0
+                f = [None if i == 0 and layers is self.backbone else l.f16() for i, l in enumerate(layers)]
+                return (ctypes.POINTER(_lib.ConvDescF16) * len(layers))(*[None if d is None else ctypes.pointer(d) for d in f])
+            m16 = None if mh is None else mh.f16()
+            rc = L.einx_extractor_set_conv_f16(h, arr16(self.backbone), arr16(self.det_head), arr16(self.desc_head),
+                                               None if m16 is None else ctypes.pointer(m16))
+            if rc:
+                L.einx_extractor_destroy(h)
+                _lib.check(rc, "einx_extractor_set_conv_f16")
         self._handle, self._handle_key, self._shapes = h, key, {}
         return h
 
@@ -417,7 +428,7 @@ class ExtractorEngine:
                 self.nms_iters = max(self.nms_base, self.nms_iters // 2)
                 self._calm = 0
 
-    def run(self, x, mask, *, scale, dilate_mask, dense=False, nms_iters=None, input_div=0.0, defer_dense=False):
+    def run(self, x, mask, *, scale, dilate_mask, dense=False, nms_iters=None, input_div=0.0, defer_dense=False, half=False):
         """One einx_extract call (handle-level ABI) enqueues the whole network; the op-by-op path below it serves the
         unbounded-capacity configurations (no top-k: the descriptor buffer is sized from the real counts)."""
         if x.dim() != 4:
@@ -447,7 +458,7 @@ class ExtractorEngine:
             if H <= 2 * crop + 8 or W <= 2 * crop + 8:
                 raise ValueError("image too small for nine un-padded 3x3 convolutions")
         else:
-            h = self.handle(scale, dilate_mask, input_div)
+            h = self.handle(scale, dilate_mask, input_div, half)
             sh = self.shapes(h, H, W)
             if sh.cap <= 8192 and self.use_handle:
                 return self._run_handle(h, sh, x, mask, pads, scale, dense, nms_iters or self.nms_iters, defer_dense=defer_dense)
@@ -456,16 +467,16 @@ class ExtractorEngine:
         t = x
         first = True
         for layer in self.backbone:
-            t = layer(t, fold=(h0, w0, Hp, Wp) if first else None)
+            t = layer(t, fold=(h0, w0, Hp, Wp) if first else None, half=half and not first)
             first = False
         feats = t
         d = feats
         for layer in self.det_head:
-            d = layer(d)
+            d = layer(d, half=half)
         logits = d
         d = feats
         for layer in self.desc_head:
-            d = layer(d)
+            d = layer(d, half=half)
         raw = d
         if crop:
             feats = feats[:, :, crop - 1:-(crop - 1), crop - 1:-(crop - 1)].contiguous()

@@ -18,6 +18,12 @@ class ConvDesc(ctypes.Structure):
                 ("pool", ctypes.c_int32)]
 
 
+class ConvDescF16(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t), ("w_f16", c_void_p), ("bias", c_void_p), ("scale", c_void_p), ("shift", c_void_p),
+                ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("ks", ctypes.c_int32), ("relu", ctypes.c_int32),
+                ("pool", ctypes.c_int32)]
+
+
 class DetectParams(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("Hp", ctypes.c_int32), ("Wp", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("W", ctypes.c_int32), ("h0", ctypes.c_int32), ("w0", ctypes.c_int32), ("radius", ctypes.c_int32),
@@ -124,6 +130,13 @@ SIGNATURES = {
     "einx_conv_first_two_fused_ok": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), c_int, c_int, c_int]),
     "einx_conv_first_two_fused": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc),
                                   c_void_p, c_void_p]),
+    "einx_conv_weight_elems_f16": (c_size_t, [c_int, c_int, c_int]),
+    "einx_conv_repack_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "einx_conv_block_f16": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(ConvDescF16), c_void_p, c_void_p]),
+    "einx_conv_f16_plan": (c_char_p, [c_int] * 7),
+    "einx_conv_f16_last_kernel": (c_char_p, []),
+    "einx_extractor_set_conv_f16": (c_int, [c_void_p, ctypes.POINTER(ctypes.POINTER(ConvDescF16)), ctypes.POINTER(ctypes.POINTER(ConvDescF16)),
+                                            ctypes.POINTER(ctypes.POINTER(ConvDescF16)), ctypes.POINTER(ConvDescF16)]),
     "einx_div_inplace": (c_int, [c_void_p, c_size_t, c_float, c_void_p]),
     "einx_image_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                            c_float, c_void_p, c_void_p]),

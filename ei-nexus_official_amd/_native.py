@@ -164,9 +164,25 @@ class ConvLayer:
                              0 if self.scale is None else self.scale.data_ptr(), 0 if self.shift is None else self.shift.data_ptr(),
                              cin, cout, ks, int(relu), int(pool))
         self._keep = w  # repack reads it asynchronously
+        self._f16 = None
 
-    def __call__(self, x, fold=None):
-        """x [B,cin,Hs,Ws]; fold = (h0, w0, H, W) applies replicate padding on the fly."""
+    def f16(self):
+        """The binary16 weight image and its descriptor (_lib.ConvDescF16) for the opt-in fp16 convolutions, built
+        at the first use beside the fp32 image and dropped with it; None for a layer the mode does not cover (cin % 8 != 0)."""
+        if self.cin % 8 != 0:
+            return None
+        if self._f16 is None:
+            L = lib()
+            w = self._keep
+            self.w_f16 = torch.empty(L.einx_conv_weight_elems_f16(self.cin, self.cout, self.ks), dtype=torch.float16, device=w.device)
+            check(L.einx_conv_repack_f16(_ptr(w), self.cin, self.cout, self.ks, _ptr(self.w_f16), _stream(w)), "einx_conv_repack_f16")
+            self._f16 = _lib.ConvDescF16(ctypes.sizeof(_lib.ConvDescF16), self.w_f16.data_ptr(), self.desc.bias, self.desc.scale, self.desc.shift,
+                                         self.cin, self.cout, self.ks, int(self.relu), int(self.pool))
+        return self._f16
+
+    def __call__(self, x, fold=None, half=False):
+        """x [B,cin,Hs,Ws]; fold = (h0, w0, H, W) applies replicate padding on the fly.  half: through einx_conv_block_f16 where
+        einx_conv_f16_plan covers the layer and the call (never with a fold)."""
         _dev_check(x)
         B, C, Hs, Ws = x.shape
         if C != self.cin:
@@ -174,7 +190,11 @@ class ConvLayer:
         h0, w0, H, W = fold if fold is not None else (0, 0, Hs, Ws)
         Ho, Wo = (H // 2, W // 2) if self.pool else (H, W)
         out = torch.empty((B, self.cout, Ho, Wo), dtype=F32, device=x.device)
-        check(lib().einx_conv_block(_ptr(x), B, Hs, Ws, h0, w0, H, W, ctypes.byref(self.desc), _ptr(out), _stream(x)), "einx_conv_block")
+        L = lib()
+        if half and (h0, w0, H, W) == (0, 0, Hs, Ws) and L.einx_conv_f16_plan(self.cin, self.cout, self.ks, int(self.pool), B, H, W) is not None:
+            check(L.einx_conv_block_f16(_ptr(x), B, H, W, ctypes.byref(self.f16()), _ptr(out), _stream(x)), "einx_conv_block_f16")
+            return out
+        check(L.einx_conv_block(_ptr(x), B, Hs, Ws, h0, w0, H, W, ctypes.byref(self.desc), _ptr(out), _stream(x)), "einx_conv_block")
         return out
 
 

@@ -19,6 +19,17 @@ class NativeExtractor(nn.Module):
     dilate_mask = False
     input_div = 0.0  # SuperPointv1: the input tensor is divided by 255 IN PLACE inside the forward (reference quirk)
     padding = 1      # 0: un-padded 3x3 convolutions (cell-1 networks; keypoints mapped back by +9)
+    # opt-in: the convolutions with cin % 8 == 0 on the f16 matrix-core instruction -- activations and weights rounded
+    # to binary16, fp32 accumulation and epilogue.  Results then follow that contract, not the fp32 forward.  Read at every call.
+    half_precision = False
+
+    @property
+    def conv_mode(self):
+        """"fp16" when `half_precision` is set, the module is in eval mode and its parameters are on a GPU; "fp32" otherwise"""
+        if not self.half_precision or self.training:
+            return "fp32"
+        p = next(self.parameters(), None)
+        return "fp16" if p is not None and p.device.type == "cuda" else "fp32"
 
     def _init_common(self, nms_radius, detection_top_k, detection_threshold, remove_borders, ordering, descriptor_scale_factor,
                      learnable_descriptor_scale_factor):
@@ -176,7 +187,7 @@ class NativeExtractor(nn.Module):
         scale = self._scale_host
         # (the engine's weight watch rides on the call and reports through its own device word, bf.det.stale)
         return eng.run(x, score_mask, scale=scale, dilate_mask=self.dilate_mask, dense=self.dense_outputs if dense is None else dense,
-                       nms_iters=nms_iters, input_div=input_div, defer_dense=defer_dense)
+                       nms_iters=nms_iters, input_div=input_div, defer_dense=defer_dense, half=self.conv_mode == "fp16")
 
     @on_input_device
     def forward(self, x, score_mask=None, **kwargs):

@@ -28,6 +28,9 @@ struct einx_extractor {
   std::vector<einx_conv_desc> backbone, det, desc;
   bool has_merged = false;  // det[0] + desc[0] as one layer (see einx_extractor_desc::merged_head0)
   einx_conv_desc merged;
+  // opt-in binary16 images (einx_extractor_set_conv_f16), parallel to the lists above: w_f16 == nullptr leaves the layer on fp32
+  std::vector<einx_conv_desc_f16> backbone16, det16, desc16;
+  einx_conv_desc_f16 merged16 = {};
 };
 
 namespace {
@@ -175,6 +178,34 @@ EINX_EXPORT einx_extractor* einx_extractor_create(const einx_extractor_desc* d) 
 
 EINX_EXPORT void einx_extractor_destroy(einx_extractor* e) { delete e; }
 
+EINX_EXPORT int einx_extractor_set_conv_f16(einx_extractor* e, const einx_conv_desc_f16* const* backbone, const einx_conv_desc_f16* const* det_head,
+                                            const einx_conv_desc_f16* const* desc_head, const einx_conv_desc_f16* merged_head0) {
+  EINX_CHECK_ARG(e, "null pointer");
+  // checked whole before anything is stored: a refused call leaves the handle as it was
+  auto fits = [](const einx_conv_desc_f16* h, const einx_conv_desc& c) {
+    return h->struct_size == sizeof(einx_conv_desc_f16) && h->w_f16 && h->cin == c.cin && h->cout == c.cout && h->ks == c.ks && h->relu == c.relu &&
+           h->pool == c.pool && h->cin % 8 == 0 && (h->scale == nullptr) == (c.scale == nullptr) && (h->scale == nullptr) == (h->shift == nullptr);
+  };
+  auto list_fits = [&](const einx_conv_desc_f16* const* src, const std::vector<einx_conv_desc>& L) {
+    for (size_t i = 0; src && i < L.size(); ++i)
+      if (src[i] && !fits(src[i], L[i])) return false;
+    return true;
+  };
+  EINX_CHECK_ARG(list_fits(backbone, e->backbone) && list_fits(det_head, e->det) && list_fits(desc_head, e->desc) &&
+                     (!merged_head0 || (e->has_merged && fits(merged_head0, e->merged))),
+                 "a binary16 descriptor does not describe its layer (struct_size, image, cin % 8 == 0, cin / cout / ks / relu / pool / BN as created)");
+  auto store = [](const einx_conv_desc_f16* const* src, size_t n, std::vector<einx_conv_desc_f16>& dst) {
+    dst.assign(n, einx_conv_desc_f16{});
+    for (size_t i = 0; src && i < n; ++i)
+      if (src[i]) dst[i] = *src[i];
+  };
+  store(backbone, e->backbone.size(), e->backbone16);
+  store(det_head, e->det.size(), e->det16);
+  store(desc_head, e->desc.size(), e->desc16);
+  e->merged16 = merged_head0 ? *merged_head0 : einx_conv_desc_f16{};
+  return EINX_OK;
+}
+
 EINX_EXPORT int einx_extract_shapes(const einx_extractor* e, int H, int W, einx_extract_shapes_t* s) {
   EINX_CHECK_ARG(e && s, "null pointer");
   Plan pl;
@@ -264,13 +295,24 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
     rc = einx_div_inplace(in, (size_t)B * e->backbone.front().cin * H * W, e->d.input_div, stream);
     if (rc) return rc;
   }
+  // one un-folded layer: through einx_conv_block_f16 exactly when a binary16 image is set for it and einx_conv_f16_plan covers the call
+  auto use_f16 = [&](const einx_conv_desc_f16* c16, int hh, int ww) {
+    return c16 && c16->w_f16 && einx_conv_f16_plan(c16->cin, c16->cout, c16->ks, c16->pool, B, hh, ww) != nullptr;
+  };
+  auto conv = [&](const float* x, int hh, int ww, const einx_conv_desc* c, const einx_conv_desc_f16* c16, float* out, void* st) -> int {
+    if (use_f16(c16, hh, ww)) return einx_conv_block_f16(x, B, hh, ww, c16, out, st);
+    return einx_conv_block(x, B, hh, ww, 0, 0, hh, ww, c, out, st);
+  };
+  auto f16_of = [](const std::vector<einx_conv_desc_f16>& L, size_t i) { return i < L.size() ? &L[i] : nullptr; };
   // ---- backbone
   const float* cur = in;
   int h = pl.Hp, w = pl.Wp;
   const int nb = (int)e->backbone.size();
   int first = 0;
-  // the first two layers of a 1-channel network as one launch (large launches only: einx_conv_first_two_fused_ok)
-  if (nb >= 2 && 1 == einx_conv_first_two_fused_ok(&e->backbone[0], &e->backbone[1], B, pl.Hp, pl.Wp)) {
+  // the first two layers of a 1-channel network as one launch (large launches only: einx_conv_first_two_fused_ok); with a binary16
+  // image set for the second layer they are two launches, the first one on the fp32 kernel
+  if (nb >= 2 && !use_f16(f16_of(e->backbone16, 1), pl.Hp, pl.Wp) &&
+      1 == einx_conv_first_two_fused_ok(&e->backbone[0], &e->backbone[1], B, pl.Hp, pl.Wp)) {
     float* out = (2 < nb) ? wk.buf[1] : o->feats;
     if ((rc = einx_conv_first_two_fused(in, B, H, W, pl.h0, pl.w0, pl.Hp, pl.Wp, &e->backbone[0], &e->backbone[1], out, stream))) return rc;
     if (e->backbone[1].pool) {
@@ -284,7 +326,7 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
     const einx_conv_desc& c = e->backbone[i];
     float* out = (i + 1 < nb) ? wk.buf[i & 1] : o->feats;
     if (i == 0) rc = einx_conv_block(cur, B, H, W, pl.h0, pl.w0, pl.Hp, pl.Wp, &c, out, stream);
-    else rc = einx_conv_block(cur, B, h, w, 0, 0, h, w, &c, out, stream);
+    else rc = conv(cur, h, w, &c, f16_of(e->backbone16, i), out, stream);
     if (rc) return rc;
     if (c.pool) {
       h /= 2;
@@ -293,11 +335,11 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
     cur = out;
   }
   // ---- heads (the hidden 3x3 layer of each head goes through a scratch buffer)
-  auto run_head = [&](const std::vector<einx_conv_desc>& L, float* scratch, float* final_out, void* st) -> int {
+  auto run_head = [&](const std::vector<einx_conv_desc>& L, const std::vector<einx_conv_desc_f16>& L16, float* scratch, float* final_out, void* st) -> int {
     const float* x = o->feats;
     for (size_t i = 0; i < L.size(); ++i) {
       float* out = (i + 1 < L.size()) ? scratch : final_out;
-      const int r = einx_conv_block(x, B, h, w, 0, 0, h, w, &L[i], out, st);
+      const int r = conv(x, h, w, &L[i], f16_of(L16, i), out, st);
       if (r) return r;
       x = out;
     }
@@ -307,15 +349,15 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   // single images: the two heads' first layers as one launch into `head` (det channels first); each head's second layer then reads
   // its slice (one image: a channel slice is contiguous)
   const bool merged = e->has_merged && B == 1;
-  if (merged && (rc = einx_conv_block(o->feats, B, h, w, 0, 0, h, w, &e->merged, wk.head, stream))) return rc;
+  if (merged && (rc = conv(o->feats, h, w, &e->merged, &e->merged16, wk.head, stream))) return rc;
   const float* desc_in = wk.head + (size_t)e->det.front().cout * h * w;
   auto det_branch = [&](void* st) -> int {
-    if (merged) return einx_conv_block(wk.head, B, h, w, 0, 0, h, w, &e->det[1], o->logits, st);
-    return run_head(e->det, wk.head, o->logits, st);
+    if (merged) return conv(wk.head, h, w, &e->det[1], f16_of(e->det16, 1), o->logits, st);
+    return run_head(e->det, e->det16, wk.head, o->logits, st);
   };
   // descriptor branch: head convs + the dense by-product that depends on `raw` only
   auto desc_branch = [&](void* st) -> int {
-    int r = merged ? einx_conv_block(desc_in, B, h, w, 0, 0, h, w, &e->desc[1], o->raw, st) : run_head(e->desc, head2, o->raw, st);
+    int r = merged ? conv(desc_in, h, w, &e->desc[1], f16_of(e->desc16, 1), o->raw, st) : run_head(e->desc, e->desc16, head2, o->raw, st);
     if (r) return r;
     if (e->d.cell == 8) r = einx_normalize_map(o->raw, B, D, h * w, e->d.desc_scale, o->coarse, o->raw_cl, st);
     return r;

@@ -144,6 +144,38 @@ const char* einx_conv_last_kernel(void);
  * (einx_conv_first_two_fused_ok stays the query for the fused first pair.) */
 const char* einx_conv_plan(int cin, int cout, int ks, int pool, int B, int Hs, int Ws, int h0, int w0, int H, int W);
 
+/* Opt-in binary16 convolutions on v_mfma_f32_32x32x16_f16 (no reference counterpart beyond its autocast training).
+ * The same block as einx_conv_block for layers with cin % 8 == 0 and no padding fold, under another arithmetic contract: every input
+ * activation and every weight element is rounded to IEEE binary16 (nearest even, overflow to infinity: tensor.half()), the products
+ * are exact in fp32 and summed in fp32 in an unspecified order, and bias / ReLU / BN affine / 2x2 max are einx_conv_block's fp32
+ * epilogue.  Input and output stay fp32 NCHW.  Results follow this contract, NOT the fp32 forward.
+ * einx_conv_weight_elems_f16: binary16 elements (2 bytes each) of the weight image; 0 for arguments outside ks {1,3}, cin, cout > 0.
+ * einx_conv_repack_f16: OIHW fp32 -> the image [cout tile of 64][chunk][64][tap][channels of the chunk], zero-filled past cin /
+ * cout, each element rounded once; runs on `stream`. */
+size_t einx_conv_weight_elems_f16(int cin, int cout, int ks);
+int einx_conv_repack_f16(const float* w_oihw, int cin, int cout, int ks, void* w_f16, void* stream);
+
+typedef struct einx_conv_desc_f16 {
+  size_t struct_size;    /* sizeof(einx_conv_desc_f16) of the caller's header (checked) */
+  const void* w_f16;     /* from einx_conv_repack_f16 */
+  const float* bias;     /* [cout] or NULL */
+  const float* scale;    /* [cout] or NULL, as einx_conv_desc */
+  const float* shift;    /* [cout] or NULL */
+  int32_t cin, cout, ks; /* ks in {1,3}; cin % 8 == 0 */
+  int32_t relu;
+  int32_t pool;          /* 3x3 only; H, W must be even */
+} einx_conv_desc_f16;
+
+/* in [B,cin,H,W] -> out [B,cout,H,W] or [B,cout,H/2,W/2] when pool.  Refused by name (einx_last_error): cin % 8 != 0, ks outside
+ * {1,3}, pooling with odd H or W (or on a 1x1 layer), null pointers, a wrong struct_size, tensors of 2^30 elements per image.
+ * No allocation, no atomics, no host synchronisation: capturable. */
+int einx_conv_block_f16(const float* in, int B, int H, int W, const einx_conv_desc_f16* d, float* out, void* stream);
+/* the instantiation einx_conv_block_f16 WOULD launch / the calling thread's last call launched, e.g. "conv_f16_kernel<3,8,32,16,true>"
+ * (KS, tile rows, tile columns, channels per LDS round, pool).  einx_conv_f16_plan is host only (usable without a GPU) and returns
+ * NULL for what the entry refuses; these names never appear in einx_conv_plan. */
+const char* einx_conv_f16_plan(int cin, int cout, int ks, int pool, int B, int H, int W);
+const char* einx_conv_f16_last_kernel(void);
+
 /* x /= divisor in place (SuperPointv1.forward `image /= 255.0`, superpoint_extractor.py:372) */
 int einx_div_inplace(float* x, size_t n, float divisor, void* stream);
 
@@ -629,6 +661,16 @@ typedef struct einx_weight_watch {
 
 einx_extractor* einx_extractor_create(const einx_extractor_desc* d); /* NULL on error (einx_last_error) */
 void einx_extractor_destroy(einx_extractor* e);
+/* Opt-in binary16 convolutions for a handle (einx_conv_block_f16's contract).  backbone / det_head / desc_head: host
+ * arrays of n_backbone / n_det / n_desc POINTERS, parallel to the layer arrays einx_extractor_create copied (the descriptors are
+ * copied here too); a NULL entry or a NULL array leaves that layer on einx_conv_block, all NULL restores the fp32 forward.  Each
+ * descriptor must describe its layer (cin, cout, ks, relu, pool) and have cin % 8 == 0.  einx_extract / einx_extract_watch then run
+ * a layer through einx_conv_block_f16 exactly when an image is set for it and einx_conv_f16_plan covers the call; the first layer
+ * (replicate-pad fold) never is, and a second layer with an image set runs as a launch of its own instead of inside the fused first
+ * pair.  Streams, workspace (einx_extract_ws_bytes) and every other launch are unchanged.  Not to be called while another thread
+ * runs einx_extract on the handle. */
+int einx_extractor_set_conv_f16(einx_extractor* e, const einx_conv_desc_f16* const* backbone, const einx_conv_desc_f16* const* det_head,
+                                const einx_conv_desc_f16* const* desc_head, const einx_conv_desc_f16* merged_head0);
 /* Side streams (no reference counterpart).  einx_extract forks onto a side stream of its caller's stream; a host that runs two
  * extractors on two streams wants the second beside the first.  HIP deals streams onto a few hardware queues, and a side stream
  * on its caller's queue serialises the fork (single pair: 0.77 -> 1.06 ms).  So, per device, the library keeps EINX_FORK_STREAMS_MAX
