@@ -73,6 +73,11 @@ class GtMatchesParams(ctypes.Structure):
                                                                             "homography")] + [("pos_sq", c_float), ("neg_sq", c_float)]
 
 
+class GtDenseParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "F0", "F1", "H0", "W0", "H1", "W1")] + [("pos_sq", c_float),
+                                                                                                                      ("neg_sq", c_float)]
+
+
 class EventArrays(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("y", c_void_p), ("t", c_void_p), ("p", c_void_p), ("x_type", ctypes.c_int32), ("y_type", ctypes.c_int32),
                 ("t_type", ctypes.c_int32), ("p_type", ctypes.c_int32), ("n", ctypes.c_int64)]
@@ -196,6 +201,8 @@ SIGNATURES = {
     "einx_gt_warp": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 8),
     "einx_gt_label": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 17),
     "einx_gt_matches": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 30),
+    "einx_gt_dense_ws_bytes": (c_size_t, [ctypes.POINTER(GtDenseParams)]),
+    "einx_gt_dense": (c_int, [ctypes.POINTER(GtDenseParams)] + [c_void_p] * 23),
     "einx_match_pr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "einx_desc_loss_ws_bytes": (c_size_t, [c_int] * 11),
     "einx_desc_loss": (c_int, [c_void_p, c_float, c_void_p, c_float] + [c_int] * 11 + [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

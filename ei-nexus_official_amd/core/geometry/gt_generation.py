@@ -7,7 +7,7 @@ first read (the FeatsDict pattern of the extractors' dense maps)."""
 import torch
 
 from ..._extract import FeatsDict, _Lazy
-from ..metrics._native_metrics import gt_matches
+from ..metrics._native_metrics import gt_matches, gt_matches_dense
 from .wrappers import Camera, Pose  # noqa: F401
 
 IGNORE_FEATURE = -2
@@ -168,4 +168,30 @@ def gt_matches_from_homography(kp0, kp1, H, pos_th=3, neg_th=6, **kw):
         "matching_scores0": r["matching_scores0"], "matching_scores1": r["matching_scores1"],
         "proj_0to1": r["proj_0to1"], "proj_1to0": r["proj_1to0"],
     })
+    return out
+
+
+DENSE_GRID_KEYS = ("matches0", "matches1", "matching_scores0", "matching_scores1", "depth_keypoints0", "depth_keypoints1", "proj_0to1",
+                   "proj_1to0", "visible0", "visible1")
+
+
+def valid_ratio(counts):
+    """check_indices' ratio from einx_gt_dense's counts [B,4]: #(matches0 > -1) / min(#visible0, #visible1) in float32; 0 / 0 is NaN"""
+    c = counts.to(torch.float32)
+    return c[:, 0] / torch.minimum(c[:, 2], c[:, 3])
+
+
+@torch.no_grad()
+def gt_matches_dense_grid(camera0, camera1, depth0, depth1, T_0to1, T_1to0=None, pos_th=3, neg_th=5):
+    """gt_matches_from_pose_depth with every pixel centre of both depth maps as a keypoint (the call of the reference's
+    datasets/generate_MVSEC_relative_pose_val.py:250-259): kp = grid + 0.5 in raster order, ordering "yx".  depth [B,H,W] per side
+    (the sides may differ in size and intrinsics).  Returns the ten O(N) keys of the 12-key dict with its dtypes -- equal, bit for
+    bit, to gt_matches_from_pose_depth on those keypoints -- plus num_matches0 / num_matches1 / num_visible0 / num_visible1 (int32
+    [B]) and valid_ratio (float32 [B]).  The dense `assignment` / `reward` are not offered."""
+    K0, K1 = _calibration(camera0), _calibration(camera1)
+    T10 = None if T_1to0 is None else _matrix(T_1to0)
+    r = gt_matches_dense(depth0, depth1, K0, K1, _matrix(T_0to1), T10, pos_th=pos_th, neg_th=neg_th)
+    out = {k: r[k] for k in DENSE_GRID_KEYS}
+    c = r["counts"]
+    out.update(num_matches0=c[:, 0], num_matches1=c[:, 1], num_visible0=c[:, 2], num_visible1=c[:, 3], valid_ratio=valid_ratio(c))
     return out

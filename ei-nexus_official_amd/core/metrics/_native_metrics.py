@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import GtMatchesParams, HomographyParams, MetricParams, PoseParams, check
+from ..._lib import GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -342,6 +342,65 @@ def gt_matches(kp0, kp1, n=None, m=None, depth0=None, depth1=None, K0=None, K1=N
                             *[P(t) for t in a["pre"]], P(H), P(ws), P(o.get("depth_keypoints0")), P(o.get("depth_keypoints1")), P(o.get("valid0")),
                             P(o.get("valid1")), P(o["proj_0to1"]), P(o["proj_1to0"]), P(o.get("visible0")), P(o.get("visible1")), P(o["matches0"]),
                             P(o["matches1"]), P(o["matching_scores0"]), P(o["matching_scores1"]), P(o["pos0"]), N._stream(kp0)), "einx_gt_matches")
+    return _bools(o)
+
+
+def _frame_index(idx, B, F, dev, name):
+    """int32 [B] frame indices on the device, or None.  Host-visible indices (a list, numpy, a CPU tensor) are checked against the
+    stack here; indices already on the device are not read back: the kernel clamps them to [0, F)."""
+    if idx is None:
+        if F < B:
+            raise ValueError(f"einx: {name} is None (pair b reads frame b), but the stack has {F} frames for {B} pairs")
+        return None
+    if not (torch.is_tensor(idx) and idx.device.type == "cuda"):
+        idx = torch.as_tensor(idx).reshape(-1).to(torch.int64)
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= F):
+            raise IndexError(f"einx: {name} holds a frame outside [0, {F})")
+    idx = idx.to(dev, torch.int32).reshape(-1).contiguous()
+    if idx.numel() != B:
+        raise ValueError(f"einx: {name} must hold one frame index per pair ({B})")
+    return idx
+
+
+@on_input_device
+def gt_matches_dense(depth0, depth1, K0, K1, T_0to1, T_1to0=None, pos_th=3, neg_th=5, idx0=None, idx1=None, labels=True):
+    """gt_matches with every pixel centre of both depth maps as a keypoint (einx_gt_dense), no host sync: keypoint
+    i = y W + x is (x + 0.5, y + 0.5).  depth0 [F0,H0,W0] / depth1 [F1,H1,W1] float32 on the device; idx0 / idx1 [B] pick each
+    pair's frames (None: frame b; host-visible indices are range-checked, device ones are clamped by the kernel), B is that of K0
+    [B,3,3].  Returns counts [B,4] int32 = #(matches0 > -1), #(matches1 > -1), #visible0, #visible1 and, with `labels`, every
+    O(N) tensor of gt_matches for those keypoints, bit for bit, at (2 pos_th + 3)^2 instead of H W candidates per pixel."""
+    pos_sq = float(pos_th) ** 2
+    if not (0.0 < pos_sq < float("inf")):
+        raise ValueError("einx: pos_th must be finite and > 0")
+    dev = depth0.device
+    d0, d1 = (d.to(dev, torch.float32).reshape(-1, d.shape[-2], d.shape[-1]).contiguous() for d in (depth0, depth1))
+    N._dev_check(d0, d1)
+    B = K0.reshape(-1, 9).shape[0]
+    p = GtDenseParams()
+    p.struct_size = ctypes.sizeof(GtDenseParams)
+    p.B, p.F0, p.F1 = B, d0.shape[0], d1.shape[0]
+    p.H0, p.W0, p.H1, p.W1 = d0.shape[1], d0.shape[2], d1.shape[1], d1.shape[2]
+    p.pos_sq, p.neg_sq = pos_sq, float(neg_th) ** 2
+    idx0, idx1 = _frame_index(idx0, B, p.F0, dev, "idx0"), _frame_index(idx1, B, p.F1, dev, "idx1")
+    K0, K1, T01 = _f32c(K0, dev, (B, 9)), _f32c(K1, dev, (B, 9)), _f32c(T_0to1, dev, (B, 16))
+    T10 = None if T_1to0 is None else _f32c(T_1to0, dev, (B, 16))
+    L = N.lib()
+    nbytes = L.einx_gt_dense_ws_bytes(ctypes.byref(p))
+    if nbytes == 0:
+        raise ValueError("einx: gt_matches_dense: bad shape or thresholds")
+    ws = N._workspace(nbytes, dev)
+    n0, n1 = p.H0 * p.W0, p.H1 * p.W1
+    o = {"counts": torch.empty((B, 4), dtype=torch.int32, device=dev)}
+    if labels:
+        o.update(_gt_stage_a_outputs(B, n0, n1, dev))
+        o.update(_gt_label_outputs(B, n0, n1, dev))
+        del o["pos0"]
+    P = N._ptr
+    g = o.get
+    check(L.einx_gt_dense(ctypes.byref(p), P(d0), P(d1), P(idx0), P(idx1), P(K0), P(K1), P(T01), P(T10), P(ws), P(g("depth_keypoints0")),
+                          P(g("depth_keypoints1")), P(g("valid0")), P(g("valid1")), P(g("proj_0to1")), P(g("proj_1to0")), P(g("visible0")),
+                          P(g("visible1")), P(g("matches0")), P(g("matches1")), P(g("matching_scores0")), P(g("matching_scores1")),
+                          P(o["counts"]), N._stream(d0)), "einx_gt_dense")
     return _bools(o)
 
 

@@ -8,7 +8,11 @@
 //   stage B  gt_label_kernel: one thread per row (column), the other side staged in LDS and read with broadcast loads; no N x M
 //            intermediate; gt_finalize_kernel: mutual check + the three-way label
 //   stage C  match_pr_kernel: one wave per pair
-// fp32, unfused (-ffp-contract=off).  No atomics: two runs give the same bits.  Every launch goes on the caller's stream.
+//   dense    gt_dense_*_kernel (datasets/generate_MVSEC_relative_pose_val.py:194-346, check_indices): both
+//            keypoint sets are the pixel grid, one thread per pixel; stage B searches a (2 pos_th + 3)^2 window of the other map
+//            instead of all of it, with the same labels bit for bit; per-pair match / visibility counts
+// fp32, unfused (-ffp-contract=off).  No floating-point atomics (the dense counts are integer sums): two runs give the same bits.
+// Every launch goes on the caller's stream.
 #include "einx_common.h"
 
 namespace {
@@ -70,6 +74,44 @@ __device__ __forceinline__ float gt_sample_depth(const float* dm, int H, int W, 
   return v > 0.0f ? v : nan;
 }
 
+// depth.py:37-60 with ccth=None for one point (x, y) of depth d: image2cam, scale by the depth, transform by T (this view -> the
+// other; null: (R^T, -R^T t) of T_other), pinhole cam2image of the other camera Ko.  (u, v) is the projection, NaN where d is; the
+// return value is "in front of the other camera and inside its image"
+__device__ __forceinline__ bool gt_project_point(float x, float y, float d, const float* Ks, const float* Ko, const float* T,
+                                                 const float* T_other, float* u_out, float* v_out) {
+  float R[9], t[3];
+  if (T) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) R[3 * q + c] = T[4 * q + c];
+      t[q] = T[4 * q + 3];
+    }
+  } else {  // (R^T, -R^T t) of the other direction
+    T = T_other;
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) R[3 * q + c] = T[4 * c + q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) t[q] = -((R[3 * q] * T[3] + R[3 * q + 1] * T[7]) + R[3 * q + 2] * T[11]);
+  }
+  // image2cam, scale by the depth, transform, cam2image (pinhole)
+  const float px = ((x - Ks[2]) / Ks[0]) * d, py = ((y - Ks[5]) / Ks[4]) * d, pz = d;
+  const float qx = ((px * R[0] + py * R[1]) + pz * R[2]) + t[0];
+  const float qy = ((px * R[3] + py * R[4]) + pz * R[5]) + t[1];
+  const float qz = ((px * R[6] + py * R[7]) + pz * R[8]) + t[2];
+  const bool front = qz > 1e-4f;
+  const float z = qz < 1e-4f ? 1e-4f : qz;  // clamp(min=eps): NaN stays NaN
+  const float u = (qx / z) * Ko[0] + Ko[2];
+  const float v = (qy / z) * Ko[4] + Ko[5];
+  // the camera's size is (2 cx, 2 cy) (Camera.from_calibration_matrix), not the depth map's
+  const float wmax = 2.0f * Ko[2] - 1.0f, hmax = 2.0f * Ko[5] - 1.0f;
+  *u_out = u;
+  *v_out = v;
+  return front && u >= 0.0f && u <= wmax && v >= 0.0f && v <= hmax;
+}
+
 struct GtProjArgs {
   GtSide s[2];
   int kp_yx;
@@ -104,43 +146,14 @@ __global__ __launch_bounds__(256) void gt_project_kernel(const GtProjArgs a) {
     d = gt_sample_depth(s.depth + (size_t)b * s.H * s.W, s.H, s.W, x, y);
     valid = d == d && d > 0.0f;
   }
-  const float* Ks = s.K + b * 9;
-  const float* Ko = o.K + b * 9;
-  float R[9], t[3];
-  if (s.T) {
-    const float* T = s.T + b * 16;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) R[3 * q + c] = T[4 * q + c];
-      t[q] = T[4 * q + 3];
-    }
-  } else {  // (R^T, -R^T t) of the other direction
-    const float* T = s.T_other + b * 16;
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) R[3 * q + c] = T[4 * c + q];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) t[q] = -((R[3 * q] * T[3] + R[3 * q + 1] * T[7]) + R[3 * q + 2] * T[11]);
-  }
-  // image2cam, scale by the depth, transform, cam2image (pinhole)
-  const float px = ((x - Ks[2]) / Ks[0]) * d, py = ((y - Ks[5]) / Ks[4]) * d, pz = d;
-  const float qx = ((px * R[0] + py * R[1]) + pz * R[2]) + t[0];
-  const float qy = ((px * R[3] + py * R[4]) + pz * R[5]) + t[1];
-  const float qz = ((px * R[6] + py * R[7]) + pz * R[8]) + t[2];
-  const bool front = qz > 1e-4f;
-  const float z = qz < 1e-4f ? 1e-4f : qz;  // clamp(min=eps): NaN stays NaN
-  const float u = (qx / z) * Ko[0] + Ko[2];
-  const float v = (qy / z) * Ko[4] + Ko[5];
-  // the camera's size is (2 cx, 2 cy) (Camera.from_calibration_matrix), not the depth map's
-  const float wmax = 2.0f * Ko[2] - 1.0f, hmax = 2.0f * Ko[5] - 1.0f;
-  const bool inside = u >= 0.0f && u <= wmax && v >= 0.0f && v <= hmax;
+  float u, v;
+  const bool seen = gt_project_point(x, y, d, s.K + b * 9, o.K + b * 9, s.T ? s.T + b * 16 : nullptr,
+                                     s.T ? nullptr : s.T_other + b * 16, &u, &v);
   s.dk[r] = d;
   s.valid[r] = valid;
   s.proj[2 * r] = u;
   s.proj[2 * r + 1] = v;
-  s.vis[r] = valid && front && inside;
+  s.vis[r] = valid && seen;
 }
 
 struct GtWarpArgs {
@@ -389,6 +402,192 @@ __global__ __launch_bounds__(64) void match_pr_kernel(const int64_t* matches0, c
   }
 }
 
+// ---- both keypoint sets are the pixel grid of their depth map: pixel i = y W + x is the keypoint (x + 0.5, y + 0.5)
+struct GtDenseSide {
+  const float* depth;    // [F,H,W]
+  const int32_t* idx;    // [B] frame of pair b, clamped to [0, F); null: frame b
+  const float* K;        // [B,9]
+  const float* T;        // [B,16] this side -> the other, or null: the inverse of T_other
+  const float* T_other;  // [B,16]
+  float* dk;             // outputs [B,H W], each may be null
+  uint8_t* valid;
+  float* proj_out;       // [B,H W,2]
+  uint8_t* vis;
+  int64_t* matches;
+  float* scores;
+  float* proj;           // ws [B,H W,2]
+  uint8_t* flags;        // ws [B,H W]: bit 0 visible, bit 1 valid
+  uint8_t* neg;          // ws [B,H W]: valid && near > neg_sq
+  int32_t* arg;          // ws [B,H W]: the row's arg-min among the candidates with dist < pos_sq, -1 without one
+  int F, H, W;
+};
+
+struct GtDenseArgs {
+  GtDenseSide s[2];
+  int32_t* counts;  // [B,4]: #(matches0 > -1), #(matches1 > -1), #visible0, #visible1
+  float pos_sq, neg_sq;
+};
+
+// the side and the pixel of a thread: side 0's workgroups come first (as in gt_project_kernel)
+__device__ __forceinline__ int gt_dense_pixel(const GtDenseArgs& a, int* side) {
+  const int blocks0 = einx_cdiv(a.s[0].H * a.s[0].W, 256);
+  *side = (int)blockIdx.x >= blocks0 ? 1 : 0;
+  return ((int)blockIdx.x - (*side ? blocks0 : 0)) * 256 + threadIdx.x;
+}
+
+// stage A: gt_project_kernel's work for the pixel centres; also zeroes the pair's counts for gt_dense_finalize_kernel
+__global__ __launch_bounds__(256) void gt_dense_project_kernel(const GtDenseArgs a) {
+  const int b = blockIdx.y;
+  if (blockIdx.x == 0 && threadIdx.x < 4) a.counts[4 * b + threadIdx.x] = 0;
+  int side;
+  const int i = gt_dense_pixel(a, &side);
+  const GtDenseSide& s = a.s[side];
+  const GtDenseSide& o = a.s[1 - side];
+  const int npix = s.H * s.W;
+  if (i >= npix) return;
+  const int f = s.idx ? max(0, min(s.idx[b], s.F - 1)) : b;
+  const float x = (float)(i % s.W) + 0.5f, y = (float)(i / s.W) + 0.5f;
+  const float d = gt_sample_depth(s.depth + (size_t)f * npix, s.H, s.W, x, y);
+  const bool valid = d == d && d > 0.0f;
+  float u, v;
+  const bool seen = gt_project_point(x, y, d, s.K + b * 9, o.K + b * 9, s.T ? s.T + b * 16 : nullptr,
+                                     s.T ? nullptr : s.T_other + b * 16, &u, &v);
+  const bool vis = valid && seen;
+  const size_t r = (size_t)b * npix + i;
+  s.proj[2 * r] = u;
+  s.proj[2 * r + 1] = v;
+  s.flags[r] = (uint8_t)((vis ? 1 : 0) | (valid ? 2 : 0));
+  if (s.dk) s.dk[r] = d;
+  if (s.valid) s.valid[r] = valid;
+  if (s.vis) s.vis[r] = vis;
+  if (s.proj_out) {
+    s.proj_out[2 * r] = u;
+    s.proj_out[2 * r + 1] = v;
+  }
+}
+
+// stage B: gt_label_kernel's row (column) of pixel i restricted to the pixels of the other map within r = pos_th + 1 of its
+// projection p, in raster order.  dist >= |p - kp_other|^2, so every candidate with dist < pos_sq is inside the box, and the
+// arg-min over them is the row's global arg-min whenever that can become a positive.  kp_other is x + 0.5f.
+__global__ __launch_bounds__(256) void gt_dense_label_kernel(const GtDenseArgs a) {
+  const int b = blockIdx.y;
+  int side;
+  const int i = gt_dense_pixel(a, &side);
+  const GtDenseSide& s = a.s[side];
+  const GtDenseSide& o = a.s[1 - side];
+  if (i >= s.H * s.W) return;
+  const size_t r = (size_t)b * s.H * s.W + i;
+  const size_t ro = (size_t)b * o.H * o.W;
+  const float inf = einx_u2f(0x7f800000u);
+  const float kx = (float)(i % s.W) + 0.5f, ky = (float)(i / s.W) + 0.5f;
+  const float px = s.proj[2 * r], py = s.proj[2 * r + 1];
+  const int fl = s.flags[r];
+  float best = inf;
+  int arg = -1;
+  if ((fl & 1) && fabsf(px) < inf && fabsf(py) < inf) {  // an invisible row has dist = inf everywhere; NaN / inf: an empty box
+    const float rad = sqrtf(a.pos_sq) + 1.0f;
+    // |x + 0.5 - p.x| <= rad, clamped to the map in float so that the conversions are defined
+    const int x0 = (int)fminf(fmaxf(ceilf(px - rad - 0.5f), 0.0f), (float)o.W);
+    const int x1 = (int)fmaxf(fminf(floorf(px + rad - 0.5f), (float)(o.W - 1)), -1.0f);
+    const int y0 = (int)fminf(fmaxf(ceilf(py - rad - 0.5f), 0.0f), (float)o.H);
+    const int y1 = (int)fmaxf(fminf(floorf(py + rad - 0.5f), (float)(o.H - 1)), -1.0f);
+    for (int yy = y0; yy <= y1; ++yy) {
+      const float oky = (float)yy + 0.5f;
+      for (int xx = x0; xx <= x1; ++xx) {
+        const int j = yy * o.W + xx;
+        // the flag first: a byte per candidate, and the 8 bytes of the projection only where it counts (one 8-byte load of a
+        // NaN-masked projection for every candidate instead was measured: 0.93 ms against 0.69 ms at B = 32, 260 x 346, 6.8 % holes)
+        if (!(o.flags[ro + j] & 1)) continue;  // dist = inf
+        const float okx = (float)xx + 0.5f;
+        const float opx = o.proj[2 * (ro + j)], opy = o.proj[2 * (ro + j) + 1];
+        const float ax = px - okx, ay = py - oky;
+        const float cx = kx - opx, cy = ky - opy;
+        const float da = ax * ax + ay * ay;
+        const float dc = cx * cx + cy * cy;
+        const float d = fmaxf(da, dc);
+        if (d < a.pos_sq && d < best) {  // strict: the lowest raster index wins a tie
+          best = d;
+          arg = j;
+        }
+      }
+    }
+  }
+  // min_j dist0[i,j] over ALL j: the distance to the nearest pixel centre, clamped to the map (fp32 rounding is monotone, so the
+  // minimum of (p.x - cx)^2 + (p.y - cy)^2 sits at the nearest column and the nearest row); NaN compares false everywhere: +inf
+  const float ncx = fminf(fmaxf(floorf(px), 0.0f), (float)(o.W - 1)) + 0.5f;
+  const float ncy = fminf(fmaxf(floorf(py), 0.0f), (float)(o.H - 1)) + 0.5f;
+  const float nx = px - ncx, ny = py - ncy;
+  const float dn = nx * nx + ny * ny;
+  const float near = dn == dn ? dn : inf;
+  s.arg[r] = arg;
+  s.neg[r] = (fl & 2) && near > a.neg_sq;
+}
+
+constexpr int GT_DENSE_FIN = 8;  // pixels per thread of gt_dense_finalize_kernel: 2048 per workgroup
+
+// mutual check, the three-way label and stage C.  The counts are integer sums, so two runs give the same bits; a workgroup adds its
+// 2048 pixels up before its one atomicAdd per counter (one per wave made the launch wait on ~180,000 atomics to 128 words at
+// B = 32, 260 x 346: 0.77 ms, more than the labelling itself; now 0.04 ms)
+__global__ __launch_bounds__(256) void gt_dense_finalize_kernel(const GtDenseArgs a) {
+  __shared__ int s_nm[4], s_nv[4];
+  const int b = blockIdx.y;
+  const int per = 256 * GT_DENSE_FIN;
+  const int blocks0 = einx_cdiv(a.s[0].H * a.s[0].W, per);
+  const int side = (int)blockIdx.x >= blocks0 ? 1 : 0;
+  const GtDenseSide& s = a.s[side];
+  const GtDenseSide& o = a.s[1 - side];
+  const int npix = s.H * s.W;
+  const int first = ((int)blockIdx.x - (side ? blocks0 : 0)) * per + threadIdx.x;
+  int nm = 0, nv = 0;
+#pragma unroll
+  for (int k = 0; k < GT_DENSE_FIN; ++k) {
+    const int i = first + 256 * k;
+    if (i >= npix) break;
+    const size_t r = (size_t)b * npix + i;
+    const int j = s.arg[r];
+    const int pos = (j >= 0 && o.arg[(size_t)b * o.H * o.W + j] == i) ? j : -1;
+    const long long label = s.neg[r] ? -1 : (pos >= 0 ? pos : -2);
+    nm += label > -1;
+    nv += s.flags[r] & 1;
+    if (s.matches) s.matches[r] = label;
+    if (s.scores) s.scores[r] = label > -1 ? 1.0f : 0.0f;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    nm += __shfl_xor(nm, off, 64);
+    nv += __shfl_xor(nv, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_nm[threadIdx.x >> 6] = nm;
+    s_nv[threadIdx.x >> 6] = nv;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    nm = (s_nm[0] + s_nm[1]) + (s_nm[2] + s_nm[3]);
+    nv = (s_nv[0] + s_nv[1]) + (s_nv[2] + s_nv[3]);
+    if (nm) atomicAdd(a.counts + 4 * b + side, nm);
+    if (nv) atomicAdd(a.counts + 4 * b + 2 + side, nv);
+  }
+}
+
+bool dense_params_ok(const einx_gt_dense_params* p) {
+  return p && p->struct_size == sizeof(einx_gt_dense_params) && p->B > 0 && p->B <= 65535 && p->F0 > 0 && p->F1 > 0 && p->H0 > 0 &&
+         p->W0 > 0 && p->H1 > 0 && p->W1 > 0 && (int64_t)p->H0 * p->W0 <= (1 << 24) && (int64_t)p->H1 * p->W1 <= (1 << 24) &&
+         p->pos_sq > 0.0f && p->pos_sq < einx_u2f(0x7f800000u) && p->neg_sq >= 0.0f;
+}
+
+// einx_gt_dense's workspace: O(B (H0 W0 + H1 W1)), no N x M term; and 256 bytes of slack
+void dense_carve(WsCarver& c, GtDenseArgs& a, const einx_gt_dense_params* p) {
+  const size_t n[2] = {(size_t)p->B * p->H0 * p->W0, (size_t)p->B * p->H1 * p->W1};
+  for (int side = 0; side < 2; ++side) {
+    a.s[side].proj = c.take<float>(2 * n[side]);
+    a.s[side].arg = c.take<int32_t>(n[side]);
+    a.s[side].flags = c.take<uint8_t>(n[side]);
+    a.s[side].neg = c.take<uint8_t>(n[side]);
+  }
+  c.slack(256);
+}
+
 bool params_ok(const einx_gt_matches_params* p) {
   return p && p->struct_size == sizeof(einx_gt_matches_params) && p->B > 0 && p->B <= 65535 && p->cap0 > 0 && p->cap1 > 0 && p->cols0 >= 2 &&
          p->cols1 >= 2 && p->cap0 <= (1 << 24) && p->cap1 <= (1 << 24);
@@ -521,6 +720,52 @@ EINX_EXPORT int einx_match_pr(const int64_t* matches0, const float* scores0, con
   EINX_CHECK_ARG(B > 0 && cap0 > 0, "bad shape");
   EINX_PROF("match_pr", stream);
   hipLaunchKernelGGL(match_pr_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, matches0, scores0, gt_matches0, n, cap0, out);
+  EINX_CHECK_LAUNCH();
+  return EINX_OK;
+}
+
+EINX_EXPORT size_t einx_gt_dense_ws_bytes(const einx_gt_dense_params* p) {
+  if (!dense_params_ok(p)) return 0;
+  WsCarver c{nullptr};
+  GtDenseArgs a;
+  dense_carve(c, a, p);
+  return c.bytes;
+}
+
+EINX_EXPORT int einx_gt_dense(const einx_gt_dense_params* p, const float* depth0, const float* depth1, const int32_t* idx0,
+                              const int32_t* idx1, const float* K0, const float* K1, const float* T_0to1, const float* T_1to0, void* ws,
+                              float* dk0, float* dk1, uint8_t* valid0, uint8_t* valid1, float* proj01, float* proj10, uint8_t* vis0,
+                              uint8_t* vis1, int64_t* matches0, int64_t* matches1, float* scores0, float* scores1, int32_t* counts,
+                              void* stream) {
+  EINX_CHECK_ARG(dense_params_ok(p), "bad params (struct_size, shape, pos_sq must be finite and > 0)");
+  EINX_CHECK_ARG(depth0 && depth1 && K0 && K1 && T_0to1 && ws && counts, "null pointer");
+  EINX_CHECK_ARG((idx0 || p->F0 >= p->B) && (idx1 || p->F1 >= p->B), "without frame indices a stack needs a frame per pair");
+  GtDenseArgs a;
+  a.s[0] = GtDenseSide{depth0, idx0, K0, T_0to1, T_1to0, dk0, valid0, proj01, vis0, matches0, scores0, nullptr, nullptr, nullptr, nullptr,
+                       p->F0, p->H0, p->W0};
+  a.s[1] = GtDenseSide{depth1, idx1, K1, T_1to0, T_0to1, dk1, valid1, proj10, vis1, matches1, scores1, nullptr, nullptr, nullptr, nullptr,
+                       p->F1, p->H1, p->W1};
+  a.counts = counts;
+  a.pos_sq = p->pos_sq;
+  a.neg_sq = p->neg_sq;
+  WsCarver c{(char*)ws};
+  dense_carve(c, a, p);
+  const dim3 grid((unsigned)(einx_cdiv(p->H0 * p->W0, 256) + einx_cdiv(p->H1 * p->W1, 256)), (unsigned)p->B);
+  hipStream_t s = (hipStream_t)stream;
+  {
+    EINX_PROF("gt_dense_project", stream);
+    hipLaunchKernelGGL(gt_dense_project_kernel, grid, dim3(256), 0, s, a);
+    EINX_CHECK_LAUNCH();
+  }
+  {
+    EINX_PROF("gt_dense_label", stream);
+    hipLaunchKernelGGL(gt_dense_label_kernel, grid, dim3(256), 0, s, a);
+    EINX_CHECK_LAUNCH();
+  }
+  EINX_PROF("gt_dense_finalize", stream);
+  const int per = 256 * GT_DENSE_FIN;
+  const dim3 fin_grid((unsigned)(einx_cdiv(p->H0 * p->W0, per) + einx_cdiv(p->H1 * p->W1, per)), (unsigned)p->B);
+  hipLaunchKernelGGL(gt_dense_finalize_kernel, fin_grid, dim3(256), 0, s, a);
   EINX_CHECK_LAUNCH();
   return EINX_OK;
 }

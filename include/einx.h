@@ -850,6 +850,34 @@ int einx_match_pr(const int64_t* matches0, const float* scores0, const int64_t* 
                   void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dense-grid ground-truth matches and pair covisibility (csrc/gt_matches.hip)
+ *   check_indices                                             datasets/generate_MVSEC_relative_pose_val.py:194-346
+ * einx_gt_matches with BOTH keypoint sets the pixel grid of their depth map: keypoint i = y W + x is the pixel centre
+ * (x + 0.5, y + 0.5), raster order, no keypoint arrays and no counts.  The outputs equal, bit for bit, what einx_gt_matches writes
+ * for those keypoints (pose form), but stage B visits only the pixels of the other map within pos_th + 1 of a pixel's projection:
+ * (2 pos_th + 3)^2 candidates per pixel instead of H W.
+ * depth0 [F0,H0,W0], depth1 [F1,H1,W1] float32 frame stacks; idx0 / idx1 int32 [B] pick pair b's frames (clamped to [0, F) on the
+ * device; NULL = frame b, which needs F >= B).  K0 / K1 [B,9], T_0to1 / T_1to0 [B,16] float32; T_1to0 may be NULL (inverted in the
+ * kernel).  Outputs, each of which may be NULL: dk [B,H W] float32, valid / vis [B,H W] uint8, proj [B,H W,2] (x, y), matches
+ * [B,H W] int64 (index into the other grid, -1 unmatched, -2 ignore), scores [B,H W] float32 = (matches > -1).  counts [B,4] int32
+ * (required) = #(matches0 > -1), #(matches1 > -1), #visible0, #visible1: integer sums, the reference's valid_ratio is
+ * counts[0] / min(counts[2], counts[3]).  pos_sq must be finite and > 0, neg_sq >= 0.  Workspace O(B (H0 W0 + H1 W1)), aligned to
+ * 256 bytes.  Nothing synchronises or allocates; the call can be captured; two runs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_gt_dense_params {
+  size_t struct_size;     /* sizeof(einx_gt_dense_params) (checked) */
+  int32_t B;              /* image pairs */
+  int32_t F0, F1;         /* frames in depth0 / depth1 */
+  int32_t H0, W0, H1, W1; /* map sizes: H W <= 2^24 per side */
+  float pos_sq, neg_sq;   /* pos_th^2, neg_th^2 rounded to float32 */
+} einx_gt_dense_params;
+size_t einx_gt_dense_ws_bytes(const einx_gt_dense_params* p); /* 0 on a bad shape */
+int einx_gt_dense(const einx_gt_dense_params* p, const float* depth0, const float* depth1, const int32_t* idx0, const int32_t* idx1,
+                  const float* K0, const float* K1, const float* T_0to1, const float* T_1to0, void* ws, float* dk0, float* dk1,
+                  uint8_t* valid0, uint8_t* valid1, float* proj01, float* proj10, uint8_t* vis0, uint8_t* vis1, int64_t* matches0,
+                  int64_t* matches1, float* scores0, float* scores1, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Forward values of the extractor losses (csrc/loss.hip): validation under no_grad, no autograd.
  *   ScoreLoss, LogitsLoss, DescriptorsLoss (mse / mae / cosine_similarity), FeatureLoss      core/loss/extractor_loss.py:6-383
  * Every call writes out [B,2] float64 = one (sum, count) pair per image: the reference's (pooled) loss value is
