@@ -74,29 +74,37 @@ __device__ __forceinline__ int nister_col(int ex, int ey, int ez) {
   }
 }
 
-// exponents of Nister's column order (nister_col)
-constexpr int NX[20] = {3, 0, 2, 1, 2, 2, 0, 0, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
-constexpr int NY[20] = {0, 3, 1, 2, 0, 0, 2, 2, 1, 1, 0, 0, 0, 1, 1, 1, 0, 0, 0, 0};
-constexpr int NZ[20] = {0, 0, 0, 0, 1, 0, 1, 0, 1, 0, 2, 1, 0, 2, 1, 0, 3, 2, 1, 0};
-
-// Gauss-Newton on the ten cubics M0 . mon(x, y, z) = 0 from a root of the degree-10 polynomial: the root alone carries that
-// polynomial's conditioning (tests/pose_f64.py:_polish does the same from the action matrix's eigenpairs)
-__device__ void polish(const double (*M0)[20], double& x, double& y, double& z) {
+// Gauss-Newton on det E = 0 and 2 E E^T E - tr(E E^T) E = 0 from a root of the degree-10 polynomial, evaluated on E(x, y, z) =
+// Ec . (x, y, z, 1) itself: the ten cubics expanded over the monomials carry coefficients of |Ec|^3 that cancel, which leaves E
+// 1e-8 off the essential variety on ill-conditioned samples (tests/pose_f64.py:_polish does the same from the eigenpairs)
+__device__ void polish(const double (*Ec)[4], double* w, double& x, double& y, double& z) {
+  double* E = w;         // w: 39 doubles of LDS of this lane's own: E, E E^T, E^T E and the cofactors, read by rolled loops
+  double* G = w + 9;     // (all in registers and unrolled, a step takes 254 VGPRs and 316 bytes of scratch, one wave per SIMD)
+  double* H = w + 18;
+  double* cof = w + 27;
+  double* dv = w + 36;   // one residual row of the Jacobian
 #pragma unroll 1
-  for (int step = 0; step < 3; ++step) {
-    double X[4] = {1.0, x, x * x, x * x * x}, Y[4] = {1.0, y, y * y, y * y * y}, Z[4] = {1.0, z, z * z, z * z * z};
-    double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+  for (int step = 0; step < 12; ++step) {  // quadratic from a good root (three or four steps); a root of a cluster starts farther off
 #pragma unroll 1
-    for (int r = 0; r < 10; ++r) {
-      double res = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0;
-#pragma unroll
-      for (int c = 0; c < 20; ++c) {
-        const double m = M0[r][c];
-        res += m * (X[NX[c]] * Y[NY[c]] * Z[NZ[c]]);
-        if (NX[c] > 0) d0 += m * (NX[c] * X[NX[c] - 1] * Y[NY[c]] * Z[NZ[c]]);
-        if (NY[c] > 0) d1 += m * (NY[c] * X[NX[c]] * Y[NY[c] - 1] * Z[NZ[c]]);
-        if (NZ[c] > 0) d2 += m * (NZ[c] * X[NX[c]] * Y[NY[c]] * Z[NZ[c] - 1]);
+    for (int e = 0; e < 9; ++e) E[e] = Ec[e][0] * x + Ec[e][1] * y + Ec[e][2] * z + Ec[e][3];
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i)
+#pragma unroll 1
+      for (int j = 0; j < 3; ++j) {
+        G[3 * i + j] = E[3 * i] * E[3 * j] + E[3 * i + 1] * E[3 * j + 1] + E[3 * i + 2] * E[3 * j + 2];  // E E^T
+        H[3 * i + j] = E[i] * E[j] + E[3 + i] * E[3 + j] + E[6 + i] * E[6 + j];                          // E^T E
       }
+    const double tr = G[0] + G[4] + G[8];
+#pragma unroll 1
+    for (int r = 0; r < 3; ++r) {
+      const int a = r == 2 ? 0 : r + 1, b = r == 0 ? 2 : r - 1;
+      cof[3 * r + 0] = E[3 * a + 1] * E[3 * b + 2] - E[3 * a + 2] * E[3 * b + 1];
+      cof[3 * r + 1] = E[3 * a + 2] * E[3 * b + 0] - E[3 * a + 0] * E[3 * b + 2];
+      cof[3 * r + 2] = E[3 * a + 0] * E[3 * b + 1] - E[3 * a + 1] * E[3 * b + 0];
+    }
+    // J'J and J'r one residual row at a time: the Jacobian is never held
+    double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    auto row = [&](double res, double d0, double d1, double d2) {
       a00 += d0 * d0;
       a01 += d0 * d1;
       a02 += d0 * d2;
@@ -106,6 +114,39 @@ __device__ void polish(const double (*M0)[20], double& x, double& y, double& z) 
       g0 += d0 * res;
       g1 += d1 * res;
       g2 += d2 * res;
+    };
+    double ed[3] = {0.0, 0.0, 0.0}, dd[3] = {0.0, 0.0, 0.0};  // <E, dE/dv> and the derivative of det E, dE/dv = Ec[.][v]
+#pragma unroll 1
+    for (int e = 0; e < 9; ++e) {
+#pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        ed[v] += E[e] * Ec[e][v];
+        dd[v] += cof[e] * Ec[e][v];
+      }
+    }
+    row(E[0] * cof[0] + E[1] * cof[1] + E[2] * cof[2], dd[0], dd[1], dd[2]);
+#pragma unroll 1
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll 1
+      for (int j = 0; j < 3; ++j) {
+        // the (i, j) loops stay rolled and their LDS loads inside them: hoisted, the loop-invariant operands alone take 100 VGPRs
+        __asm__ volatile("" ::: "memory");
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+          double dh = 0.0, fe = 0.0, gd = 0.0;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const double f = E[3 * i] * Ec[3 * k][v] + E[3 * i + 1] * Ec[3 * k + 1][v] + E[3 * i + 2] * Ec[3 * k + 2][v];  // (E dE^T)[i][k]
+            dh += Ec[3 * i + k][v] * H[3 * k + j];
+            fe += f * E[3 * k + j];
+            gd += G[3 * i + k] * Ec[3 * k + j][v];
+          }
+          dv[v] = 2.0 * (dh + fe + gd) - 2.0 * ed[v] * E[3 * i + j] - tr * Ec[3 * i + j][v];
+        }
+        __asm__ volatile("" ::: "memory");
+        const double res = 2.0 * (G[3 * i] * E[j] + G[3 * i + 1] * E[3 + j] + G[3 * i + 2] * E[6 + j]) - tr * E[3 * i + j];
+        row(res, dv[0], dv[1], dv[2]);
+      }
     }
     // (J'J) delta = -J'r by Cramer's rule
     const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
@@ -118,6 +159,8 @@ __device__ void polish(const double (*M0)[20], double& x, double& y, double& z) 
     x += dx;
     y += dy;
     z += dz;
+    // quadratic convergence: after a step this small the next one is below the rounding of (x, y, z)
+    if (fmax(fabs(dx), fmax(fabs(dy), fabs(dz))) <= 1e-9 * (1.0 + fmax(fabs(x), fmax(fabs(y), fabs(z))))) break;
   }
 }
 
@@ -142,7 +185,6 @@ struct SolveLds {
   double Ec[9][4];
   double T[10][64];
   double M[10][20];
-  double M0[10][20];  // the constraints before elimination: Gauss-Newton polish of each solution
   double fac[10];
   double D[11][11];   // p and its derivatives, coefficients ascending: D[k] = k-th derivative (degree n - k)
   double crit[12];    // sorted real roots of the level below (critical points of the current level), bracketed by -+bound
@@ -153,6 +195,7 @@ struct SolveLds {
   double Bz[6][10];   // rows 4..9 of the reduced system, basis part
   double sol[MAXS][9];
   int valid[MAXS];
+  double pw[MAXS][39];  // the polish's working set of each solution's lane
 };
 
 // the five-point solver for one sample, one 64-lane workgroup: x[5] = (u1, v1, u2, v2).  Writes the solutions ordered by
@@ -204,7 +247,6 @@ __device__ int solve5(SolveLds& L, const double4* x, double* E_out) {
       if (nister_col(ex, ey, ez) == col) s += L.T[r][t];
     }
     L.M[r][col] = s;
-    L.M0[r][col] = s;
   }
   __syncthreads();
   double mmax = 0.0;
@@ -257,11 +299,16 @@ __device__ int solve5(SolveLds& L, const double4* x, double* E_out) {
       pmax = fmax(pmax, fabs(L.D[0][i]));
     }
     int n = 10;
-    while (n > 0 && !(fabs(L.D[0][n]) > 1e-14 * pmax)) --n;
+    // solutions far out in z (|E[2,2]| small against E[2,1]) come with leading coefficients many orders below the largest one,
+    // so magnitude alone does not tell such a coefficient from a true zero computed as rounding noise: only one below 1e-30 of
+    // the largest lowers the degree.  A noise coefficient that stays adds a root near +-1e16, which the polish on E either
+    // turns into a solution or leaves to the det E guard; its bracket of up to +-2e30 is why the bisection below may take 300
+    // halvings (2e30 down to a root of 1e-10 at full precision takes about 240)
+    while (n > 0 && !(fabs(L.D[0][n]) > 1e-30 * pmax)) --n;
     L.n = (pmax > 0.0) ? n : 0;
     double cb = 0.0;
-    for (int i = 0; i < n; ++i) cb = fmax(cb, fabs(L.D[0][i] / L.D[0][n]));
-    L.bound = 1.0 + cb;  // Cauchy: every root of p (and, by Gauss-Lucas, of its derivatives) lies inside
+    for (int k = 1; k <= n; ++k) cb = fmax(cb, pow(fabs(L.D[0][n - k] / L.D[0][n]), 1.0 / k));
+    L.bound = 2.0 * cb + 1.0;  // Fujiwara: every root of p (and, by Gauss-Lucas, of its derivatives) lies inside
     for (int k = 1; k <= n; ++k)
       for (int i = 0; i <= n - k; ++i) L.D[k][i] = (i + 1) * L.D[k - 1][i + 1];
     L.ncrit = 0;
@@ -284,7 +331,7 @@ __device__ int solve5(SolveLds& L, const double4* x, double* E_out) {
         got = 1;
       } else if (flo != 0.0 && ((flo < 0.0) != (fhi < 0.0)) && lo < hi) {
         const bool neg_lo = flo < 0.0;
-        for (int it = 0; it < 200; ++it) {
+        for (int it = 0; it < 300; ++it) {
           const double mid = 0.5 * (lo + hi);
           if (!(mid > lo && mid < hi)) break;
           const double fm = horner(c, dk, mid);
@@ -342,7 +389,7 @@ __device__ int solve5(SolveLds& L, const double4* x, double* E_out) {
       }
     }
     double sx = cx / cz, sy = cy / cz;
-    polish(L.M0, sx, sy, z);
+    polish(L.Ec, L.pw[lane], sx, sy, z);
     bool good = true;
     double ev[9], en = 0.0;
 #pragma unroll

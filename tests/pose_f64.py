@@ -113,18 +113,23 @@ def constraints(Ec):
     return T.reshape(10, 64) @ _P64
 
 
-def _polish(M, p, steps=4):
-    """Gauss-Newton on the ten cubics from an eigenpair's (x, y, z): eigenvectors alone lose digits on ill-conditioned samples"""
-    E = np.array(ALL, dtype=float)
+def _polish(Ec, p, steps=6):
+    """Gauss-Newton on det E = 0 and 2 E E^T E - tr(E E^T) E = 0 from an eigenpair's (x, y, z), evaluated on E(x, y, z) itself:
+    eigenvectors alone lose digits on ill-conditioned samples, and the cubics expanded over the monomials (`constraints`) carry
+    coefficients of |Ec|^3 that cancel, which leaves E 1e-8 off the essential variety there"""
+    B = Ec.reshape(3, 3, 4)
     for _ in range(steps):
-        mon = np.prod(p[None] ** E, 1)
-        J = np.zeros((20, 3))
+        E = B @ np.array([p[0], p[1], p[2], 1.0])
+        EEt = E @ E.T
+        tr = np.trace(EEt)
+        r = np.concatenate([[np.linalg.det(E)], (2.0 * EEt @ E - tr * E).ravel()])
+        C = cofactor(E)
+        J = np.zeros((10, 3))
         for v in range(3):
-            d = E.copy()
-            d[:, v] -= 1
-            J[:, v] = np.where(E[:, v] > 0, E[:, v] * np.prod(p[None] ** np.maximum(d, 0), 1), 0.0)
-        r = M @ mon
-        step = np.linalg.lstsq(M @ J, -r, rcond=None)[0]
+            D = B[:, :, v]
+            J[0, v] = np.sum(C * D)
+            J[1:, v] = (2.0 * (D @ E.T @ E + E @ D.T @ E + EEt @ D) - 2.0 * np.sum(E * D) * E - tr * D).ravel()
+        step = np.linalg.lstsq(J, -r, rcond=None)[0]
         if not np.all(np.isfinite(step)):
             break
         p = p + step
@@ -154,7 +159,7 @@ def solve5(x1, x2):
         v = V[:, k].real
         if not abs(v[9]) > 0:
             continue
-        xyz = _polish(M, np.array([w[k].real, v[7] / v[9], v[8] / v[9]]))
+        xyz = _polish(Ec, np.array([w[k].real, v[7] / v[9], v[8] / v[9]]))
         E = Ec @ np.array([xyz[0], xyz[1], xyz[2], 1.0])
         if not np.all(np.isfinite(E)):
             continue

@@ -61,9 +61,9 @@ def batch():
     return pairs, args, out, ref
 
 
-# forward driving with 30 % outliers: the kernel's scan takes iteration 73, the restatement's iteration 57 (a hypothesis whose
-# inlier count differs between the two solver routes on this far-out (x, y, z) solution); both poses meet the ground-truth bound
-ITER_DIFFERS = {17}
+# pairs whose chosen iteration differs between the two solver routes for an understood reason (none: pair 17, forward driving
+# with 30 % outliers, was pinned here until the degree-10 polynomial kept its small leading coefficients)
+ITER_DIFFERS = set()
 
 
 def test_kernel_matches_restatement(batch):
@@ -82,6 +82,7 @@ def test_kernel_matches_restatement(batch):
         # the chosen iteration must agree; the solution's index inside the sample may not (a root that one route keeps and the
         # other loses to the det E guard shifts the indices), the model itself is compared through R and t below
         assert status[b] >= 0 and (status[b] >> 4) == it, (b, status[b], r["it"])
+        assert not mask[b, n:].any(), b  # past the pair's matches the mask is zero
         diff = np.nonzero(mask[b, :n] != r["mask"])[0]
         if len(diff):  # allowed only where the float64 error sits within 1e-6 (relative) of thr^2: reported
             a0, a1, K0, K1 = pairs[b][:4]
@@ -90,7 +91,7 @@ def test_kernel_matches_restatement(batch):
             _, e64 = P.sampson_f32(r["E"], x1, x2)
             assert np.all(np.abs(e64[diff] - thr2) <= 1e-6 * thr2), f"pair {b}: mask differs at {diff[:10]}"
             near.append((b, diff.tolist()))
-        # both solver routes polish every solution by Gauss-Newton on the ten cubics
+        # both solver routes polish every solution by Gauss-Newton on the essential constraints of E itself
         e = P.pose_errors(pairs[b][4], r["R"], r["t"])
         d = (np.abs(R[b] - r["R"]).max(), min(np.abs(t[b] - r["t"]).max(), np.abs(t[b] + r["t"]).max()), np.abs(rows[b, :3] - e).max())
         worst = [max(w, v) for w, v in zip(worst, d)]
@@ -111,7 +112,7 @@ def test_ground_truth_bounds(batch):
             assert rows[b, 3] == 1.0, (b, rows[b])
 
 
-LOST_ROOTS = {9: 4}  # problem 9: four real roots within 0.11 of each other (z = -1.4947 .. -1.3913): the device finds none
+LOST_ROOTS = {9: 2}  # problem 9: four real roots within 0.11 of each other (z = -1.4947 .. -1.3913): the device finds two
 
 
 def test_essential_5pt_matches_restatement():
