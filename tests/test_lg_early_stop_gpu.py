@@ -17,7 +17,7 @@ import torch
 
 import lg_early_stop_ref as R
 import test_lightglue_f64_gpu as T
-from helpers import lgf64_pair, lgf64_shipped_state_dict, synth, synth_raw_events
+from helpers import lgf64_pair, lgf64_shipped_state_dict, state_dict_for, synth, synth_raw_events
 from gpu_support import DEV, _np, _t, pkg
 
 pytestmark = pytest.mark.gpu
@@ -27,6 +27,12 @@ SHIFTS = {3: 2.0, 7: 1.0}
 SIZE = (260, 346)
 STACKED = [(31, 33), (64, 64), (130, 130), (1, 1), (0, 5)]  # cap0 == cap1 == 130: the sides stacked, one launch over 2B entries
 UNSTACKED = [(129, 300), (40, 300), (31, 33), (5, 0)]  # cap0 = 129, cap1 = 300: one launch per side
+# The one cell of the GEMM launch table that no shipped-width case reaches at test sizes: EPI_DIV_HEAD on the WIDE
+# kernel.  d = 96 (3 heads of 32) is no multiple of the small kernel's 64 columns, so every linear of this model runs lg_gemm_kernel
+# whatever the grid; three layers, token bias 0 at -30 and 1 at +30: every pair with rows stops after layer 2, far from any
+# threshold, and is read by head 1 (not the last one); the empty pair keeps stop = 0
+OTHER_WIDTH = dict(input_dim=96, descriptor_dim=96, num_heads=3, n_layers=3)
+OTHER_WIDTH_COUNTS = [(129, 130), (33, 1), (0, 130)]  # stacked at cap 130
 
 
 def _state_dict(shifts=SHIFTS):
@@ -84,6 +90,28 @@ class World:
             assert torch.equal(pb0.counts, n0) and torch.equal(pb1.counts, m0)  # the caller's counts are never written
             ref = [R.run(self.sd, *p[:4], DEPTH) for p in pairs]
             self.cases[name] = dict(counts=counts, pairs=pairs, r=r, stop=_np(r.stop).tolist(), ref=ref, pb=(pb0, pb1))
+
+    def other_width(self):
+        """the d = 96 case, built when its test asks for it"""
+        if "other_width" not in self.cases:
+            probe = pkg.LightGlue(OTHER_WIDTH).to(DEV)
+            sd = state_dict_for(dict(wseed=829, state_keys={k: list(v.shape) for k, v in probe.state_dict().items()}))
+            for i, v in ((0, -30.0), (1, 30.0)):
+                sd[f"token_confidence.{i}.token.0.bias"] = np.full_like(sd[f"token_confidence.{i}.token.0.bias"], v)
+            lg = T._model(dict(OTHER_WIDTH, depth_confidence=DEPTH), sd)
+            lg.early_stop = True
+            pairs = []
+            for b, (n, m) in enumerate(OTHER_WIDTH_COUNTS):
+                d0, d1, k0, k1 = lgf64_pair(40 + b, max(n, 1), max(m, 1), 96)
+                pairs.append((k0[:n], d0[:n], k1[:m], d1[:m], SIZE, SIZE))
+            pb0 = T._batch([p[0] for p in pairs], [p[1] for p in pairs], 130, SIZE)
+            pb1 = T._batch([p[2] for p in pairs], [p[3] for p in pairs], 130, SIZE, dfill=-3.0)
+            r = lg.match_batched(pb0, pb1)
+            torch.cuda.synchronize()
+            ref = [R.run(sd, *p[:4], DEPTH) for p in pairs]
+            self.cases["other_width"] = dict(counts=OTHER_WIDTH_COUNTS, pairs=pairs, r=r, stop=_np(r.stop).tolist(), ref=ref, pb=(pb0, pb1), sd=sd,
+                                             conf=OTHER_WIDTH)
+        return self.cases["other_width"]
 
     def model_of(self, stop):
         if stop not in self.truncated:
@@ -153,17 +181,21 @@ def test_each_pair_equals_the_truncated_model_alone(world, name):
 
 
 # ------------------------------------------------------------------------------------------------ 4. against float64
-@pytest.mark.parametrize("name", ["stacked", "unstacked"])
+@pytest.mark.parametrize("name", ["stacked", "unstacked", "other_width"])
 def test_each_pair_against_float64(world, oracle, name):
     """the rules of test_lightglue_f64_gpu._check_pair (la_bound_f64 over the float32 peers, the float64 decision margins), applied
-    with the truncated state dict: its full-depth float64 forward IS the restatement of a pair that stopped there"""
-    c = world.cases[name]
+    with the truncated state dict: its full-depth float64 forward IS the restatement of a pair that stopped there.  other_width:
+    the wide kernel's EPI_DIV_HEAD (see OTHER_WIDTH), every decision safe and as the restatement takes it"""
+    c = world.other_width() if name == "other_width" else world.cases[name]
+    sd, conf = c.get("sd", world.sd), c.get("conf", T.SHIPPED)
+    if name == "other_width":
+        assert all(all(ref["safe"]) for ref in c["ref"]) and c["stop"] == [ref["stop"] for ref in c["ref"]] == [2, 2, 0]
     for b, (n, m) in enumerate(c["counts"]):
         stop = c["stop"][b]
         if stop == 0:
             continue
-        sdt = R.truncated_state_dict(world.sd, stop)
-        ex = T._check_pair(f"lg_early_stop.{name}.{b}", sdt, dict(T.SHIPPED, n_layers=stop), c["pairs"][b], _cut(c["r"], b, n, m), oracle)
+        sdt = R.truncated_state_dict(sd, stop)
+        ex = T._check_pair(f"lg_early_stop.{name}.{b}", sdt, dict(conf, n_layers=stop), c["pairs"][b], _cut(c["r"], b, n, m), oracle)
         assert np.array_equal(ex["log_assignment"], c["ref"][b]["log_assignment"])
         x0 = c["ref"][b]["x0"]
         assert np.abs(_cut(c["r"], b, n, m)["ref0"] - x0).max() <= 1e-3 * max(1.0, np.abs(x0).max())  # (a sanity check; the bits are test 3's)
