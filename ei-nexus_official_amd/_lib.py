@@ -58,6 +58,13 @@ class MetricParams(ctypes.Structure):
                [("mma_thr", c_float * 4), ("vdd_thr", c_float * 4), ("rep_nan_if_empty", ctypes.c_int32)]
 
 
+class PoseMetricParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + \
+               [(n, ctypes.c_int32) for n in ("B", "cap0", "cap1", "D", "cols", "H0", "W0", "H1", "W1", "dH0", "dW0", "dH1", "dW1", "kp_yx",
+                                              "n_mma", "n_vdd", "n_epi")] + \
+               [("mma_thr", c_float * 4), ("vdd_thr", c_float * 4), ("epi_thr", c_float * 4), ("occlusion_th", c_float)]
+
+
 class PoseParams(ctypes.Structure):
     _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap", "cols", "kp_yx", "k_f64", "max_iters")] + \
                [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("seed", ctypes.c_uint64)]
@@ -190,6 +197,8 @@ SIGNATURES = {
     "einx_events_pack": (c_int, [ctypes.POINTER(EventArrays), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "einx_metrics_ws_bytes": (c_size_t, [ctypes.POINTER(MetricParams)]),
     "einx_pair_metrics": (c_int, [ctypes.POINTER(MetricParams)] + [c_void_p] * 13),
+    "einx_pair_metrics_pose_ws_bytes": (c_size_t, [ctypes.POINTER(PoseMetricParams)]),
+    "einx_pair_metrics_pose": (c_int, [ctypes.POINTER(PoseMetricParams)] + [c_void_p] * 18),
     "einx_relative_pose_ws_bytes": (c_size_t, [ctypes.POINTER(PoseParams)]),
     "einx_relative_pose": (c_int, [ctypes.POINTER(PoseParams)] + [c_void_p] * 13),
     "einx_essential_5pt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

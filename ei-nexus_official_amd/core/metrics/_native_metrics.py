@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseParams, check
+from ..._lib import GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -51,6 +51,69 @@ def batch_metrics(ev, im, mr, homography=None, mma_thr=(1, 3), vdd_thr=(1, 3)):
     """Metrics for a whole EIM.forward_batched result (BatchedFeats x2 + MatchResult), no host sync."""
     return pair_metrics(ev.det.positions, ev.sparse_desc, ev.det.counts, im.det.positions, im.sparse_desc, im.det.counts, mr.mk0, mr.mk1,
                         mr.nmatch, ev.image_size, im.image_size, homography, mma_thr, vdd_thr, ordering=ev.ordering)
+
+
+def pose_metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), epi_thr=()):
+    """the columns of pair_metrics_pose: DT_ for what is measured through depth and motion, EPI@t for the motion alone"""
+    names = ["MR"] + [f"DT_MMA@{t}" for t in mma_thr] + ["DT_judged_ratio"]
+    for t in vdd_thr:
+        names += [f"DT_Repeatability@{t}", f"DT_ValidDistance@{t}", f"DT_Angle@{t}"]
+    return names + [f"EPI@{t}" for t in epi_thr]
+
+
+@on_input_device
+def pair_metrics_pose(kpts0, desc0, n, kpts1, desc1, m, mk0, mk1, nmatch, size0, size1, K0, K1, T_0to1, T_1to0=None, depth0=None,
+                      depth1=None, mma_thr=(1, 3), vdd_thr=(1, 3), epi_thr=(), occlusion_th=None, ordering="yx"):
+    """pair_metrics for a pair related by depth and motion instead of a homography (einx_pair_metrics_pose), no host
+    sync.  Keypoints, descriptors, counts and matched rows as pair_metrics takes them; size0 / size1 the image sizes (H, W);
+    K0 / K1 [B,3,3], T_0to1 [B,4,4] (T_1to0 None: inverted in the kernel); depth0 [B,dH0,dW0] and depth1 [B,dH1,dW1], both or
+    neither -- without them only MR and EPI@t are finite.  occlusion_th (pixels; None or <= 0: off) drops what the other view's depth
+    map says is hidden.  Returns float64 [B, 2 + len(mma_thr) + 3 * len(vdd_thr) + len(epi_thr)] (see pose_metric_names)."""
+    if (depth0 is None) != (depth1 is None):
+        raise ValueError("einx: pair_metrics_pose takes both depth maps or neither")
+    mma_thr, vdd_thr, epi_thr = tuple(mma_thr), tuple(vdd_thr), tuple(epi_thr)
+    if max(len(mma_thr), len(vdd_thr), len(epi_thr)) > 4:
+        raise ValueError("einx: at most 4 thresholds per metric")
+    B, cap0, _ = kpts0.shape
+    dev = kpts0.device
+    p = PoseMetricParams()
+    p.struct_size = ctypes.sizeof(PoseMetricParams)
+    p.B, p.cap0, p.cap1, p.D, p.cols = B, cap0, kpts1.shape[1], desc0.shape[-1], mk0.shape[-1]
+    p.H0, p.W0, p.H1, p.W1 = int(size0[0]), int(size0[1]), int(size1[0]), int(size1[1])
+    p.kp_yx = int(ordering == "yx")
+    p.n_mma, p.n_vdd, p.n_epi = len(mma_thr), len(vdd_thr), len(epi_thr)
+    for dst, thr in ((p.mma_thr, mma_thr), (p.vdd_thr, vdd_thr), (p.epi_thr, epi_thr)):
+        for i, t in enumerate(thr):
+            dst[i] = float(t)
+    p.occlusion_th = 0.0 if occlusion_th is None else float(occlusion_th)
+    d0 = d1 = None
+    if depth0 is not None:
+        d0, d1 = (d.to(dev, torch.float32).reshape(B, d.shape[-2], d.shape[-1]).contiguous() for d in (depth0, depth1))
+        p.dH0, p.dW0, p.dH1, p.dW1 = d0.shape[1], d0.shape[2], d1.shape[1], d1.shape[2]
+    K0, K1, T01 = _f32c(K0, dev, (B, 9)), _f32c(K1, dev, (B, 9)), _f32c(T_0to1, dev, (B, 16))
+    T10 = None if T_1to0 is None else _f32c(T_1to0, dev, (B, 16))
+    L = N.lib()
+    nbytes = L.einx_pair_metrics_pose_ws_bytes(ctypes.byref(p))
+    if nbytes == 0:
+        raise ValueError("einx: pair_metrics_pose: bad shape (sizes must be positive, matched rows have 2 or 3 columns)")
+    ws = N._workspace(nbytes, dev)
+    out = torch.empty((B, 2 + p.n_mma + 3 * p.n_vdd + p.n_epi), dtype=torch.float64, device=dev)
+    N._dev_check(kpts0, kpts1, desc0, desc1, mk0, mk1)
+    N._dev_check(n, m, nmatch, dt=torch.int32)
+    P = N._ptr
+    check(L.einx_pair_metrics_pose(ctypes.byref(p), P(kpts0), P(kpts1), P(desc0), P(desc1), P(n), P(m), P(mk0), P(mk1), P(nmatch), P(d0), P(d1),
+                                   P(K0), P(K1), P(T01), P(T10), P(ws), P(out), N._stream(kpts0)), "einx_pair_metrics_pose")
+    return out
+
+
+@on_input_device
+def batch_metrics_pose(ev, im, mr, K0, K1, T_0to1, depth=None, T_1to0=None, mma_thr=(1, 3), vdd_thr=(1, 3), epi_thr=(), occlusion_th=None):
+    """pair_metrics_pose for a whole EIM.forward_batched result (BatchedFeats x2 + MatchResult; events = view 0, image = view 1),
+    depth = (depth0, depth1) or None, no host sync."""
+    d0, d1 = depth if depth is not None else (None, None)
+    return pair_metrics_pose(ev.det.positions, ev.sparse_desc, ev.det.counts, im.det.positions, im.sparse_desc, im.det.counts, mr.mk0, mr.mk1,
+                             mr.nmatch, ev.image_size, im.image_size, K0, K1, T_0to1, T_1to0, d0, d1, mma_thr, vdd_thr, epi_thr, occlusion_th,
+                             ordering=ev.ordering)
 
 
 def _pad3(k):

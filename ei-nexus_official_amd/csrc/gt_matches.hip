@@ -4,7 +4,8 @@
 // Replaces (reference file:line): core/geometry/gt_generation.py:15-224 (gt_matches_from_pose_depth, gt_matches_from_homography),
 // core/geometry/depth.py:9-60 (sample_depth, project with ccth=None), core/geometry/wrappers.py:337-385 (pinhole cam2image),
 // core/modules/matchers/lightglue.py:17-63 (matcher_metrics).
-//   stage A  gt_project_kernel / gt_warp_kernel: one thread per keypoint, both directions in one launch
+//   stage A  gt_project_kernel / gt_warp_kernel: one thread per keypoint, both directions in one launch (the depth sampler and the
+//            projection are gt_project.h's, shared with metrics.hip)
 //   stage B  gt_label_kernel: one thread per row (column), the other side staged in LDS and read with broadcast loads; no N x M
 //            intermediate; gt_finalize_kernel: mutual check + the three-way label
 //   stage C  match_pr_kernel: one wave per pair
@@ -14,6 +15,7 @@
 // fp32, unfused (-ffp-contract=off).  No floating-point atomics (the dense counts are integer sums): two runs give the same bits.
 // Every launch goes on the caller's stream.
 #include "einx_common.h"
+#include "gt_project.h"
 
 namespace {
 
@@ -37,80 +39,6 @@ struct GtSide {
   uint8_t* vis;         // [B,cap]
   int cap, cols, H, W;
 };
-
-// sample_depth (depth.py:9-25): bilinear with zero padding at ix = x - 0.5; a hole (<= 0 or NaN) under a tap of non-zero weight
-// sends the whole sample to the nearest pixel (half to even), NaN when that is a hole, 0 outside the map
-__device__ __forceinline__ float gt_sample_depth(const float* dm, int H, int W, float x, float y) {
-  const float nan = einx_u2f(0x7fc00000u);
-  const float ix = x - 0.5f, iy = y - 0.5f;
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  const float tx = ix - fx0, ty = iy - fy0;
-  // floorf of anything outside the int range (or NaN) is clamped so that the casts are defined: every tap is then outside the map
-  const int x0 = fx0 >= -2.0f && fx0 <= (float)W ? (int)fx0 : -2;
-  const int y0 = fy0 >= -2.0f && fy0 <= (float)H ? (int)fy0 : -2;
-  const float wx[2] = {(fx0 + 1.0f) - ix, tx};
-  const float wy[2] = {(fy0 + 1.0f) - iy, ty};
-  float acc = 0.0f;
-  bool hole = false;
-#pragma unroll
-  for (int dy = 0; dy < 2; ++dy) {
-#pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {  // nw, ne, sw, se
-      const int xx = x0 + dx, yy = y0 + dy;
-      if (xx < 0 || xx >= W || yy < 0 || yy >= H) continue;
-      const float w = wx[dx] * wy[dy];
-      const float v = dm[(size_t)yy * W + xx];
-      if (!(v > 0.0f)) {
-        if (w != 0.0f) hole = true;
-        continue;
-      }
-      acc = acc + v * w;
-    }
-  }
-  if (!hole && ix == ix && iy == iy) return acc;
-  const float nx = nearbyintf(ix), ny = nearbyintf(iy);  // round half to even (the default rounding mode)
-  if (!(nx >= 0.0f && nx < (float)W && ny >= 0.0f && ny < (float)H)) return 0.0f;
-  const float v = dm[(size_t)(int)ny * W + (int)nx];
-  return v > 0.0f ? v : nan;
-}
-
-// depth.py:37-60 with ccth=None for one point (x, y) of depth d: image2cam, scale by the depth, transform by T (this view -> the
-// other; null: (R^T, -R^T t) of T_other), pinhole cam2image of the other camera Ko.  (u, v) is the projection, NaN where d is; the
-// return value is "in front of the other camera and inside its image"
-__device__ __forceinline__ bool gt_project_point(float x, float y, float d, const float* Ks, const float* Ko, const float* T,
-                                                 const float* T_other, float* u_out, float* v_out) {
-  float R[9], t[3];
-  if (T) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) R[3 * q + c] = T[4 * q + c];
-      t[q] = T[4 * q + 3];
-    }
-  } else {  // (R^T, -R^T t) of the other direction
-    T = T_other;
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) R[3 * q + c] = T[4 * c + q];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) t[q] = -((R[3 * q] * T[3] + R[3 * q + 1] * T[7]) + R[3 * q + 2] * T[11]);
-  }
-  // image2cam, scale by the depth, transform, cam2image (pinhole)
-  const float px = ((x - Ks[2]) / Ks[0]) * d, py = ((y - Ks[5]) / Ks[4]) * d, pz = d;
-  const float qx = ((px * R[0] + py * R[1]) + pz * R[2]) + t[0];
-  const float qy = ((px * R[3] + py * R[4]) + pz * R[5]) + t[1];
-  const float qz = ((px * R[6] + py * R[7]) + pz * R[8]) + t[2];
-  const bool front = qz > 1e-4f;
-  const float z = qz < 1e-4f ? 1e-4f : qz;  // clamp(min=eps): NaN stays NaN
-  const float u = (qx / z) * Ko[0] + Ko[2];
-  const float v = (qy / z) * Ko[4] + Ko[5];
-  // the camera's size is (2 cx, 2 cy) (Camera.from_calibration_matrix), not the depth map's
-  const float wmax = 2.0f * Ko[2] - 1.0f, hmax = 2.0f * Ko[5] - 1.0f;
-  *u_out = u;
-  *v_out = v;
-  return front && u >= 0.0f && u <= wmax && v >= 0.0f && v <= hmax;
-}
 
 struct GtProjArgs {
   GtSide s[2];

@@ -28,8 +28,8 @@ import numpy as np
 import torch
 
 from . import _native as native
-from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, batch_homography, batch_metrics, batch_relative_pose, match_pr,
-                                            metric_names)
+from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, batch_homography, batch_metrics, batch_metrics_pose,
+                                            batch_relative_pose, match_pr, metric_names, pose_metric_names)
 from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
@@ -385,6 +385,14 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
       the forward's last-layer descriptors and the batch's labels, with no host synchronisation; result() adds matcher_loss (the
       mean of losses["total"]), matcher_nll_pos, matcher_nll_neg and matcher_row_norm over the pairs that have keypoints on both
       sides.  With the default nothing is launched and result() is unchanged.
+    * `reproj_thr=(1, 3)` / `epi_thr=(1, 3)` / `occlusion_th=` (all None by default: nothing is launched, rows and
+      result() are unchanged).  The inherited MMA@t / VDD_* warp view 0 with a homography (None: the identity), which a pair with
+      parallax does not have.  With `reproj_thr`, a batch that carries pose and depth also measures them through the depth maps and
+      the motion (einx_pair_metrics_pose): result() gains DT_MMA@t, DT_judged_ratio, DT_Repeatability@t, DT_ValidDistance@t and
+      DT_Angle@t.  With `epi_thr`, a batch that carries pose gains EPI@t, the share of matches within t pixels of their epipolar
+      lines (no depth needed).  One call serves both; each key is the mean over the pairs where it is finite and appears once some
+      pair gave a finite value.  `occlusion_th` (pixels) drops keypoints and matches the other view's depth map says are hidden;
+      without `reproj_thr` it raises.  The returned rows are unchanged.
     * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
       RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
       all-gathered before the AUC.  Once depth was given: the four matcher_metrics means over the pairs that have keypoints.
@@ -395,7 +403,12 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
                  ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None,
-                 matcher_loss=False):
+                 matcher_loss=False, reproj_thr=None, epi_thr=None, occlusion_th=None):
+        if occlusion_th is not None and reproj_thr is None:
+            raise ValueError("einx: occlusion_th needs reproj_thr: the occlusion check belongs to the depth form of the metrics")
+        for name, thr in (("reproj_thr", reproj_thr), ("epi_thr", epi_thr)):
+            if thr is not None and not 1 <= len(tuple(thr)) <= 4:
+                raise ValueError(f"einx: {name} takes 1 to 4 thresholds")
         if losses is not None:
             raise ValueError("einx: DifferentTimeEvaluator takes no losses: its two views are not aligned pixel by pixel, which is what "
                              "the extractor losses compare (SameTimeEvaluator does)")
@@ -412,6 +425,12 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
             raise ValueError("einx: matcher_loss=True needs a LightGlue matcher: the loss is that of its assignment head (an MNN "
                              "matcher has no parameters and no loss in the validation loop)")
         self._nll_mean = _RunningMean(len(MATCHER_LOSS_NAMES), finite_only=True)  # of the [B,4] rows of matcher_loss_rows
+        # the depth / motion form of the metrics: one row layout for every batch, NaN where a batch had no depth
+        self.reproj_thr = None if reproj_thr is None else tuple(reproj_thr)
+        self.epi_thr = None if epi_thr is None else tuple(epi_thr)
+        self.occlusion_th = None if occlusion_th is None else float(occlusion_th)
+        self.dt_names = pose_metric_names(self.reproj_thr or (), self.reproj_thr or (), self.epi_thr or ())[1:]  # without MR
+        self._dt_mean = _RunningMean(len(self.dt_names), finite_only=True)
 
     @torch.no_grad()
     def step(self, events_list, images, homography=None, pose=None, depth=None):
@@ -443,6 +462,11 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
             K0, K1, T = batch.pose
             self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
                                                        ordering=ef._batched.ordering)[4])
+            depth = batch.depth if self.reproj_thr is not None else None
+            if depth is not None or self.epi_thr is not None:  # one call for the depth form and the EPI columns
+                rows = batch_metrics_pose(ef._batched, imf._batched, self.model._last_match, K0, K1, T, depth, None, self.reproj_thr or (),
+                                          self.reproj_thr or (), self.epi_thr or (), self.occlusion_th)
+                self._dt_mean.add(rows[:, 1:])
         return out
 
     def result(self):
@@ -455,6 +479,10 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
             s, c = self._nll_mean.reduced(self.sums.device)
             if float(c.max()) > 0:  # some rank had a pair with keypoints on both sides
                 out.update(zip(MATCHER_LOSS_NAMES, _RunningMean.means(s, c)))
+        if self.reproj_thr is not None or self.epi_thr is not None:
+            s, c = self._dt_mean.reduced(self.sums.device)
+            means = _RunningMean.means(s, c)
+            out.update({k: v for k, v, cnt in zip(self.dt_names, means, c.tolist()) if cnt > 0})  # once a pair gave a finite value
         return out
 
     def pose_inputs(self, matches, b=0):

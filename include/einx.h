@@ -739,6 +739,55 @@ int einx_pair_metrics(const einx_metric_params* p, const float* kpts0, const flo
                       const float* homography, void* ws, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same metrics for a pair related by depth + motion instead of a homography (csrc/metrics.hip): what
+ * the different-time evaluation (test_events-image_different_time.py:187-264) can say about keypoints and matches under the
+ * geometry it has.  The reference has no such metric; each part restates reference text:
+ *   sample_depth, project (ccth= branch: the occlusion check)   core/geometry/depth.py:9-69
+ *   pinhole cam2image                                           core/geometry/wrappers.py:337-385
+ *   keep_true_points (inside the other IMAGE)                   core/metrics/util.py:43-70
+ *   MeanMatchingAccuracy / ValidDescriptorsDistance rules       core/metrics/matching_metrics.py:84-156, keypoints_metrics.py:160-290
+ *   sym_epipolar_distance_all (F = K1^-T [t]x R K0^-1)          core/geometry/epipolar.py:59-80, gt_generation.py:128-133
+ * Inputs as einx_pair_metrics takes them, with depth0 [B,dH0,dW0] / depth1 [B,dH1,dW1] float32 (BOTH NULL or both given), K0 / K1
+ * [B,9], T_0to1 [B,16] float32 and T_1to0 [B,16] or NULL ((R^T, -R^T t) of T_0to1, as 8e).  A keypoint of view 0 goes through
+ * depth0 and T_0to1 into view 1 with 8e stage A's sampler and projection, bit for bit; it is kept when its depth is valid, it lies
+ * in front of camera 1 (q.z > 1e-4) and 0 <= u < W1, 0 <= v < H1; view 1 likewise into image 0.  occlusion_th > 0 adds the
+ * reference's circle-consistency test: the other map sampled at (u, v), back-projected with the inverse motion, must be valid, in
+ * front and within occlusion_th PIXELS of the keypoint (squared on both sides; the reference compares the squared distance with
+ * the unsquared ccth).
+ * out: [B, 1 + n_mma + 1 + 3 n_vdd + n_epi] float64 =
+ *   MR                                 as einx_pair_metrics
+ *   MMA@t...                           #(judged and |proj(mk0) - mk1| <= t) / #judged, judged = valid and in front (and the occlusion
+ *                                      test); a match whose true location left the image is wrong, not unjudged
+ *   judged_ratio                       #judged / M
+ *   (Repeatability, ValidDistance, Angle)@t...   einx_pair_metrics' rule on the projected / kept keypoints
+ *   EPI@t...                           #(symmetric epipolar distance <= t) / M, the distance in double, pixels; needs no depth.  A
+ *                                      pure rotation has F = 0: every match passes
+ * Quotients of counts are float32 quotients.  A quotient with an empty denominator is NaN (nothing could be judged): MMA@t without
+ * a judged match, judged_ratio / EPI@t for M == 0, the VDD triple when either view keeps no keypoint.  With the depth pointers
+ * NULL everything but MR and EPI@t is NaN and nothing is sampled.  Workspace O(B (cap0 + cap1)), no N x M term; integer atomics
+ * only: two runs give the same bits.  Nothing synchronises or allocates; the call can be captured.
+ * EINX_ERR_ARG (and a workspace query of 0): wrong struct_size, more than 4 thresholds of a kind, cols outside {2, 3}, a
+ * non-positive size; the call also refuses exactly one depth pointer.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_pose_metric_params {
+  size_t struct_size;         /* sizeof(einx_pose_metric_params) (checked) */
+  int32_t B, cap0, cap1, D, cols;
+  int32_t H0, W0, H1, W1;     /* image sizes: the bound of "inside the other image" */
+  int32_t dH0, dW0, dH1, dW1; /* sizes of depth0 / depth1 (unused when they are NULL) */
+  int32_t kp_yx;              /* 1: keypoints are (y,x,..) */
+  int32_t n_mma, n_vdd, n_epi; /* thresholds of each kind (0..4) */
+  float mma_thr[4];
+  float vdd_thr[4];
+  float epi_thr[4];
+  float occlusion_th;         /* pixels; <= 0: no occlusion check */
+} einx_pose_metric_params;
+size_t einx_pair_metrics_pose_ws_bytes(const einx_pose_metric_params* p); /* 0 on refused parameters */
+int einx_pair_metrics_pose(const einx_pose_metric_params* p, const float* kpts0, const float* kpts1, const float* desc0, const float* desc1,
+                           const int32_t* n, const int32_t* m, const float* mk0, const float* mk1, const int32_t* nmatch,
+                           const float* depth0, const float* depth1, const float* K0, const float* K1, const float* T_0to1,
+                           const float* T_1to0, void* ws, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Relative pose of the different-time evaluation (csrc/pose.hip)
  *   RelativePoseEstimation   core/metrics/matching_metrics.py:347-559 (cv2.findEssentialMat RANSAC + cv2.recoverPose)
  * B pairs of matched keypoints mk0 / mk1 [B,cap,cols] float32 + nmatch int32 [B] (einx_gather_matches' layout), K0 / K1
