@@ -195,6 +195,14 @@ SIGNATURES = {
     "einx_events_mask_windows": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                          c_void_p]),
     "einx_events_pack": (c_int, [ctypes.POINTER(EventArrays), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "einx_rectify_map_fisheye": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_rectify_map_radtan": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_undistort_points_map_radtan": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_remap_bilinear": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "einx_events_remap_ws_bytes": (c_size_t, [ctypes.c_int64]),
+    "einx_events_remap": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int, c_int, c_float, c_float,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "einx_events_remap_chunk": (c_int, []),
     "einx_metrics_ws_bytes": (c_size_t, [ctypes.POINTER(MetricParams)]),
     "einx_pair_metrics": (c_int, [ctypes.POINTER(MetricParams)] + [c_void_p] * 13),
     "einx_pair_metrics_pose_ws_bytes": (c_size_t, [ctypes.POINTER(PoseMetricParams)]),

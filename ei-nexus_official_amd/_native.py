@@ -769,3 +769,69 @@ def logits_loss(x, y, cell, crop=None, mask=None):
     check(L.einx_logits_loss(_ptr(x), _ptr(y), B, C, int(cell), hc, wc, h0, w0, H, W, _ptr(m), mt, _ptr(out), _ptr(ws), nws, _stream(x)),
           "einx_logits_loss")
     return out
+
+
+def _f64(values, n, what):
+    """n host doubles for the map builders' K / D / R / P arguments"""
+    a = np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1))
+    if a.size != n:
+        raise ValueError(f"einx: {what} must hold {n} values, got {a.size}")
+    return a
+
+
+def rectify_map(model, K, D, R, P, H, W, device, iters=5, round_out=False):
+    """(map_x, map_y) [H,W] fp32 of einx_rectify_map_fisheye / _radtan / einx_undistort_points_map_radtan (model: "fisheye", "radtan",
+    "points"); K: 4 values, D: 4 (fisheye) or 5, R / P: 9 row-major each (R unused for "points")"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"einx: maps are built on a HIP device (torch device type 'cuda'); there is no CPU path. Got {device}.")
+    k, d, p = _f64(K, 4, "K"), _f64(D, 4 if model == "fisheye" else 5, "D"), _f64(P, 9, "P")
+    hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    mx, my = (torch.empty((H, W), dtype=F32, device=device) for _ in range(2))
+    L = lib()
+    with torch.cuda.device(device):
+        if model == "points":
+            check(L.einx_undistort_points_map_radtan(hp(k), hp(d), hp(p), H, W, int(iters), int(bool(round_out)), _ptr(mx), _ptr(my), _stream(mx)),
+                  "einx_undistort_points_map_radtan")
+        else:
+            r = _f64(R, 9, "R")
+            name = f"einx_rectify_map_{model}"
+            check(getattr(L, name)(hp(k), hp(d), hp(r), hp(p), H, W, _ptr(mx), _ptr(my), _stream(mx)), name)
+    return mx, my
+
+
+def remap_bilinear(src, map_x, map_y):
+    """src [F,Hs,Ws] uint8 or fp32 -> [F,H,W] of the same type, sampled bilinearly at the maps [H,W] (einx_remap_bilinear)"""
+    _dev_check(src, dt=src.dtype)
+    _dev_check(map_x, map_y)
+    F_, Hs, Ws = (int(v) for v in src.shape)
+    H, W = (int(v) for v in map_x.shape)
+    dst = torch.empty((F_, H, W), dtype=src.dtype, device=src.device)
+    if F_ == 0:
+        return dst
+    with torch.cuda.device(src.device):
+        check(lib().einx_remap_bilinear(_ptr(src), 0 if src.dtype == U8 else 1, F_, Hs, Ws, _ptr(map_x), _ptr(map_y), H, W, _ptr(dst), _stream(src)),
+              "einx_remap_bilinear")
+    return dst
+
+
+def events_remap(x, y, t, p, map_x, map_y, x_hi, y_hi, out=None):
+    """einx_events_remap on a resident stream: (out_x, out_y, out_t, out_p, head) with the outputs sized like the inputs and
+    head an int64 [2 + N] tensor whose first two words are (kept, out of map) and whose rest IS out_t's storage, so that one copy
+    brings the counts and the stamps to the host.  out: the same tuple from an earlier call, to write into (graph capture)."""
+    _dev_check(x, y, p, map_x, map_y)
+    _dev_check(t, dt=torch.float64)
+    n = int(t.numel())
+    H, W = (int(v) for v in map_x.shape)
+    if out is None:
+        head = torch.empty(2 + n, dtype=I64, device=t.device)
+        out = (torch.empty(n, dtype=F32, device=t.device), torch.empty(n, dtype=F32, device=t.device), head[2:].view(torch.float64),
+               torch.empty(n, dtype=F32, device=t.device), head)
+    ox, oy, ot, op, head = out
+    L = lib()
+    nws = int(L.einx_events_remap_ws_bytes(n))
+    ws = _workspace(nws, t.device)
+    with torch.cuda.device(t.device):
+        check(L.einx_events_remap(_ptr(x), _ptr(y), _ptr(t), _ptr(p), n, _ptr(map_x), _ptr(map_y), H, W, float(x_hi), float(y_hi), _ptr(ox), _ptr(oy),
+                                  _ptr(ot), _ptr(op), _ptr(head), _ptr(ws), nws, _stream(t)), "einx_events_remap")
+    return out

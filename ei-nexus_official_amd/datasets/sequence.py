@@ -84,17 +84,26 @@ class EventSequence:
     def from_tensors(cls, x, y, t, p):
         """the same from four 1-D tensors that are already on the device (converted to fp32 / fp64 there when they are of
         another type); t is read back once for the search"""
-        self = cls.__new__(cls)
         lens = {name: int(v.numel()) for name, v in (("x", x), ("y", y), ("t", t), ("p", p))}
         if len(set(lens.values())) != 1 or any(v.dim() != 1 for v in (x, y, t, p)):
             raise ValueError("EventSequence: x / y / t / p must be 1-D and of one length: " + ", ".join(f"{k}: {v}" for k, v in lens.items()))
         if len({v.device for v in (x, y, t, p)}) != 1:
             raise ValueError("EventSequence: x / y / t / p lie on different devices")
+        x, y, t, p = (v.detach().to(dt).contiguous() for v, (_, dt) in zip((x, y, t, p), FIELDS))
+        return cls._from_parts(x, y, t, p, t.cpu().numpy())  # (the read-back waits for the conversions above as well)
+
+    @classmethod
+    def _from_parts(cls, x, y, t, p, t_host, check=True):
+        """a sequence around four contiguous device arrays of the right types and the host copy of their stamps, as they are (no
+        conversion, no copy, no read-back); check=False: the caller vouches that the stamps are sorted (a subsequence of a
+        sequence's)"""
+        self = cls.__new__(cls)
         self.events = None
         self.device = t.device
-        self.x, self.y, self.t, self.p = (v.detach().to(dt).contiguous() for v, (_, dt) in zip((x, y, t, p), FIELDS))
-        self.t_host = self.t.cpu().numpy()  # (waits for the conversions above as well)
-        _check_stamps(self.t_host)
+        self.x, self.y, self.t, self.p = x, y, t, p
+        self.t_host = t_host
+        if check:
+            _check_stamps(self.t_host)
         return self
 
     def __len__(self):
@@ -108,6 +117,11 @@ class EventSequence:
         begin = np.searchsorted(self.t_host, ts - np.float64(events_dt), side="left")
         end = np.searchsorted(self.t_host, ts, side="right")
         return EventWindows(self, begin, np.maximum(end, begin))
+
+    def rectified(self, map_x, map_y, rule):
+        """this stream rectified on the device (datasets/rectify.py::rectify_events, DESIGN.md 8q): a new, shorter EventSequence"""
+        from .rectify import rectify_events
+        return rectify_events(self, map_x, map_y, rule)
 
     def windows_from_ranges(self, begin, end):
         """windows by explicit event indices: sample b is the events begin[b] <= k < end[b]"""

@@ -585,6 +585,56 @@ typedef struct einx_event_arrays {
 int einx_events_pack(const einx_event_arrays* samples, int B, float* x, float* y, double* t, float* p, int64_t* offsets, int threads);
 
 /* ------------------------------------------------------------------------------------------
+ * Rectification of raw recordings (csrc/rectify.hip)
+ * replaces: datasets/MVSEC_rectify.py (maps, frames, events), datasets/rectify_ec.py (frames, events)
+ * All maps are [H,W] fp32 pairs (map_x, map_y) on the device, computed in float64 with every operation rounded as written and
+ * stored as float32.  K = (fx, fy, cx, cy), R and P row-major 3x3 (the left 3x3 block of a 3x4 projection matrix), all HOST arrays
+ * of doubles.  Every call enqueues on `stream`, allocates nothing, waits for nothing and can be captured; two calls give the same
+ * bits.  EINX_ERR_ARG: null pointers, non-positive sizes, H * W >= 2^31, a singular P R, a short workspace.
+ * ------------------------------------------------------------------------------------------ */
+/* cv.fisheye.initUndistortRectifyMap(K, D, R, P, (W, H), CV_32FC1) (datasets/MVSEC_rectify.py:91-106): destination pixel (u, v) ->
+ * source position.  iR = (P R)^-1 (host, double); (X, Y, Wd) = iR (u, v, 1), x = X / Wd, y = Y / Wd, r = sqrt(x x + y y),
+ * th = atan(r), thd = th (1 + k1 th^2 + k2 th^4 + k3 th^6 + k4 th^8), s = thd / r (1 where r == 0),
+ * map = (fx x s + cx, fy y s + cy); Wd <= 0 gives (-1, -1).  D = (k1, k2, k3, k4). */
+int einx_rectify_map_fisheye(const double* K, const double* D, const double* R, const double* P, int H, int W, float* map_x, float* map_y,
+                             void* stream);
+/* cv.initUndistortRectifyMap(K, D, R, P, (W, H), CV_32FC1); cv.undistort(img, K, D) (datasets/rectify_ec.py:48-50) remaps with
+ * the map of R = I, P = K.  x, y as above; r2 = x x + y y, kr = 1 + ((k3 r2 + k2) r2 + k1) r2,
+ * xd = x kr + 2 p1 x y + p2 (r2 + 2 x x), yd = y kr + p1 (r2 + 2 y y) + 2 p2 x y, map = (fx xd + cx, fy yd + cy).
+ * D = (k1, k2, p1, p2, k3): the order of EC's calib.txt. */
+int einx_rectify_map_radtan(const double* K, const double* D, const double* R, const double* P, int H, int W, float* map_x, float* map_y,
+                            void* stream);
+/* cv.undistortPoints(pixels, K, D, P=P) for EVERY integer pixel of the sensor (datasets/rectify_ec.py:70-77): raw pixel (u, v) ->
+ * its undistorted position, so that 10^8 events need one lookup each.  x0 = (u - cx) / fx, y0 = (v - cy) / fy; `iters` times
+ * x = (x0 - dx(x, y)) / kr(x, y), y = (y0 - dy(x, y)) / kr(x, y) from (x0, y0), dx / dy the tangential terms above (5: the
+ * reference call's default criteria); (X, Y, Wp) = P (x, y, 1), map = (X / Wp, Y / Wp).  round_out = 1 stores rint of the double
+ * result (rectify_ec.py:78). */
+int einx_undistort_points_map_radtan(const double* K, const double* D, const double* P, int H, int W, int iters, int round_out, float* map_x,
+                                     float* map_y, void* stream);
+/* cv.remap(frame, map_x, map_y, INTER_LINEAR) with BORDER_CONSTANT 0 for F frames in one launch (datasets/MVSEC_rectify.py:16-21;
+ * with the radtan map: cv.undistort, datasets/rectify_ec.py:48-50).  src [F,Hs,Ws], dst [F,H,W], both uint8 or both fp32; maps [H,W].
+ * x0 = floor(mx), fx = mx - x0 (y likewise), top = I00 + fx (I01 - I00), bot = I10 + fx (I11 - I10), v = top + fy (bot - top),
+ * every operation rounded to fp32; a tap outside the source reads 0, a map entry that is not finite gives 0; uint8 output is
+ * rint(v) clamped to 0..255.  Interpolates at the map's own coordinate (OpenCV quantises it to 1/32 px first: DESIGN.md 8q). */
+enum { EINX_REMAP_U8 = 0, EINX_REMAP_F32 = 1 };
+int einx_remap_bilinear(const void* src, int src_type, int F, int Hs, int Ws, const float* map_x, const float* map_y, int H, int W, void* dst,
+                        void* stream);
+/* The event pass of both scripts (datasets/MVSEC_rectify.py:23-45, datasets/rectify_ec.py:70-83 with the points map above): for
+ * event k of the stream x / y / p (fp32), t (fp64) of N events, in order: ox = rint(x[k]), oy = rint(y[k]) (half to even,
+ * np.round); an event with ox outside [0, W) or oy outside [0, H), or either not finite, is counted in out_counts[1] and dropped
+ * (numpy raises for a coordinate >= W and wraps a negative one); otherwise x' = map_x[oy, ox], y' = map_y[oy, ox] and the event is
+ * kept iff 0 <= x' < x_hi and 0 <= y' < y_hi (NaN fails): (W - 1, H - 1) is MVSEC's rule (:37-43), (W, H) EC's (:80-83).  The kept
+ * events are written densely and in input order to out_* (sized N): x', y' the map's values, t and p copied, all bit for bit;
+ * out_counts[0] = the number kept (device, int64 [2]).  A stable compaction: per-workgroup counts, a scan of the counts, a
+ * ranked scatter; every offset is an integer sum, so two calls give the same bits.  N may exceed 2^31 (N = 0: only the counts
+ * are written).  The workspace holds one int64 per einx_events_remap_chunk() events and per 1024 of those. */
+size_t einx_events_remap_ws_bytes(int64_t N);
+int einx_events_remap(const float* x, const float* y, const double* t, const float* p, int64_t N, const float* map_x, const float* map_y,
+                      int H, int W, float x_hi, float y_hi, float* out_x, float* out_y, double* out_t, float* out_p, int64_t* out_counts,
+                      void* ws, size_t ws_bytes, void* stream);
+int einx_events_remap_chunk(void); /* events per workgroup of einx_events_remap (host only) */
+
+/* ------------------------------------------------------------------------------------------
  * Handle-level extractor: ONE call enqueues a whole network (SURVEY.md 8b's coarse ABI)
  * replaces: VGGExtractor.forward / VGGExtractorNP.forward
  *             core/modules/event_extractors/EventExtractors.py:517-624, :331-434
