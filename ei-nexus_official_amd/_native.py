@@ -835,3 +835,59 @@ def events_remap(x, y, t, p, map_x, map_y, x_hi, y_hi, out=None):
         check(L.einx_events_remap(_ptr(x), _ptr(y), _ptr(t), _ptr(p), n, _ptr(map_x), _ptr(map_y), H, W, float(x_hi), float(y_hi), _ptr(ox), _ptr(oy),
                                   _ptr(ot), _ptr(op), _ptr(head), _ptr(ws), nws, _stream(t)), "einx_events_remap")
     return out
+
+
+# ------------------------------------------------------------------------------ pose tracks (csrc/posetrack.hip)
+F64 = torch.float64
+
+
+def _track_check(stamps, trans, quats):
+    _dev_check(stamps, trans, quats, dt=F64)
+    n = int(stamps.numel())
+    if stamps.dim() != 1 or tuple(trans.shape) != (n, 3) or tuple(quats.shape) != (n, 4):
+        raise ValueError(f"einx: a track is stamps [N], translations [N,3] and quaternions [N,4], got {tuple(stamps.shape)}, "
+                         f"{tuple(trans.shape)}, {tuple(quats.shape)}")
+    return n
+
+
+def pose_interp(stamps, trans, quats, queries, inverse=True, dtype=F32):
+    """einx_pose_interp: queries [Q] float64 on the track's device -> (poses [Q,4,4] of `dtype` (float32 or float64), out_of_range
+    int32 [1] on the device); no host synchronisation"""
+    n = _track_check(stamps, trans, quats)
+    _dev_check(queries, dt=F64)
+    if dtype not in (F32, F64):
+        raise TypeError(f"einx: poses are float32 or float64, got {dtype}")
+    q = int(queries.numel())
+    out = torch.empty((q, 4, 4), dtype=dtype, device=stamps.device)
+    bad = torch.empty(1, dtype=I32, device=stamps.device)
+    with torch.cuda.device(stamps.device):
+        check(lib().einx_pose_interp(_ptr(stamps), _ptr(trans), _ptr(quats), n, _ptr(queries), q, int(bool(inverse)), 0 if dtype == F32 else 1,
+                                     _ptr(out), _ptr(bad), _stream(stamps)), "einx_pose_interp")
+    return out, bad
+
+
+def pose_relative(stamps, trans, quats, q0, q1):
+    """einx_pose_relative: q0, q1 [P] float64 -> (T_0to1, T_1to0 [P,4,4] float32, out_of_range int32 [1]); no host synchronisation"""
+    n = _track_check(stamps, trans, quats)
+    _dev_check(q0, q1, dt=F64)
+    p = int(q0.numel())
+    if int(q1.numel()) != p:
+        raise ValueError(f"einx: pose_relative takes two query arrays of one length, got {p} and {int(q1.numel())}")
+    t01, t10 = (torch.empty((p, 4, 4), dtype=F32, device=stamps.device) for _ in range(2))
+    bad = torch.empty(1, dtype=I32, device=stamps.device)
+    with torch.cuda.device(stamps.device):
+        check(lib().einx_pose_relative(_ptr(stamps), _ptr(trans), _ptr(quats), n, _ptr(q0), _ptr(q1), p, _ptr(t01), _ptr(t10), _ptr(bad),
+                                       _stream(stamps)), "einx_pose_relative")
+    return t01, t10, bad
+
+
+def nearest_stamp(stamps, queries):
+    """einx_nearest_stamp: sorted stamps [F] and queries [Q], float64 on one device -> int64 [Q]"""
+    _dev_check(stamps, queries, dt=F64)
+    f, q = int(stamps.numel()), int(queries.numel())
+    if f == 0:
+        raise ValueError("einx: nearest_stamp: no stamps")
+    out = torch.empty(q, dtype=I64, device=stamps.device)
+    with torch.cuda.device(stamps.device):
+        check(lib().einx_nearest_stamp(_ptr(stamps), f, _ptr(queries), q, _ptr(out), _stream(stamps)), "einx_nearest_stamp")
+    return out

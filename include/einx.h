@@ -635,6 +635,40 @@ int einx_events_remap(const float* x, const float* y, const double* t, const flo
 int einx_events_remap_chunk(void); /* events per workgroup of einx_events_remap (host only) */
 
 /* ------------------------------------------------------------------------------------------
+ * Pose tracks and the depth / image pairing of a recording (csrc/posetrack.hip)
+ * replaces: datasets/Interpolator.py (PoseInterpolator), datasets/MVSEC.py:818-830 (get_relative_pose), :362-369 (nearest pairing)
+ * A track is N >= 2 knots on the device: stamps double[N] strictly increasing (epoch seconds: float32 cannot hold them),
+ * translations double[N,3] and UNIT quaternions double[N,4] as (x, y, z, w) of the poses T_W_j.  All arithmetic is float64 with
+ * every operation rounded as written.  Every call enqueues on `stream`, takes no workspace, waits for nothing and can be captured;
+ * two calls give the same bits.  EINX_ERR_ARG: null pointers, N < 2, negative counts, an unknown out_type, F <= 0.
+ * ------------------------------------------------------------------------------------------ */
+/* PoseInterpolator.interpolate (datasets/Interpolator.py:54-69) for Q queries double[Q], one thread each: out [Q,4,4] row-major of
+ * out_type.  i = clamp(lower_bound(stamps, q) - 1, 0, N - 2), the interval of scipy's Slerp.__call__ and linear interp1d (a query
+ * on a knot takes the interval on its left with alpha = 1, the first knot i = 0 with alpha = 0); alpha = (q - t_i) / (t_i+1 - t_i);
+ * translation (p_i+1 - p_i) / (t_i+1 - t_i) * (q - t_i) + p_i (interp1d's order, :45-47, :65-67); rotation by quaternion slerp on
+ * the shorter arc (:50-52, :68): q_i+1 negated when the dot product d is negative, theta = atan2(|q_i+1 - d q_i|, d), weights
+ * sin((1 - alpha) theta) / sin(theta) and sin(alpha theta) / sin(theta) (1 - alpha and alpha below 1e-12 rad), the result
+ * renormalised.  inverse = 1 writes T_j_W = [R^T | -R^T p] in closed form (:69 calls np.linalg.inv), inverse = 0 T_W_j = [R | p].
+ * A query outside [t_0, t_N-1] or NaN gives sixteen NaNs and adds one to *out_of_range (device int32, zeroed by the call); the
+ * reference prints a line and interp1d raises. */
+enum { EINX_POSE_F32 = 0, EINX_POSE_F64 = 1 };
+int einx_pose_interp(const double* stamps, const double* trans, const double* quats, int N, const double* queries, int Q, int inverse,
+                     int out_type, void* out, int32_t* out_of_range, void* stream);
+/* MVSECDataset_RPE_VAL.__getitem__'s two get_relative_pose calls (datasets/MVSEC.py:1081-1085, :818-830) for P pairs of queries
+ * q0[P], q1[P]: T_0to1 = T_1_W T_W_0 and T_1to0 = T_0_W T_W_1, both [P,4,4] fp32.  The two interpolations above, the closed-form
+ * rigid inverse and the products are float64, cast ONCE (the rule of datasets/pairs.py::relative_transforms).  The reference casts
+ * each interpolated pose to float32 first and then forms pose1 @ np.linalg.inv(pose0) in float32: the two can differ in the last
+ * float32 bit.  A pair with a query outside the track has NaN in both matrices; *out_of_range counts such QUERIES. */
+int einx_pose_relative(const double* stamps, const double* trans, const double* quats, int N, const double* q0, const double* q1, int P,
+                       float* T_0to1, float* T_1to0, int32_t* out_of_range, void* stream);
+/* np.abs(np.subtract.outer(stamps, queries)).argmin(axis=0) (datasets/MVSEC.py:364-366) for sorted stamps double[F] (non-decreasing,
+ * duplicates allowed) without the F x Q matrix: out[k] int64 = the FIRST index i whose fabs(stamps[i] - queries[k]), evaluated in
+ * float64, is minimal.  Two binary searches per query: for the first stamp that is not below the query, and -- when the minimum
+ * lies left of it -- for the first stamp with that rounded distance (equal stamps, or different stamps that tie after rounding).
+ * A tie between the stamp below and the stamp above gives the lower index.  A NaN query gives 0, as argmin of an all-NaN column. */
+int einx_nearest_stamp(const double* stamps, int64_t F, const double* queries, int64_t Q, int64_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Handle-level extractor: ONE call enqueues a whole network (SURVEY.md 8b's coarse ABI)
  * replaces: VGGExtractor.forward / VGGExtractorNP.forward
  *             core/modules/event_extractors/EventExtractors.py:517-624, :331-434
