@@ -175,9 +175,12 @@ __global__ void border_kernel(float* score, int B, int Hp, int Wp, int border) {
 // scans so that every lane does the same fixed amount of LDS work (the naive 81-tap test makes a
 // whole wave wait for its one surviving maximum on every pass):
 //   A  R9[y][x]   = max(v[y][x-R..x+R])                                   (row scan)
-//   B  ismax[y][x]= v>0 && max(v[y][x-R..x-1]) <  v && max(v[y][x+1..x+R]) <= v
+//   B  ismax[y][x]= inside the image && max(v[y][x-R..x-1]) <  v && max(v[y][x+1..x+R]) <= v
 //                        && max(R9[y-R..y-1][x]) <  v && max(R9[y+1..y+R][x]) <= v
-//      (first maximum wins: earlier raster taps must be strictly smaller, later ones <=)
+//      (first maximum wins: earlier raster taps must be strictly smaller, later ones <=; taps outside the image count as 0.
+//      No sign test on v: like the reference's argmax over the zero-padded window, a negative pixel or an exact zero whose
+//      window holds nothing larger is a maximum and suppresses its neighbours.  On non-negative maps a zero never qualifies,
+//      because its earlier taps are not strictly below it)
 //   C  rowor[y][x]= OR(ismax[y][x-R..x+R]);   D  suppressed = OR(rowor[y-R..y+R][x]) && !ismax
 // A pass for image b runs only while the previous pass changed that image (flags[b][it-1]); it
 // raises flags[b][it] if it zeroes any non-zero pixel.  When a pass changes nothing src == dst, so
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_pass_kernel(const float* src,
       above = fmaxf(above, r9[(vy - R + dy) * MW + mx]);
       below = fmaxf(below, r9[(vy + 1 + dy) * MW + mx]);
     }
-    const bool ok = c > 0.0f && y >= 0 && y < Hp && x >= 0 && x < Wp && left < c && above < c && right <= c && below <= c;
+    const bool ok = y >= 0 && y < Hp && x >= 0 && x < Wp && left < c && above < c && right <= c && below <= c;
     ismax[i] = ok ? 1 : 0;
   }
   __syncthreads();
@@ -298,7 +301,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_pass_kernel(const float* src,
 // neighbouring columns of one row, read with 16-byte LDS loads, and the boolean planes are bit-packed
 // (one byte per eight columns), so a pass issues ~4x fewer LDS instructions -- the LDS pipe, shared by
 // the four resident workgroups of a CU, is what bounds the generic kernel above.  Same predicates:
-//   ismax = v > 0 && inside && max(left 4) < v && max(right 4) <= v && max(4 rows above of R9) < v
+//   ismax = inside && max(left 4) < v && max(right 4) <= v && max(4 rows above of R9) < v
 //           && max(4 rows below of R9) <= v;   suppressed = (some ismax in the 9x9 window) && !ismax
 // ------------------------------------------------------------------------------------------
 struct __attribute__((aligned(16))) Nms4Smem {
@@ -308,7 +311,7 @@ struct __attribute__((aligned(16))) Nms4Smem {
   static constexpr int G = MW / 8, TG = NMS_TW / 8;               // 9 column groups of the is-max grid, 8 of the tile
   float vals[VH * VW];
   float r9[VH * MW];
-  uint8_t rowok8[VH * G];  // bit k of [vy][g]: centre > 0 and row-wise conditions hold at column g*8+k
+  uint8_t rowok8[VH * G];  // bit k of [vy][g]: the row-wise conditions hold at column g*8+k (any sign of the centre; in-image test in phase B)
   uint8_t ismax8[MH * (G + 1)];
   uint8_t rowor8[MH * TG];
   int changed;
@@ -364,7 +367,7 @@ __device__ __forceinline__ void nms4_tile(Nms4Smem& sm, const float* s, float* d
       }
       const float c = v[k + 4];
       m9[k] = fmaxf(fmaxf(left, right), c);
-      ok |= (c > 0.0f && left < c && right <= c) ? (1u << k) : 0u;
+      ok |= (left < c && right <= c) ? (1u << k) : 0u;
     }
     float* o = sm.r9 + vy * MW + g * 8;
     *reinterpret_cast<f32x4*>(o) = f32x4{m9[0], m9[1], m9[2], m9[3]};

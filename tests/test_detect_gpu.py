@@ -107,8 +107,10 @@ def test_nms_finisher_on_tie_heavy_full_size_maps(oracle):
 
 
 def test_detect_generic_path_dense_and_negative(oracle):
-    """dense maps (more non-zeros than the LDS candidate list holds) and negative values take the
-    generic radix-select path of einx_detect; compare with the oracle bit for bit."""
+    """dense maps (more non-zeros than the LDS candidate list holds), with and without a minority of negative values, take the
+    generic radix-select path of einx_detect; compare with the oracle bit for bit.  The radius-2 case draws uniform(-0.2, 1): an
+    all-negative window practically never occurs there, so it says nothing about NMS on negative maps (negative or zero maxima,
+    thresholds below zero: test_detect_paths_gpu.py::test_nms_signs, test_select_paths[negative_thr_below_zero])."""
     for seed, lo_val, radius, k in ((91, 0.0, 0, 700), (92, -0.5, 0, 300), (93, -0.2, 2, 50)):
         s = synth.uniform(seed, (2, 1, 120, 136), lo_val, 1.0)
         exp_nms, exp_pos, exp_idx, exp_thr, _ = oracle.detect_post(s.copy(), k, radius, 0, 1.0)
