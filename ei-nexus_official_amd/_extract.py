@@ -265,17 +265,17 @@ class BatchedFeats:
 
 
 def _mask_u8(mask, H, W):
+    """-> (uint8 bytes or None, EINX_MASK_PAD_* rule): N.mask_bytes after the checks of the fused path"""
     if mask is None:
-        return None
+        return None, N.MASK_PAD_ZERO
     if mask.device.type != "cuda":
         raise RuntimeError(f"einx: the mask must live on a HIP device, got {mask.device}")
     if tuple(mask.shape[-2:]) != (H, W):
         raise ValueError(f"mask spatial size {tuple(mask.shape[-2:])} does not match the image ({H},{W})")
-    if mask.dtype == torch.bool:
-        return mask.contiguous().view(torch.uint8)
-    # other dtypes: "non-zero is visible" -- the reference averages `score_mask.float()` over 3x3 and tests `> 0`
-    # (EventExtractors.py:529-535), so a fractional 0.5 counts; a plain cast to uint8 would truncate it to 0
-    return mask.ne(0).contiguous().view(torch.uint8)
+    # other dtypes than bool: "non-zero is visible" -- the reference averages `score_mask.float()` over 3x3 and tests `> 0`
+    # (EventExtractors.py:544-550), so a fractional 0.5 counts; a plain cast to uint8 would truncate it to 0 -- and the padding
+    # ring repeats the edge pixels (Padder.pad, utils/util.py:17-32)
+    return N.mask_bytes(mask)
 
 
 class ExtractorEngine:
@@ -373,20 +373,19 @@ class ExtractorEngine:
         bf.sparse_desc = e(B, cap, D)
         nws = int(L.einx_extract_ws_bytes(h, B, H, W, cap, int(nms_iters)))
         ws = N._workspace(nws, dev)
-        m8 = _mask_u8(mask, H, W)
+        m8, mpad = _mask_u8(mask, H, W)
         P = N._ptr
         bf.score_crop = e(B, 1, H, W)  # the dict's un-padded `score`, written by the score kernel (no crop + clone launch afterwards)
         out = _lib.ExtractOut(P(bf.feats), P(bf.logits), P(bf.raw), P(bf.prob), P(bf.score), P(bf.coarse), P(bf.raw_cl), P(det.nms),
                               P(det.positions), P(det.indices), P(det.counts), P(det.thr), P(det.not_converged), P(bf.sparse_desc), cap,
                               P(bf.score_crop))
         wt = getattr(self, "watch", None)
+        ww = None
         if wt is not None and wt.n:  # `.data` edits of the weights: compared inside the call, reported through the watch's own `stale` word
-            ww = _lib.WeightWatch(ctypes.sizeof(_lib.WeightWatch), wt.n, P(wt.table), P(wt.ref), P(wt.scratch), P(wt.stale))
-            _lib.check(L.einx_extract_watch(h, P(x), P(m8), B, H, W, int(nms_iters), P(ws), nws, ctypes.byref(out), ctypes.byref(ww), N._stream(x)),
-                       "einx_extract_watch")
+            ww = ctypes.byref(_lib.WeightWatch(ctypes.sizeof(_lib.WeightWatch), wt.n, P(wt.table), P(wt.ref), P(wt.scratch), P(wt.stale)))
             det.stale = wt.stale
-        else:
-            _lib.check(L.einx_extract(h, P(x), P(m8), B, H, W, int(nms_iters), P(ws), nws, ctypes.byref(out), N._stream(x)), "einx_extract")
+        _lib.check(L.einx_extract_pad(h, P(x), P(m8), mpad, B, H, W, int(nms_iters), P(ws), nws, ctypes.byref(out), ww, N._stream(x)),
+                   "einx_extract_pad")
         if dense and not defer_dense:
             bf.run_dense()
         return bf

@@ -133,6 +133,8 @@ SIGNATURES = {
     "einx_extract": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(ExtractOut), c_void_p]),
     "einx_extract_watch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(ExtractOut),
                            ctypes.POINTER(WeightWatch), c_void_p]),
+    "einx_extract_pad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(ExtractOut),
+                         ctypes.POINTER(WeightWatch), c_void_p]),
     "einx_conv_last_kernel": (c_char_p, []),
     "einx_conv_plan": (c_char_p, [c_int] * 11),
     "einx_conv_weight_elems": (c_size_t, [c_int, c_int, c_int]),
@@ -154,6 +156,8 @@ SIGNATURES = {
                            c_float, c_void_p, c_void_p]),
     "einx_score_map": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, c_void_p]),
+    "einx_score_map_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p]),
     "einx_remove_border": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "einx_detect_ws_bytes": (c_size_t, [ctypes.POINTER(DetectParams)]),
     "einx_detect": (c_int, [c_void_p, ctypes.POINTER(DetectParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

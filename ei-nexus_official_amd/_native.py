@@ -225,8 +225,21 @@ def image_prepare(image, divisor):
 
 
 # ------------------------------------------------------------------------------ detector
+MASK_PAD_ZERO, MASK_PAD_REPLICATE = 0, 1  # include/einx.h: EINX_MASK_PAD_*
+
+
+def mask_bytes(mask):
+    """mask of any dtype -> (uint8 view / copy the score kernels read, the Padder's padding rule for that dtype).  The reference
+    pads a bool mask with zeros and every other dtype by repeating its edge pixels (core/modules/utils/util.py:17-32); of a mask
+    that is not bool the non-zero pixels are the visible ones (stated departures, for signed and denormal values:
+    the reference tests `conv(mask.float(), ones / 9) > 0`, EventExtractors.py:544-550)."""
+    if mask.dtype == torch.bool:
+        return mask.contiguous().view(torch.uint8), MASK_PAD_ZERO
+    return mask.ne(0).contiguous().view(torch.uint8), MASK_PAD_REPLICATE
+
+
 def score_map(logits, mask=None, pads=(0, 0, 0, 0), dilate=False, border=0):
-    """-> (probability [B,C,hc,wc], score [B,1,Hp,Wp])."""
+    """-> (probability [B,C,hc,wc], score [B,1,Hp,Wp]).  mask [B,1,H,W]: bool, or any other dtype (see mask_bytes)."""
     _dev_check(logits)
     if mask is not None and mask.device.type != "cuda":
         raise RuntimeError(f"einx: the mask must live on a HIP device, got {mask.device}")
@@ -237,14 +250,13 @@ def score_map(logits, mask=None, pads=(0, 0, 0, 0), dilate=False, border=0):
     H, W = Hp - h0 - h1, Wp - w0 - w1
     prob = torch.empty_like(logits)
     score = torch.empty((B, 1, Hp, Wp), dtype=F32, device=logits.device)
-    m8 = None
+    m8, pad = None, MASK_PAD_ZERO
     if mask is not None:
         if tuple(mask.shape[-2:]) != (H, W):
             raise ValueError(f"mask spatial size {tuple(mask.shape[-2:])} does not match the image ({H},{W})")
-        # non-bool masks: non-zero is visible (the reference tests `conv(mask.float()) > 0`), see _extract._mask_u8
-        m8 = (mask if mask.dtype == torch.bool else mask.ne(0)).contiguous().view(torch.uint8)
-    check(lib().einx_score_map(_ptr(logits), B, C, hc, wc, _ptr(m8), H, W, h0, w0, int(dilate), int(border), _ptr(prob), _ptr(score),
-                               _stream(logits)), "einx_score_map")
+        m8, pad = mask_bytes(mask)
+    check(lib().einx_score_map_pad(_ptr(logits), B, C, hc, wc, _ptr(m8), pad, H, W, h0, w0, int(dilate), int(border), _ptr(prob),
+                                   _ptr(score), _stream(logits)), "einx_score_map_pad")
     return prob, score
 
 

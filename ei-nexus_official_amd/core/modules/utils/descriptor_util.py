@@ -26,39 +26,60 @@ def get_dense_descriptors(normalized_descriptors):
     return normalized_descriptors.reshape(B, C, -1).permute(0, 2, 1)
 
 
-def _pack_positions(positions, width):
-    """list of [n_i,>=2] (y,x) positions -> (indices [B,cap] int32, counts [B] int32); integer
-    index arithmetic only (floor, y*W+x)."""
+def _pack_positions(positions, size, bilinear):
+    """list of [n_i,>=2] (y,x) positions on a [H,W] = `size` grid -> (indices [B,cap] int32, counts [B] int32); integer index
+    arithmetic only (floor, y*W+x).  The positions are validated first, because the kernels read at the index unchecked:
+      gather (bilinear=False): a position outside the map is an IndexError, as the reference's `raw[i, :, y, x]` raises for an
+        index >= size (descriptor_util.py:59-61; it would wrap a negative one, which no detector emits: refused here too);
+      bilinear: the sampler takes its sample at the centre of the position's pixel, so a position whose fractional part is not
+        0.5 (the reference's grid_sample interpolates at the float position, descriptor_util.py:105-121) or that lies outside
+        the padded image (zero padding there) is refused, not silently moved.  A NaN is refused by either rule.
+    The check is one small reduction and one read-back per call: these drop-in helpers are off the hot path -- the extractors
+    hand the detector's own `indices` straight to desc_sample and never come through here."""
     B = len(positions)
+    H, W = int(size[0]), int(size[1])
     cap = max([int(p.shape[0]) for p in positions] + [1])
     dev = positions[0].device
     idx = torch.zeros((B, cap), dtype=torch.int32, device=dev)
     cnt = torch.tensor([int(p.shape[0]) for p in positions], dtype=torch.int32, device=dev)
+    bad = []
     for b, p in enumerate(positions):
         if p.shape[0]:
-            yx = p[:, :2].floor().to(torch.int32)
-            idx[b, :p.shape[0]] = yx[:, 0] * width + yx[:, 1]
+            yx = p[:, :2]
+            fl = yx.floor()
+            ok = (fl[:, 0] >= 0) & (fl[:, 0] < H) & (fl[:, 1] >= 0) & (fl[:, 1] < W)
+            if bilinear:
+                ok = ok & (yx - fl == 0.5).all(dim=1)
+            bad.append((~ok).any())
+            fi = fl.to(torch.int32)
+            idx[b, :p.shape[0]] = fi[:, 0] * W + fi[:, 1]
+    if bad and bool(torch.stack(bad).any()):
+        if bilinear:
+            raise NotImplementedError(f"einx: sparsify_low_resolution_descriptors samples at pixel centres (y + 0.5, x + 0.5) inside the "
+                                      f"padded image {(H, W)}; a position with another fractional part or outside it is not supported")
+        raise IndexError(f"position out of bounds for the descriptor map of size {(H, W)}")
     return idx, cnt
 
 
 def sparsify_full_resolution_descriptors(raw_descriptors, positions, scale_factor=1.0, normalize=True):
-    """integer gather + normalise for cell-1 networks (descriptor_util.py:50-71)."""
+    """integer gather + normalise for cell-1 networks (descriptor_util.py:50-71); IndexError for a position outside the map."""
     if not normalize:
         raise NotImplementedError
     raw = _f32(raw_descriptors).contiguous()
     H, W = raw.shape[-2:]
-    idx, cnt = _pack_positions(positions, W)
+    idx, cnt = _pack_positions(positions, (H, W), bilinear=False)
     out = desc_sample(raw, idx, cnt, (H, W), bilinear=False, scale=_scale(scale_factor))
     return tuple(out[b, :int(positions[b].shape[0])] for b in range(len(positions)))
 
 
 def sparsify_low_resolution_descriptors(raw_descriptors, positions, image_size, scale_factor=1.0, normalize=True):
-    """bilinear grid_sample at keypoints + normalise for cell-8 networks (descriptor_util.py:74-128)."""
+    """bilinear grid_sample at keypoints + normalise for cell-8 networks (descriptor_util.py:74-128).  The positions are pixel
+    centres of the padded image (what the detector emits); see _pack_positions for what is refused."""
     if not normalize:
         raise NotImplementedError
     raw = _f32(raw_descriptors).contiguous()
     Hp, Wp = int(image_size[0]), int(image_size[1])
-    idx, cnt = _pack_positions(positions, Wp)
+    idx, cnt = _pack_positions(positions, (Hp, Wp), bilinear=True)
     out = desc_sample(raw, idx, cnt, (Hp, Wp), bilinear=True, scale=_scale(scale_factor))
     return [out[b, :int(positions[b].shape[0])] for b in range(len(positions))]
 

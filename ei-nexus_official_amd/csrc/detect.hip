@@ -18,9 +18,11 @@ namespace {
 // K3: one thread per cell (C==65) or per pixel (C==1).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool mask_on(const uint8_t* mask, int b, int H, int W, int h0, int w0, int Hp, int Wp, int y, int x,
-                                        int dilate) {
-  // mask zero-padded to [Hp,Wp]; optional 3x3 dilation evaluated inside the padded map.  The nine bytes are requested
-  // together (clamped addresses, validity folded into the test): no dependent load-and-branch chain per pixel
+                                        int dilate, int replicate) {
+  // mask padded to [Hp,Wp] -- with zeros, or (replicate: the reference's Padder for a mask that is not bool) with its edge
+  // pixels; optional 3x3 dilation evaluated inside the padded map.  The nine bytes are requested together (clamped addresses,
+  // validity folded into the test): no dependent load-and-branch chain per pixel.  The clamped address IS the replicate load,
+  // so that mode only drops the source-range terms of the test
   const int r = dilate ? 1 : 0;
   bool any = false;
 #pragma unroll
@@ -28,7 +30,8 @@ __device__ __forceinline__ bool mask_on(const uint8_t* mask, int b, int H, int W
 #pragma unroll
     for (int dx = -1; dx <= 1; ++dx) {
       const int yy = y + dy, xx = x + dx, sy = yy - h0, sx = xx - w0;
-      const bool ok = dy >= -r && dy <= r && dx >= -r && dx <= r && yy >= 0 && yy < Hp && xx >= 0 && xx < Wp && sy >= 0 && sy < H && sx >= 0 && sx < W;
+      const bool ok = dy >= -r && dy <= r && dx >= -r && dx <= r && yy >= 0 && yy < Hp && xx >= 0 && xx < Wp &&
+                      (replicate || (sy >= 0 && sy < H && sx >= 0 && sx < W));
       const uint8_t m = mask[((size_t)b * H + min(max(sy, 0), H - 1)) * W + min(max(sx, 0), W - 1)];
       any |= ok && m != 0;
     }
@@ -42,8 +45,8 @@ __device__ __forceinline__ bool mask_on(const uint8_t* mask, int b, int H, int W
 // is bit-identical to the one-thread-per-cell form.  A lane writes its 8 score pixels as two 16-byte
 // stores; 8 neighbouring cells give 256 contiguous bytes per row.
 __global__ __launch_bounds__(256) void score65_kernel(const float* logits, int B, int hc, int wc, const uint8_t* mask, int H, int W,
-                                                      int h0, int w0, int dilate, int border, float* prob, float* score, int32_t* zero_ptr,
-                                                      int zero_n, float* crop) {
+                                                      int h0, int w0, int dilate, int replicate, int border, float* prob, float* score,
+                                                      int32_t* zero_ptr, int zero_n, float* crop) {
   // (einx_extract: the NMS pass flags of the detection that follows are zeroed here instead of by a memset launch of their own)
   if ((int)(blockIdx.x * 256 + threadIdx.x) < zero_n) zero_ptr[blockIdx.x * 256 + threadIdx.x] = 0;
   const int cells = hc * wc;
@@ -79,7 +82,8 @@ __global__ __launch_bounds__(256) void score65_kernel(const float* logits, int B
   const int y = h * 8 + i;
   // events mask of the lane's 8 pixels (row y, columns 8w..8w+7), dilated 3x3 inside the padded map: the 3 x 10 bytes around
   // them are requested together (clamped addresses, validity folded into the bit), bit k of `cols` = some row has an event in
-  // column 8w-1+k; a per-pixel mask_on() walk is up to 72 dependent byte loads per lane
+  // column 8w-1+k; a per-pixel mask_on() walk is up to 72 dependent byte loads per lane.  replicate (a mask that is not bool):
+  // the padding ring repeats the mask's edge pixels, which is what the clamped addresses load -- only the range terms go
   unsigned cols = 0x3ffu;
   if (mask) {
     cols = 0;
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(256) void score65_kernel(const float* logits, int B
 #pragma unroll
     for (int dy = -1; dy <= 1; ++dy) {
       const int yy = y + dy, sy = yy - h0;
-      const bool rok = dy >= -r && dy <= r && yy >= 0 && yy < Hp && sy >= 0 && sy < H;
+      const bool rok = dy >= -r && dy <= r && yy >= 0 && yy < Hp && (replicate || (sy >= 0 && sy < H));
       const uint8_t* mrow = mask + ((size_t)b * H + min(max(sy, 0), H - 1)) * W;
       uint8_t m[10];
 #pragma unroll
@@ -95,7 +99,7 @@ __global__ __launch_bounds__(256) void score65_kernel(const float* logits, int B
 #pragma unroll
       for (int k = 0; k < 10; ++k) {
         const int xx = w * 8 - 1 + k, sx = xx - w0;
-        if (rok && xx >= 0 && xx < Wp && sx >= 0 && sx < W && m[k]) cols |= 1u << k;
+        if (rok && xx >= 0 && xx < Wp && (replicate || (sx >= 0 && sx < W)) && m[k]) cols |= 1u << k;
       }
     }
   }
@@ -129,7 +133,8 @@ __global__ __launch_bounds__(256) void score65_kernel(const float* logits, int B
 }
 
 __global__ void score1_kernel(const float* logits, int B, int Hp, int Wp, const uint8_t* mask, int H, int W, int h0, int w0,
-                              int dilate, int border, float* prob, float* score, int32_t* zero_ptr, int zero_n, float* crop) {
+                              int dilate, int replicate, int border, float* prob, float* score, int32_t* zero_ptr, int zero_n,
+                              float* crop) {
   const int n = Hp * Wp;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid < zero_n) zero_ptr[gid] = 0;
@@ -137,7 +142,7 @@ __global__ void score1_kernel(const float* logits, int B, int Hp, int Wp, const 
   const int b = gid / n, p = gid % n;
   const int y = p / Wp, x = p % Wp;
   float v = einx_sigmoidf(logits[gid]);
-  if (mask && !mask_on(mask, b, H, W, h0, w0, Hp, Wp, y, x, dilate)) v = 0.0f;
+  if (mask && !mask_on(mask, b, H, W, h0, w0, Hp, Wp, y, x, dilate, replicate)) v = 0.0f;
   if (border > 0 && (y < border || y >= Hp - border || x < border || x >= Wp - border)) v = 0.0f;
   prob[gid] = v;  // the reference's score aliases probability for cell-1 networks
   score[gid] = v;
@@ -985,13 +990,22 @@ void topk_ranks(int N, int k, int* lo, int* hi) {
 
 EINX_EXPORT int einx_score_map(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int H, int W, int h0, int w0,
                                int dilate, int border, float* prob, float* score, void* stream) {
-  return einx_score_map_zero(logits, B, C, hc, wc, mask, H, W, h0, w0, dilate, border, prob, score, nullptr, 0, nullptr, stream);
+  return einx_score_map_zero(logits, B, C, hc, wc, mask, H, W, h0, w0, dilate, EINX_MASK_PAD_ZERO, border, prob, score, nullptr, 0, nullptr,
+                             stream);
+}
+
+EINX_EXPORT int einx_score_map_pad(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int mask_pad, int H, int W, int h0,
+                                   int w0, int dilate, int border, float* prob, float* score, void* stream) {
+  return einx_score_map_zero(logits, B, C, hc, wc, mask, H, W, h0, w0, dilate, mask_pad, border, prob, score, nullptr, 0, nullptr, stream);
 }
 
 // the same launch, which also zeroes zero_n int32 words at zero_ptr (einx_extract: the NMS pass flags of the detection that follows;
 // returns EINX_ERR_ARG when the launch has fewer threads than words -- the caller then keeps the memset)
 int einx_score_map_zero(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int H, int W, int h0, int w0, int dilate,
-                        int border, float* prob, float* score, int32_t* zero_ptr, int zero_n, float* crop, void* stream) {
+                        int mask_pad, int border, float* prob, float* score, int32_t* zero_ptr, int zero_n, float* crop, void* stream) {
+  EINX_CHECK_ARG(mask_pad == EINX_MASK_PAD_ZERO || mask_pad == EINX_MASK_PAD_REPLICATE, "mask_pad must be EINX_MASK_PAD_ZERO or EINX_MASK_PAD_REPLICATE");
+  EINX_CHECK_ARG(!mask || (H > 0 && W > 0), "a mask needs the un-padded size");
+  const int replicate = mask_pad == EINX_MASK_PAD_REPLICATE;
   EINX_CHECK_ARG(!crop || (H > 0 && W > 0), "the cropped map needs the un-padded size");
   EINX_CHECK_ARG(logits && prob && score, "null pointer");
   EINX_CHECK_ARG(zero_n == 0 || (zero_ptr && (long)zero_n <= (long)(C == 65 ? einx_cdiv(B * hc * wc, 32) : einx_cdiv(B * hc * wc, 256)) * 256),
@@ -1002,11 +1016,11 @@ int einx_score_map_zero(const float* logits, int B, int C, int hc, int wc, const
   EINX_PROF("score_map (score65/score1)", s);
   if (C == 65) {
     const int n = B * hc * wc;
-    hipLaunchKernelGGL(score65_kernel, dim3(einx_cdiv(n, 32)), dim3(256), 0, s, logits, B, hc, wc, mask, H, W, h0, w0, dilate, border,
+    hipLaunchKernelGGL(score65_kernel, dim3(einx_cdiv(n, 32)), dim3(256), 0, s, logits, B, hc, wc, mask, H, W, h0, w0, dilate, replicate, border,
                        prob, score, zero_ptr, zero_n, crop);
   } else {
     const int n = B * hc * wc;
-    hipLaunchKernelGGL(score1_kernel, dim3(einx_cdiv(n, 256)), dim3(256), 0, s, logits, B, hc, wc, mask, H, W, h0, w0, dilate, border,
+    hipLaunchKernelGGL(score1_kernel, dim3(einx_cdiv(n, 256)), dim3(256), 0, s, logits, B, hc, wc, mask, H, W, h0, w0, dilate, replicate, border,
                        prob, score, zero_ptr, zero_n, crop);
   }
   EINX_CHECK_LAUNCH();

@@ -154,7 +154,7 @@ __device__ __forceinline__ void einx_watch_tensor(const EinxWatch& w, int t, int
 // null), and einx_detect told so (einx_extract: one launch
 // less per network on the latency-bound chain of a single-pair forward)
 int einx_score_map_zero(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int H, int W, int h0, int w0, int dilate,
-                        int border, float* prob, float* score, int32_t* zero_ptr, int zero_n, float* crop, void* stream);
+                        int mask_pad, int border, float* prob, float* score, int32_t* zero_ptr, int zero_n, float* crop, void* stream);
 // einx_detect's workspace (detect.hip); einx_extract nests it in its own and has the score kernel zero `flags`
 struct EinxDetectWs {
   float *buf0, *buf1;  // [B,Hp,Wp] each: the NMS passes ping-pong between them

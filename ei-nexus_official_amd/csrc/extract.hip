@@ -263,12 +263,18 @@ EINX_EXPORT size_t einx_extract_ws_bytes(const einx_extractor* e, int B, int H, 
 
 EINX_EXPORT int einx_extract(const einx_extractor* e, float* in, const uint8_t* mask, int B, int H, int W, int nms_iters, void* ws,
                              size_t ws_bytes, const einx_extract_out* o, void* stream) {
-  return einx_extract_watch(e, in, mask, B, H, W, nms_iters, ws, ws_bytes, o, nullptr, stream);
+  return einx_extract_pad(e, in, mask, EINX_MASK_PAD_ZERO, B, H, W, nms_iters, ws, ws_bytes, o, nullptr, stream);
 }
 
 EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uint8_t* mask, int B, int H, int W, int nms_iters, void* ws,
                                    size_t ws_bytes, const einx_extract_out* o, const einx_weight_watch* ww, void* stream) {
+  return einx_extract_pad(e, in, mask, EINX_MASK_PAD_ZERO, B, H, W, nms_iters, ws, ws_bytes, o, ww, stream);
+}
+
+EINX_EXPORT int einx_extract_pad(const einx_extractor* e, float* in, const uint8_t* mask, int mask_pad, int B, int H, int W, int nms_iters,
+                                 void* ws, size_t ws_bytes, const einx_extract_out* o, const einx_weight_watch* ww, void* stream) {
   EINX_CHECK_ARG(e && in && ws && o, "null pointer");
+  EINX_CHECK_ARG(mask_pad == EINX_MASK_PAD_ZERO || mask_pad == EINX_MASK_PAD_REPLICATE, "mask_pad must be EINX_MASK_PAD_ZERO or EINX_MASK_PAD_REPLICATE");
   EINX_CHECK_ARG(!ww || ww->struct_size == sizeof(einx_weight_watch), "einx_weight_watch::struct_size does not match this library (ABI mismatch)");
   EINX_CHECK_ARG(!ww || ww->n == 0 || (ww->n > 0 && ww->table && ww->ref && ww->scratch && ww->stale), "weight watch with null pointers");
   EINX_CHECK_ARG(o->feats && o->logits && o->raw && o->prob && o->score && o->positions && o->indices && o->counts && o->thr &&
@@ -392,7 +398,7 @@ EINX_EXPORT int einx_extract_watch(const einx_extractor* e, float* in, const uin
   const int C_det = e->det.back().cout;
   const long score_threads = (long)(C_det == 65 ? einx_cdiv(B * h * w, 32) : einx_cdiv(B * h * w, 256)) * 256;
   const bool zero_in_score = wk.det.nflags > 0 && wk.det.nflags <= score_threads;
-  rc = einx_score_map_zero(o->logits, B, C_det, h, w, mask, H, W, pl.h0, pl.w0, e->d.dilate_mask, e->d.border, o->prob, o->score,
+  rc = einx_score_map_zero(o->logits, B, C_det, h, w, mask, H, W, pl.h0, pl.w0, e->d.dilate_mask, mask_pad, e->d.border, o->prob, o->score,
                            zero_in_score ? wk.det.flags : nullptr, zero_in_score ? wk.det.nflags : 0, o->score_crop, stream);
   if (rc) {
     if (sd) (void)hipStreamWaitEvent((hipStream_t)stream, sd->join, 0);

@@ -197,9 +197,16 @@ int einx_image_prepare(float* image, int B, int C, int H, int W, long long strid
  * logits [B,C,hc,wc], C in {65,1}.  prob [B,C,hc,wc] (C==1: written with the mask/border zeros,
  * because the reference's score aliases probability there).  score [B,Hp,Wp], Hp=hc*cell.
  * mask: uint8 [B,H,W] (bool) or NULL; (h0,w0) = top/left padding of the padded map; dilate:
- * apply the 3x3 dilation (event extractors) or use the mask as is (image extractors). */
+ * apply the 3x3 dilation (event extractors) or use the mask as is (image extractors).
+ * The reference's Padder (core/modules/utils/util.py:17-32) pads a bool mask with zeros and a mask of any other dtype by
+ * repeating its edge pixels.  einx_score_map is the bool rule; einx_score_map_pad takes the rule as `mask_pad`, for a host whose
+ * bytes stand for the non-zero pixels of a mask that was not bool (the same call otherwise; EINX_ERR_ARG for another value). */
+#define EINX_MASK_PAD_ZERO 0
+#define EINX_MASK_PAD_REPLICATE 1
 int einx_score_map(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int H, int W, int h0, int w0,
                    int dilate, int border, float* prob, float* score, void* stream);
+int einx_score_map_pad(const float* logits, int B, int C, int hc, int wc, const uint8_t* mask, int mask_pad, int H, int W, int h0,
+                       int w0, int dilate, int border, float* prob, float* score, void* stream);
 
 /* remove_border_points alone, in place on [B,Hp,Wp] (detector_util.py:138-164) */
 int einx_remove_border(float* score, int B, int Hp, int Wp, int border, void* stream);
@@ -796,6 +803,9 @@ int einx_extract(const einx_extractor* e, float* in, const uint8_t* mask, int B,
 /* the same call with the weight watch riding on it (watch == NULL or watch->n == 0: exactly einx_extract) */
 int einx_extract_watch(const einx_extractor* e, float* in, const uint8_t* mask, int B, int H, int W, int nms_iters, void* ws,
                        size_t ws_bytes, const einx_extract_out* out, const einx_weight_watch* watch, void* stream);
+/* the same call with the padding rule of the mask (EINX_MASK_PAD_*, see einx_score_map_pad); the two calls above pad with zeros */
+int einx_extract_pad(const einx_extractor* e, float* in, const uint8_t* mask, int mask_pad, int B, int H, int W, int nms_iters, void* ws,
+                     size_t ws_bytes, const einx_extract_out* out, const einx_weight_watch* watch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics of the reference's test harness (the step after the path)

@@ -155,13 +155,15 @@ EXPORT void orc_logits_to_score(const float* logits, int B, int C, int hc, int w
 
 /* ---------------------------------------------------------------------------------------
  * Event-mask handling (core/modules/event_extractors/EventExtractors.py:544-550,561-562):
- * bool mask [B,H,W] is zero-padded to [Hp,Wp], optionally dilated by a 3x3 box (the reference's
- * box-filter > 0), and score is zeroed where the (dilated) mask is false.
+ * mask [B,H,W] is padded to [Hp,Wp] the way Padder.pad (core/modules/utils/util.py:17-32) pads it -- a bool mask with zeros,
+ * a mask of any other dtype by repeating its edge pixels (replicate != 0; the bytes are then its non-zero pixels) --,
+ * optionally dilated by a 3x3 box (the reference's box-filter > 0, zeros outside the padded map), and score is zeroed where
+ * the (dilated) mask is false.
  * Then remove_border_points (detector_util.py:138-164) zeroes a `border`-px frame, in place.
  * mask may be NULL (no masking).
  * ------------------------------------------------------------------------------------- */
 EXPORT void orc_mask_border(float* score, int B, int Hp, int Wp, const uint8_t* mask, int H, int W, int h0, int w0,
-                            int dilate, int border) {
+                            int dilate, int border, int replicate) {
 #pragma omp parallel for collapse(2)
   for (int b = 0; b < B; ++b)
     for (int y = 0; y < Hp; ++y)
@@ -174,8 +176,13 @@ EXPORT void orc_mask_border(float* score, int B, int Hp, int Wp, const uint8_t* 
             for (int dx = -r; dx <= r; ++dx) {
               const int yy = y + dy, xx = x + dx; /* padded-map coordinates, zero outside the map */
               if (yy < 0 || yy >= Hp || xx < 0 || xx >= Wp) continue;
-              const int sy = yy - h0, sx = xx - w0; /* constant-0 padding of the bool mask */
-              if (sy < 0 || sy >= H || sx < 0 || sx >= W) continue;
+              int sy = yy - h0, sx = xx - w0;
+              if (replicate) { /* the ring repeats the nearest mask pixel */
+                sy = sy < 0 ? 0 : (sy >= H ? H - 1 : sy);
+                sx = sx < 0 ? 0 : (sx >= W ? W - 1 : sx);
+              } else if (sy < 0 || sy >= H || sx < 0 || sx >= W) { /* constant-0 padding of the bool mask */
+                continue;
+              }
               if (mask[((size_t)b * H + sy) * W + sx]) {
                 on = 1;
                 break;

@@ -99,12 +99,15 @@ def logits_to_score(logits):
 
 
 def mask_border(score, mask, pads, dilate, border):
-    """In place on score [B,1,Hp,Wp]; mask [B,1,H,W] bool or None."""
+    """In place on score [B,1,Hp,Wp]; mask [B,1,H,W] or None.  A bool mask is padded with zeros; of a mask of another dtype the
+    non-zero pixels count and the padding ring repeats its edge pixels (Padder.pad, core/modules/utils/util.py:17-32)."""
     B, _, Hp, Wp = score.shape
     w0, w1, h0, h1 = pads
     H, W = Hp - h0 - h1, Wp - w0 - w1
-    m = None if mask is None else _c(mask, np.uint8)
-    lib().orc_mask_border(_f(score), B, Hp, Wp, None if m is None else m.ctypes.data_as(c_u8), H, W, h0, w0, int(dilate), int(border))
+    replicate = mask is not None and np.asarray(mask).dtype != np.bool_
+    m = None if mask is None else _c(np.asarray(mask) != 0, np.uint8)
+    lib().orc_mask_border(_f(score), B, Hp, Wp, None if m is None else m.ctypes.data_as(c_u8), H, W, h0, w0, int(dilate), int(border),
+                          int(replicate))
     return score
 
 
