@@ -30,7 +30,7 @@ from .core.modules.Extractors import EventKeypointsExtractor, ImageKeypointsExtr
 from .core.modules.Matchers import Matcher  # noqa: E402
 from .core.modules.matchers.MNN import NearestNeighborMatcher  # noqa: E402
 from .core.modules.matchers.lightglue import LightGlue  # noqa: E402
-from .harness import DifferentTimeEvaluator, SameTimeEvaluator  # noqa: E402
+from .harness import DifferentTimeEvaluator, HomographicEvaluator, SameTimeEvaluator  # noqa: E402
 from .datasets import EventSequence, EventWindows  # noqa: E402
 
 
@@ -51,5 +51,5 @@ def install_as_core():
     return _core
 
 
-__all__ = ["install_as_core", "SameTimeEvaluator", "DifferentTimeEvaluator", "EIM", "ImageImageMatcher", "build_model", "build_losses", "EventKeypointsExtractor", "ImageKeypointsExtractor", "Matcher",
+__all__ = ["install_as_core", "SameTimeEvaluator", "DifferentTimeEvaluator", "HomographicEvaluator", "EIM", "ImageImageMatcher", "build_model", "build_losses", "EventKeypointsExtractor", "ImageKeypointsExtractor", "Matcher",
            "NearestNeighborMatcher", "LightGlue", "default_config", "AttrDict", "native", "EventSequence", "EventWindows"]

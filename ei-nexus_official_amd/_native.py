@@ -827,6 +827,27 @@ def remap_bilinear(src, map_x, map_y):
     return dst
 
 
+WARP_MODES = {"bilinear": 0, "nearest": 1}  # einx.h: EINX_WARP_BILINEAR, EINX_WARP_NEAREST
+
+
+def warp_perspective(src, Hinv, Hd, Wd, mode="bilinear", want_valid=True):
+    """src [B,C,Hs,Ws] uint8 or fp32, Hinv [B,9] float64 (destination -> source) -> (dst [B,C,Hd,Wd] of src's type, valid uint8
+    [B,Hd,Wd] or None): einx_warp_perspective (csrc/warp.hip)"""
+    _dev_check(src, dt=src.dtype)
+    _dev_check(Hinv, dt=torch.float64)
+    if src.dtype not in (U8, F32):
+        raise TypeError(f"einx: warp_perspective takes uint8 or float32, got {src.dtype}")
+    B, C, Hs, Ws = (int(v) for v in src.shape)
+    if tuple(Hinv.shape) != (B, 9):
+        raise ValueError(f"einx: Hinv must be [{B}, 9], got {tuple(Hinv.shape)}")
+    dst = torch.empty((B, C, Hd, Wd), dtype=src.dtype, device=src.device)
+    valid = torch.empty((B, Hd, Wd), dtype=U8, device=src.device) if want_valid else None
+    with torch.cuda.device(src.device):
+        check(lib().einx_warp_perspective(_ptr(src), 0 if src.dtype == U8 else 1, B, C, Hs, Ws, _ptr(Hinv), int(Hd), int(Wd), WARP_MODES[mode],
+                                          _ptr(dst), _ptr(valid), _stream(src)), "einx_warp_perspective")
+    return dst, valid
+
+
 def events_remap(x, y, t, p, map_x, map_y, x_hi, y_hi, out=None):
     """einx_events_remap on a resident stream: (out_x, out_y, out_t, out_p, head) with the outputs sized like the inputs and
     head an int64 [2 + N] tensor whose first two words are (kept, out of map) and whose rest IS out_t's storage, so that one copy

@@ -16,6 +16,9 @@
 
                --(loss.hip, SameTimeEvaluator with losses)--> the two extractor losses per pair --> means (all-reduced across ranks)
 
+    images --(warp.hip, HomographicEvaluator)--> the image under a sampled homography + its valid mask --> the image network;
+               the same homography --> MMA / VDD / HE as above and (gt_matches.hip) ground-truth matches without depth
+
 Every batch is a `_Batch`, whichever entry point it came through: `step` and `run` differ only in how they enqueue it
 (`_enqueue_batch`), and finish it the same way (`_finish_batch`: the model's host side, `_account`, `_account_losses`).  What
 ends as a mean (metrics, losses, precision / recall) goes through one `_RunningMean` each; what ends as an AUC keeps its rows
@@ -29,7 +32,7 @@ import torch
 
 from . import _native as native
 from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, batch_homography, batch_metrics, batch_metrics_pose,
-                                            batch_relative_pose, match_pr, metric_names, pose_metric_names)
+                                            batch_relative_pose, gt_matches, match_pr, metric_names, pose_metric_names)
 from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
@@ -48,6 +51,7 @@ class _Batch(NamedTuple):
     homography: Optional[torch.Tensor] = None
     pose: Optional[tuple] = None
     depth: Optional[tuple] = None
+    image_mask: Optional[torch.Tensor] = None  # the image extractor's score mask (HomographicEvaluator: the warp's valid pixels)
 
 
 class _RunningMean:
@@ -176,13 +180,13 @@ class SameTimeEvaluator:
             stage = self._stages.get((slot, on_stage_stream, dev))
             if stage is None:  # page-locked upload path
                 stage = self._stages[(slot, on_stage_stream, dev)] = EventStage(dev)
-            im = None if on_stage_stream else self.model.enqueue_image(batch.images, None)
+            im = None if on_stage_stream else self.model.enqueue_image(batch.images, batch.image_mask)
             rep, mask = events_representation_batch(batch.events_list, (self.bins, H, W), normalize=True, device=dev, stage=stage,
                                                     on_stage_stream=on_stage_stream, representation_type=self.representation_type)
             # what the extractors saw (deterministic since round 4: bit-equal run to run); in `run`: of the batch enqueued last
             # (results lag by up to depth - 1 batches)
             self.last_inputs = (rep, mask)
-            return self.model._enqueue(rep, batch.images, mask, slot=slot, image_feats=im), mask
+            return self.model._enqueue(rep, batch.images, mask, batch.image_mask, slot=slot, image_feats=im), mask
 
     def _finish_batch(self, batch, pending, events_mask):
         """Host side of one batch: wait for the model's counts, then enqueue everything that is evaluated on its result"""
@@ -363,7 +367,49 @@ def matcher_loss_rows(rows, balancing=0.5):
     return torch.cat([vals[:, :3], row_norm[:, None]], 1)
 
 
-class DifferentTimeEvaluator(SameTimeEvaluator):
+class _MatcherLabels:
+    """What an evaluator that labels its keypoints with ground-truth matches shares, whichever geometry the labels come from
+    (DifferentTimeEvaluator: depth and motion; HomographicEvaluator: the homography it warped with): the matcher_metrics means
+    and, with matcher_loss=True, the rows of LightGlue.loss."""
+
+    def _init_labels(self, model, matcher_loss, pos_th, neg_th):
+        self._pr_mean = _RunningMean(len(MATCH_PR_NAMES))  # of the [B,4] matcher_metrics rows (a pair without keypoints has NaN rows)
+        self.gt_pos_th, self.gt_neg_th = pos_th, neg_th
+        self.last_gt = None
+        self.matcher_loss = bool(matcher_loss)
+        if self.matcher_loss and not hasattr(getattr(model.matcher, "matcher", None), "log_assignment"):
+            raise ValueError("einx: matcher_loss=True needs a LightGlue matcher: the loss is that of its assignment head (an MNN "
+                             "matcher has no parameters and no loss in the validation loop)")
+        self._nll_mean = _RunningMean(len(MATCHER_LOSS_NAMES), finite_only=True)  # of the [B,4] rows of matcher_loss_rows
+
+    def _validate_labels(self):
+        if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.early_stop_active():
+            raise ValueError("einx: matcher_loss=True with early stopping on: the loss applies the LAST assignment head, the forward's "
+                             "descriptors are those of each pair's stopping layer (LightGlue.loss refuses them too, DESIGN.md 8h)")
+        if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.point_pruning_active():
+            raise ValueError("einx: matcher_loss=True with point pruning on: the forward's descriptors hold only the surviving rows, "
+                             "the labels are those of every keypoint (LightGlue.loss refuses them too, DESIGN.md 8j)")
+
+    def _account_labels(self, gt, ef, imf):
+        self.last_gt = gt
+        self._pr_mean.add(match_pr(self.model._last_match, gt["matches0"], ef._batched.det.counts))
+        if self.matcher_loss:  # val_matcher.py:84,100: model.matcher.matcher.loss(matches, gt), VAL_loss = losses["total"].mean()
+            lg = self.model.matcher.matcher
+            rows = native.lg_assign_nll(lg._pack()[0], self.model._last_match, None, gt["matches0"], gt["matches1"], pos0=gt["pos0"],
+                                        n=ef._batched.det.counts, m=imf._batched.det.counts)
+            self._nll_mean.add(matcher_loss_rows(rows, float(lg.conf.loss.nll_balancing)))
+
+    def _label_results(self, out):
+        s, c = self._pr_mean.reduced(self.sums.device)
+        if float(c.max()) > 0:  # some rank labelled a pair that has keypoints
+            out.update(zip(MATCH_PR_NAMES, _RunningMean.means(s, c)))
+        if self.matcher_loss:
+            s, c = self._nll_mean.reduced(self.sums.device)
+            if float(c.max()) > 0:  # some rank had a pair with keypoints on both sides
+                out.update(zip(MATCHER_LOSS_NAMES, _RunningMean.means(s, c)))
+
+
+class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
     """Call pattern of test_events-image_different_time.py:187-264: the events come from frame i, the image from a LATER
     frame j of the sequence, and the two views are related by a known motion instead of the identity.
 
@@ -417,14 +463,7 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
         self._pose_rows = []
-        self._pr_mean = _RunningMean(len(MATCH_PR_NAMES))  # of the [B,4] matcher_metrics rows (a pair without keypoints has NaN rows)
-        self.gt_pos_th, self.gt_neg_th = 3, 5  # gt_matches_from_pose_depth's defaults, as val_matcher.py calls it
-        self.last_gt = None
-        self.matcher_loss = bool(matcher_loss)
-        if self.matcher_loss and not hasattr(getattr(model.matcher, "matcher", None), "log_assignment"):
-            raise ValueError("einx: matcher_loss=True needs a LightGlue matcher: the loss is that of its assignment head (an MNN "
-                             "matcher has no parameters and no loss in the validation loop)")
-        self._nll_mean = _RunningMean(len(MATCHER_LOSS_NAMES), finite_only=True)  # of the [B,4] rows of matcher_loss_rows
+        self._init_labels(model, matcher_loss, 3, 5)  # gt_matches_from_pose_depth's defaults, as val_matcher.py calls it
         # the depth / motion form of the metrics: one row layout for every batch, NaN where a batch had no depth
         self.reproj_thr = None if reproj_thr is None else tuple(reproj_thr)
         self.epi_thr = None if epi_thr is None else tuple(epi_thr)
@@ -437,12 +476,7 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         return self._step(_Batch(events_list, images, homography, pose, depth))
 
     def _validate(self, batch):
-        if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.early_stop_active():
-            raise ValueError("einx: matcher_loss=True with early stopping on: the loss applies the LAST assignment head, the forward's "
-                             "descriptors are those of each pair's stopping layer (LightGlue.loss refuses them too, DESIGN.md 8h)")
-        if getattr(self, "matcher_loss", False) and self.model.matcher.matcher.point_pruning_active():
-            raise ValueError("einx: matcher_loss=True with point pruning on: the forward's descriptors hold only the surviving rows, "
-                             "the labels are those of every keypoint (LightGlue.loss refuses them too, DESIGN.md 8j)")
+        self._validate_labels()
         if batch.depth is not None and batch.pose is None:
             raise ValueError("einx: depth=(depth0, depth1) needs pose=(K0, K1, T_0to1): ground-truth matches come from depth AND motion")
 
@@ -450,14 +484,8 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         out = super()._account(ef, imf, matches, batch)
         if batch.depth is not None:
             K0, K1, T = batch.pose
-            self.last_gt = batch_gt_matches(ef._batched, imf._batched, batch.depth[0], batch.depth[1], K0, K1, T, None, self.gt_pos_th,
-                                            self.gt_neg_th)
-            self._pr_mean.add(match_pr(self.model._last_match, self.last_gt["matches0"], ef._batched.det.counts))
-            if self.matcher_loss:  # val_matcher.py:84,100: model.matcher.matcher.loss(matches, gt), VAL_loss = losses["total"].mean()
-                lg = self.model.matcher.matcher
-                rows = native.lg_assign_nll(lg._pack()[0], self.model._last_match, None, self.last_gt["matches0"], self.last_gt["matches1"],
-                                            pos0=self.last_gt["pos0"], n=ef._batched.det.counts, m=imf._batched.det.counts)
-                self._nll_mean.add(matcher_loss_rows(rows, float(lg.conf.loss.nll_balancing)))
+            self._account_labels(batch_gt_matches(ef._batched, imf._batched, batch.depth[0], batch.depth[1], K0, K1, T, None, self.gt_pos_th,
+                                                  self.gt_neg_th), ef, imf)
         if batch.pose is not None:
             K0, K1, T = batch.pose
             self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
@@ -472,13 +500,7 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
     def result(self):
         out = super().result()
         out.update(_gathered_summary(self._pose_rows, 4, rpe_summary, self.pose_thresh))
-        s, c = self._pr_mean.reduced(self.sums.device)
-        if float(c.max()) > 0:  # some rank labelled a pair that has keypoints
-            out.update(zip(MATCH_PR_NAMES, _RunningMean.means(s, c)))
-        if self.matcher_loss:
-            s, c = self._nll_mean.reduced(self.sums.device)
-            if float(c.max()) > 0:  # some rank had a pair with keypoints on both sides
-                out.update(zip(MATCHER_LOSS_NAMES, _RunningMean.means(s, c)))
+        self._label_results(out)
         if self.reproj_thr is not None or self.epi_thr is not None:
             s, c = self._dt_mean.reduced(self.sums.device)
             means = _RunningMean.means(s, c)
@@ -491,3 +513,86 @@ class DifferentTimeEvaluator(SameTimeEvaluator):
         if self.model.event_extractor.extractor.ordering == "yx":
             xy0, xy1 = torch.flip(xy0, dims=[-1]), torch.flip(xy1, dims=[-1])
         return {"matched_kpts0": mk0, "matched_kpts1": mk1, "matched_xy0": xy0, "matched_xy1": xy1}
+
+
+class HomographicEvaluator(_MatcherLabels, SameTimeEvaluator):
+    """Same-time pairs whose image is warped by a sampled homography before the image network sees it: the
+    protocol SuperPoint, SiLK and LightGlue are validated with.  The reference's same-time script passes the identity as every
+    pair's homography, under which HE is a degenerate test (a matcher that does nothing to geometry scores well); a known
+    non-identity homography makes MMA / VDD / HE meaningful and gives exact ground-truth matches for ANY recording, with no
+    depth: the match_recall / match_precision / accuracy / average_precision rows and the matcher's validation loss that
+    DifferentTimeEvaluator can only form from depth maps.  The events stay as they are (the representations truncate event
+    coordinates: warping raw events is a different operation); the events are view 0, the warped image view 1.
+
+    * `sampler(B, (W, H)) -> [B,3,3]`: the batch's homographies, source -> destination in the continuous pixel coordinates of
+      `sparse_positions` (numpy or tensor, any float dtype), e.g. `lambda B, shape: sample_homographies(B, shape, rng=rng,
+      difficulty=0.5)` with core.geometry.homography.sample_homographies.  It is the only host work a batch adds, and it is called
+      once per batch in batch order by `step` and by `run` at every depth: a run is reproducible from the sampler's seed.
+    * `step(events_list, images)` / `run` items `(events_list, images)`: the images are warped into a NEW tensor
+      (datasets.warp.warp_perspective; the caller's tensor is not written, not even by SuperPoint's in-place scaling), the valid
+      pixels become the image extractor's score mask (an extractor that takes none, SiLK, detects on the zeros outside too), and
+      everything SameTimeEvaluator does runs under `homography=H`, HE included when `he_thresh` is set.  `last_warp` keeps
+      (H, warped, valid) of the batch enqueued last.
+    * labels: gt_matches(..., homography=H) on the forward's keypoints with `gt_pos_th` / `gt_neg_th` (gt_matches_from_homography's
+      3 and 6); `last_gt` keeps them.  `matcher_loss=True`: as DifferentTimeEvaluator, with the same refusals (an MNN matcher at
+      construction; early stopping or point pruning when a batch arrives).
+    * `result()`: the parent's keys, MATCH_PR_NAMES once a pair had keypoints, MATCHER_LOSS_NAMES when asked for, and
+      `warp_valid_ratio`, the mean share of a warped image's pixels that are valid.  Nothing is read back per batch."""
+
+    def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), he_thresh=None, he_ransac_thresh=3.0,
+                 he_conf=0.995, representation_type="VoxelGrid", losses=None, *, sampler, gt_pos_th=3, gt_neg_th=6, matcher_loss=False):
+        if not callable(sampler):
+            raise ValueError("einx: sampler must be a callable (B, (W, H)) -> [B,3,3] homographies")
+        if losses is not None:
+            raise ValueError("einx: HomographicEvaluator takes no losses: its two views are not aligned pixel by pixel, which is what "
+                             "the extractor losses compare (SameTimeEvaluator does)")
+        super().__init__(model, bins, resolution=resolution, mma_thr=mma_thr, vdd_thr=vdd_thr, he_thresh=he_thresh,
+                         he_ransac_thresh=he_ransac_thresh, he_conf=he_conf, representation_type=representation_type)
+        self.sampler = sampler
+        self._init_labels(model, matcher_loss, gt_pos_th, gt_neg_th)
+        self._valid_mean = _RunningMean(1)
+        self.last_warp = None
+
+    def _warped(self, batch):
+        """the batch `step` / `run` were given -> the batch the parent evaluates: warped images, their homographies, the valid mask"""
+        from .datasets.warp import warp_perspective
+        if batch.homography is not None or batch.pose is not None or batch.depth is not None or batch.image_mask is not None:
+            raise ValueError("einx: HomographicEvaluator takes (events_list, images) only: it samples the pair's homography itself")
+        images = batch.images
+        if not torch.is_tensor(images) or images.dim() != 4:
+            raise ValueError("einx: images must be a [B,1,H,W] tensor on the device")
+        B = int(images.shape[0])
+        H = torch.as_tensor(self.sampler(B, self.resolution))
+        if tuple(H.shape) != (B, 3, 3) or not H.is_floating_point():
+            raise ValueError(f"einx: the sampler must return [{B}, 3, 3] float homographies, got {tuple(H.shape)} {H.dtype}")
+        warped, valid = warp_perspective(images, H)
+        self.last_warp = (H, warped, valid)
+        self._valid_mean.add(valid.double().mean(dim=(1, 2, 3))[:, None])
+        return _Batch(batch.events_list, warped, H.to(images.device, torch.float32), image_mask=valid)
+
+    @torch.no_grad()
+    def step(self, events_list, images):
+        return self._step(self._warped(_Batch(events_list, images)))
+
+    @torch.no_grad()
+    def run(self, batches, depth=2):
+        """SameTimeEvaluator.run on items `(events_list, images)`; a batch is sampled and warped when the loop reaches it, so the
+        sampler's draws follow batch order at every depth"""
+        yield from super().run((self._warped(_Batch(*item)) for item in batches), depth)
+
+    def _validate(self, batch):
+        super()._validate(batch)
+        self._validate_labels()
+
+    def _account(self, ef, imf, matches, batch):
+        out = super()._account(ef, imf, matches, batch)
+        ev, im = ef._batched, imf._batched
+        self._account_labels(gt_matches(ev.det.positions, im.det.positions, ev.det.counts, im.det.counts, homography=batch.homography,
+                                        pos_th=self.gt_pos_th, neg_th=self.gt_neg_th, ordering=ev.ordering), ef, imf)
+        return out
+
+    def result(self):
+        out = super().result()
+        self._label_results(out)
+        out["warp_valid_ratio"] = _RunningMean.means(*self._valid_mean.reduced(self.sums.device))[0]
+        return out

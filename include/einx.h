@@ -642,6 +642,29 @@ int einx_events_remap(const float* x, const float* y, const double* t, const flo
 int einx_events_remap_chunk(void); /* events per workgroup of einx_events_remap (host only) */
 
 /* ------------------------------------------------------------------------------------------
+ * Perspective warp of a batch of images (csrc/warp.hip): view 1 of a homographic pair
+ * The reference has the sampler of the homographies (core/geometry/homography.py) and nothing that warps an image with one.
+ * src [B,C,Hs,Ws] -> dst [B,C,Hd,Wd], both uint8 or both fp32 (the src_type codes of einx_remap_bilinear), one matrix per sample:
+ * Hinv double[B,9] row-major ON THE DEVICE, the destination -> source map (the caller inverts the homography once, in float64).
+ * Pixel (r, c) sits at (x, y) = (c + 0.5, r + 0.5).  For every destination pixel, in float64 with every operation rounded as
+ * written: X = (h0 x + h1 y) + h2, Y = (h3 x + h4 y) + h5, w = (h6 x + h7 y) + h8, qx = X / w, qy = Y / w.  The pixel is VALID iff
+ * w is finite and > 0, 0.5 <= qx <= Ws - 0.5 and 0.5 <= qy <= Hs - 0.5: all four taps lie inside the source.  An invalid pixel is 0
+ * in every channel and in `valid`; there is no border blending.  A valid one samples the source at index coordinates
+ * (sx, sy) = (qx - 0.5, qy - 0.5):
+ *   EINX_WARP_BILINEAR: x0 = floor(sx), fx = (float)(sx - x0), gx = 1 - fx (y likewise), w00 = gx gy, w01 = fx gy, w10 = gx fy,
+ *     w11 = fx fy, v = ((w00 I00 + w01 I01) + w10 I10) + w11 I11, all fp32; a tap at x0 + 1 == Ws or y0 + 1 == Hs (weight 0) reads
+ *     as 0; NaN in any other tap propagates; uint8 output is rint(v) (half to even) clamped to 0..255.
+ *   EINX_WARP_NEAREST: the source pixel (rint(sy), rint(sx)), half to even, copied bit for bit: what a mask needs.
+ * valid: uint8 [B,Hd,Wd] or NULL.  Enqueues on `stream`, takes no workspace, allocates nothing, waits for nothing and can be
+ * captured; no atomics: two calls give the same bits.  EINX_ERR_ARG: a negative size, an unknown src_type or mode, a null pointer
+ * that would be read or written.  B, Hd or Wd == 0 (or C == 0 without `valid`) succeeds and launches nothing; Hs or Ws == 0
+ * makes every pixel invalid.
+ * ------------------------------------------------------------------------------------------ */
+enum { EINX_WARP_BILINEAR = 0, EINX_WARP_NEAREST = 1 };
+int einx_warp_perspective(const void* src, int src_type, int B, int C, int Hs, int Ws, const double* Hinv, int Hd, int Wd, int mode, void* dst,
+                          uint8_t* valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pose tracks and the depth / image pairing of a recording (csrc/posetrack.hip)
  * replaces: datasets/Interpolator.py (PoseInterpolator), datasets/MVSEC.py:818-830 (get_relative_pose), :362-369 (nearest pairing)
  * A track is N >= 2 knots on the device: stamps double[N] strictly increasing (epoch seconds: float32 cannot hold them),
