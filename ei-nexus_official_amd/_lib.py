@@ -85,6 +85,27 @@ class GtDenseParams(ctypes.Structure):
                                                                                                                       ("neg_sq", c_float)]
 
 
+class GeomSide(ctypes.Structure):
+    _ptrs = ("kp", "count", "depth", "d_in", "valid_in", "depth_other", "dj_in", "validj_in", "K", "K_other", "T", "T_other", "d_out", "valid_out",
+             "proj", "visible")
+    _fields_ = [(n, c_void_p) for n in _ptrs] + [(n, ctypes.c_int32) for n in ("cap", "cols", "H", "W", "Ho", "Wo")]
+
+
+class GeomProjectParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "sides", "kp_yx", "cc")] + [("cc_bound", c_float),
+                                                                                                          ("side", GeomSide * 2)]
+
+
+class GeomDenseSide(ctypes.Structure):
+    _ptrs = ("depth", "depth_other", "K", "K_other", "T", "T_other", "warp", "visible")
+    _fields_ = [(n, c_void_p) for n in _ptrs] + [(n, ctypes.c_int32) for n in ("H", "W", "Ho", "Wo")]
+
+
+class GeomDenseParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "sides", "cc")] + [("cc_bound", c_float), ("counts", c_void_p),
+                                                                                                  ("side", GeomDenseSide * 2)]
+
+
 class EventArrays(ctypes.Structure):
     _fields_ = [("x", c_void_p), ("y", c_void_p), ("t", c_void_p), ("p", c_void_p), ("x_type", ctypes.c_int32), ("y_type", ctypes.c_int32),
                 ("t_type", ctypes.c_int32), ("p_type", ctypes.c_int32), ("n", ctypes.c_int64)]
@@ -228,6 +249,10 @@ SIGNATURES = {
     "einx_gt_matches": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 30),
     "einx_gt_dense_ws_bytes": (c_size_t, [ctypes.POINTER(GtDenseParams)]),
     "einx_gt_dense": (c_int, [ctypes.POINTER(GtDenseParams)] + [c_void_p] * 23),
+    "einx_geom_project": (c_int, [ctypes.POINTER(GeomProjectParams), c_void_p]),
+    "einx_geom_dense_warp": (c_int, [ctypes.POINTER(GeomDenseParams), c_void_p]),
+    "einx_geom_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_epipolar_all": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "einx_match_pr": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "einx_desc_loss_ws_bytes": (c_size_t, [c_int] * 11),
     "einx_desc_loss": (c_int, [c_void_p, c_float, c_void_p, c_float] + [c_int] * 11 + [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -36,6 +36,19 @@ class Pose:
         back = self.rotation.mT
         return Pose(back, torch.matmul(back, -self.translation[..., None])[..., 0])
 
+    def transform(self, p3d):
+        """q = R p + t for points [..., N, 3] (rows times R^T, plus t)"""
+        if p3d.shape[-1] != 3:
+            raise ValueError("einx: Pose.transform takes points [..., 3]")
+        return torch.matmul(p3d, self.rotation.mT) + self.translation[..., None, :]
+
+    def __matmul__(self, other):
+        """T_b2c @ T_a2b: the chained pose a -> c; T @ points: transform"""
+        if isinstance(other, Pose):
+            shifted = torch.matmul(self.rotation, other.translation[..., None])[..., 0]
+            return Pose(torch.matmul(self.rotation, other.rotation), self.translation + shifted)
+        return self.transform(other)
+
     def to_4x4mat(self):
         bottom = self.rotation.new_tensor([0.0, 0.0, 0.0, 1.0]).expand(self.rotation.shape[:-2] + (1, 4))
         return torch.cat([torch.cat([self.rotation, self.translation[..., None]], -1), bottom], -2)
@@ -72,3 +85,21 @@ class Camera:
     @property
     def size(self):
         return 2 * self.c
+
+    eps = 1e-4  # a point is in front of the camera when z > eps; z is clamped there before the division
+
+    def image2cam(self, p2d):
+        """pixels [..., N, 2] -> homogeneous points on the plane z = 1, [..., N, 3]"""
+        if p2d.shape[-1] != 2:
+            raise ValueError("einx: Camera.image2cam takes pixels [..., 2]")
+        flat = (p2d - self.c[..., None, :]) / self.f[..., None, :]
+        return torch.cat([flat, torch.ones_like(flat[..., 0:1])], -1)
+
+    def cam2image(self, p3d):
+        """points [..., N, 3] -> (pixels [..., N, 2], valid [..., N]): valid = in front (z > eps) and 0 <= pixel <= 2c - 1"""
+        if p3d.shape[-1] != 3:
+            raise ValueError("einx: Camera.cam2image takes points [..., 3]")
+        depth = p3d[..., 2]
+        p2d = p3d[..., 0:2] / depth.clamp(min=self.eps)[..., None] * self.f[..., None, :] + self.c[..., None, :]
+        last = (self.size - 1)[..., None, :]
+        return p2d, (depth > self.eps) & ((p2d >= 0) & (p2d <= last)).all(-1)

@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, check
+from ..._lib import GeomDenseParams, GeomProjectParams, GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -468,8 +468,13 @@ def gt_matches_dense(depth0, depth1, K0, K1, T_0to1, T_1to0=None, pos_th=3, neg_
 
 
 @on_input_device
-def batch_gt_matches(ev_batched, im_batched, depth0, depth1, K0, K1, T_0to1, T_1to0=None, pos_th=3, neg_th=5):
-    """gt_matches of the keypoints of an EIM.forward_batched result (BatchedFeats x2: positions [B,cap,3] + counts), no host sync"""
+def batch_gt_matches(ev_batched, im_batched, depth0, depth1, K0, K1, T_0to1, T_1to0=None, pos_th=3, neg_th=5, cc_th=None):
+    """gt_matches of the keypoints of an EIM.forward_batched result (BatchedFeats x2: positions [B,cap,3] + counts), no host sync.
+    cc_th (a bound on the SQUARED cycle distance; None: off, the calls are those of gt_matches) labels through
+    gt_matches_cc: keypoints the other view's depth map says are hidden stop being visible."""
+    if cc_th is not None:
+        return gt_matches_cc(ev_batched.det.positions, im_batched.det.positions, ev_batched.det.counts, im_batched.det.counts, depth0, depth1,
+                             K0, K1, T_0to1, T_1to0, cc_th=cc_th, pos_th=pos_th, neg_th=neg_th, ordering=ev_batched.ordering)
     return gt_matches(ev_batched.det.positions, im_batched.det.positions, ev_batched.det.counts, im_batched.det.counts, depth0, depth1, K0, K1,
                       T_0to1, T_1to0, pos_th=pos_th, neg_th=neg_th, ordering=ev_batched.ordering)
 
@@ -495,4 +500,168 @@ def match_pr(mr, gt_m0, n=None, scores0=None):
     out = torch.empty((B, 4), dtype=torch.float64, device=dev)
     check(N.lib().einx_match_pr(N._ptr(matches0), N._ptr(scores0), N._ptr(gt_m0), N._ptr(n), B, cap, N._ptr(out), N._stream(matches0)),
           "einx_match_pr")
+    return out
+
+
+# ---- core.geometry.depth / .epipolar on the device (csrc/geometry.hip) --------------------------------------------
+def _map3(d, B, dev):
+    return None if d is None else d.to(dev, torch.float32).reshape(B, d.shape[-2], d.shape[-1]).contiguous()
+
+
+def _geom_side(B, dev, kp, count, K, K_other, T, T_other, depth=None, d=None, valid=None, depth_other=None, dj=None, validj=None):
+    """one direction of einx_geom_project: the tensors it reads (kept alive by the returned dict) and the ones it writes"""
+    N._dev_check(kp)
+    cap = kp.shape[1]
+    f = lambda t: None if t is None else t.to(dev, torch.float32).reshape(B, cap).contiguous()  # noqa: E731
+    u8 = lambda t: None if t is None else t.to(dev, torch.uint8).reshape(B, cap).contiguous()  # noqa: E731
+    if (T is None) and (T_other is None):
+        raise ValueError("einx: a projection needs the motion of its direction or of the other one")
+    if (d is None) != (valid is None) or (dj is None) != (validj is None):
+        raise ValueError("einx: given depths come with their validity")
+    if d is None and depth is None:
+        raise ValueError("einx: a projection needs this view's depth map or the points' depths")
+    return {"kp": kp, "count": None if count is None else _counts(count, B, cap, dev), "depth": None if d is not None else _map3(depth, B, dev),
+            "d_in": f(d), "valid_in": u8(valid), "depth_other": None if dj is not None else _map3(depth_other, B, dev), "dj_in": f(dj),
+            "validj_in": u8(validj), "K": _f32c(K, dev, (B, 9)), "K_other": _f32c(K_other, dev, (B, 9)),
+            "T": None if T is None else _f32c(T, dev, (B, 16)), "T_other": None if T_other is None else _f32c(T_other, dev, (B, 16)),
+            "d_out": torch.empty((B, cap), dtype=torch.float32, device=dev), "valid_out": torch.empty((B, cap), dtype=torch.uint8, device=dev),
+            "proj": torch.empty((B, cap, 2), dtype=torch.float32, device=dev), "visible": torch.empty((B, cap), dtype=torch.uint8, device=dev)}
+
+
+def _geom_project_sides(sides, cc_bound, ordering):
+    """einx_geom_project for one or two prepared sides (one launch); cc_bound None: no cycle check"""
+    kp = sides[0]["kp"]
+    p = GeomProjectParams()
+    p.struct_size = ctypes.sizeof(GeomProjectParams)
+    p.B, p.sides, p.kp_yx = kp.shape[0], len(sides), int(ordering == "yx")
+    p.cc, p.cc_bound = int(cc_bound is not None), 0.0 if cc_bound is None else float(cc_bound)
+    for k, s in enumerate(sides):
+        if p.cc and s["depth_other"] is None and s["dj_in"] is None:
+            raise ValueError("einx: the cycle check needs the other view's depth map or its depths under the projections")
+        c = p.side[k]
+        for name in c._ptrs:
+            setattr(c, name, N._ptr(s[name]))
+        c.cap, c.cols = s["kp"].shape[1], s["kp"].shape[2]
+        if s["depth"] is not None:
+            c.H, c.W = s["depth"].shape[1:]
+        if s["depth_other"] is not None:
+            c.Ho, c.Wo = s["depth_other"].shape[1:]
+    check(N.lib().einx_geom_project(ctypes.byref(p), N._stream(kp)), "einx_geom_project")
+
+
+@on_input_device
+def geom_project(kp, K_i, K_j, T_itoj=None, T_jtoi=None, depth_i=None, d=None, valid=None, depth_j=None, dj=None, validj=None, count=None,
+                 cc_bound=None, ordering="xy"):
+    """depth.py's project for one direction (einx_geom_project), no host sync.  kp [B,cap,cols>=2] float32, K [B,3,3],
+    T_itoj [B,4,4] (None: the inverse of T_jtoi, taken in the kernel); the points' depths d / valid [B,cap], or depth_i [B,H,W] to
+    sample them from; count int32 [B] or None.  cc_bound None: no cycle check.  Otherwise it bounds the SQUARED cycle distance
+    (strictly) and needs depth_j [B,Hj,Wj], or dj / validj [B,cap]: the other view's depth under each projection, for a caller that
+    samples it its own way between two calls.  Returns proj [B,cap,2] (x, y), visible, depth, valid (bool)."""
+    B, dev = kp.shape[0], kp.device
+    s = _geom_side(B, dev, kp, count, K_i, K_j, T_itoj, T_jtoi, depth_i, d, valid, depth_j, dj, validj)
+    _geom_project_sides([s], cc_bound, ordering)
+    return {"proj": s["proj"], "visible": s["visible"].bool(), "depth": s["d_out"], "valid": s["valid_out"].bool()}
+
+
+@on_input_device
+def gt_matches_cc(kp0, kp1, n=None, m=None, depth0=None, depth1=None, K0=None, K1=None, T_0to1=None, T_1to0=None, cc_th=None, pos_th=3,
+                  neg_th=5, ordering="yx"):
+    """gt_matches (pose form, depth maps) whose visibility also asks the other view's depth map: stage A with the
+    cycle check for both sides in one launch (einx_geom_project), then the unchanged stage B (einx_gt_label).  cc_th bounds the
+    SQUARED cycle distance in pixels^2, strictly, as the reference's project(ccth=) does (a caller thinking in pixels passes
+    th ** 2); None: no check, and every tensor equals gt_matches'.  Returns the same dict as gt_matches."""
+    B, dev = kp0.shape[0], kp0.device
+    kp0, kp1 = kp0.float().contiguous(), kp1.float().contiguous()
+    if kp1.shape[0] != B:
+        raise ValueError("einx: kp0 and kp1 differ in batch size")
+    if depth0 is None or depth1 is None:
+        raise ValueError("einx: gt_matches_cc needs both depth maps")
+    n, m = _counts(n, B, kp0.shape[1], dev), _counts(m, B, kp1.shape[1], dev)
+    s0 = _geom_side(B, dev, kp0, n, K0, K1, T_0to1, T_1to0, depth=depth0, depth_other=depth1)
+    s1 = _geom_side(B, dev, kp1, m, K1, K0, T_1to0, T_0to1, depth=depth1, depth_other=depth0)
+    _geom_project_sides([s0, s1], cc_th, ordering)
+    o = {"proj_0to1": s0["proj"], "proj_1to0": s1["proj"], "depth_keypoints0": s0["d_out"], "depth_keypoints1": s1["d_out"],
+         "valid0": s0["valid_out"], "valid1": s1["valid_out"], "visible0": s0["visible"], "visible1": s1["visible"]}
+    o.update(gt_label(kp0, kp1, n, m, o["proj_0to1"], o["proj_1to0"], o["visible0"], o["visible1"], o["valid0"], o["valid1"], pos_th, neg_th,
+                      ordering))
+    return _bools(o)
+
+
+@on_input_device
+def geom_dense_warp(depth_i, depth_j, K_i, K_j, T_itoj=None, T_jtoi=None, cc_bound=None, both=False):
+    """depth.py's dense_warp_consistency on raw tensors (einx_geom_dense_warp), no host sync: every pixel centre of
+    depth_i [B,Hi,Wi] at its own depth into view j; cc_bound as geom_project (it needs depth_j [B,Hj,Wj]).  Returns warp
+    [B,Hi,Wi,2] (x, y), visible [B,Hi,Wi] bool and counts int32 [B,2] = #(depth > 0), #visible.  With `both`, the other direction
+    rides on the same launch: warp1 / visible1 over depth_j's pixels, counts [B,2,2]."""
+    dev = depth_i.device
+    B = K_i.reshape(-1, 9).shape[0]
+    di, dj = _map3(depth_i, B, dev), _map3(depth_j, B, dev)
+    N._dev_check(di, dj)
+    if (cc_bound is not None or both) and dj is None:
+        raise ValueError("einx: the cycle check and the second direction need depth_j")
+    if T_itoj is None and T_jtoi is None:
+        raise ValueError("einx: a projection needs the motion of its direction or of the other one")
+    Ki, Kj = _f32c(K_i, dev, (B, 9)), _f32c(K_j, dev, (B, 9))
+    Tij = None if T_itoj is None else _f32c(T_itoj, dev, (B, 16))
+    Tji = None if T_jtoi is None else _f32c(T_jtoi, dev, (B, 16))
+    p = GeomDenseParams()
+    p.struct_size = ctypes.sizeof(GeomDenseParams)
+    p.B, p.sides = B, 2 if both else 1
+    p.cc, p.cc_bound = int(cc_bound is not None), 0.0 if cc_bound is None else float(cc_bound)
+    counts = torch.empty((B, p.sides, 2), dtype=torch.int32, device=dev)
+    p.counts = N._ptr(counts)
+    out = {}
+    keep = []
+    for k, (ds, do, Ks, Ko, T, To) in enumerate(((di, dj, Ki, Kj, Tij, Tji), (dj, di, Kj, Ki, Tji, Tij))[:p.sides]):
+        warp = torch.empty(ds.shape + (2,), dtype=torch.float32, device=dev)
+        vis = torch.empty(ds.shape, dtype=torch.uint8, device=dev)
+        c = p.side[k]
+        for name, t in zip(c._ptrs, (ds, do, Ks, Ko, T, To, warp, vis)):
+            setattr(c, name, N._ptr(t))
+        c.H, c.W = ds.shape[1:]
+        if do is not None:
+            c.Ho, c.Wo = do.shape[1:]
+        keep.append((warp, vis))
+    check(N.lib().einx_geom_dense_warp(ctypes.byref(p), N._stream(di)), "einx_geom_dense_warp")
+    out = {"warp": keep[0][0], "visible": keep[0][1].bool(), "counts": counts if both else counts[:, 0]}
+    if both:
+        out.update(warp1=keep[1][0], visible1=keep[1][1].bool())
+    return out
+
+
+@on_input_device
+def geom_sample(pts, fmap, depth_rule=False):
+    """depth.py's sample_fmap (einx_geom_sample): fmap [B,C,H,W] at pts [B,N,2] (x, y) -> [B,N,C] with stage A's depth
+    sampler per channel, a hole being a NaN.  depth_rule (C == 1): a hole is <= 0 or NaN as in sample_depth; returns (out, valid
+    [B,N] bool)."""
+    B, C, H, W = fmap.shape
+    dev = fmap.device
+    fmap = fmap.to(torch.float32).contiguous()
+    pts = pts.to(dev, torch.float32).contiguous()
+    N._dev_check(fmap, pts)
+    if pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] != 2:
+        raise ValueError("einx: pts is [B,N,2] with the map's batch size")
+    if depth_rule and C != 1:
+        raise ValueError("einx: the depth rule samples one channel")
+    n = pts.shape[1]
+    out = torch.empty((B, n, C), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, n), dtype=torch.uint8, device=dev) if depth_rule else None
+    check(N.lib().einx_geom_sample(N._ptr(fmap), B, C, H, W, N._ptr(pts), n, int(depth_rule), N._ptr(out), N._ptr(valid), N._stream(fmap)),
+          "einx_geom_sample")
+    return (out, valid.bool()) if depth_rule else out
+
+
+@on_input_device
+def epipolar_all(p0, p1, E, eps=1e-15):
+    """epipolar.py's sym_epipolar_distance_all (einx_epipolar_all): p0 [B,N,2|3], p1 [B,M,2|3], E [B,3,3] -> [B,N,M]
+    float32, no host sync"""
+    B, dev = p0.shape[0], p0.device
+    p0, p1 = p0.to(torch.float32).contiguous(), p1.to(dev, torch.float32).contiguous()
+    N._dev_check(p0, p1)
+    if p0.dim() != 3 or p1.dim() != 3 or p1.shape[0] != B or p0.shape[2] not in (2, 3) or p1.shape[2] not in (2, 3):
+        raise ValueError("einx: p0 is [B,N,2|3] and p1 [B,M,2|3]")
+    E = _f32c(E, dev, (B, 9))
+    out = torch.empty((B, p0.shape[1], p1.shape[1]), dtype=torch.float32, device=dev)
+    check(N.lib().einx_epipolar_all(N._ptr(p0), p0.shape[2], N._ptr(p1), p1.shape[2], N._ptr(E), B, p0.shape[1], p1.shape[1], float(eps),
+                                    N._ptr(out), N._stream(p0)), "einx_epipolar_all")
     return out

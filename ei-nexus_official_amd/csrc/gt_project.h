@@ -2,7 +2,7 @@
 // through a depth map: gt_matches.hip (ground-truth labels) and metrics.hip (einx_pair_metrics_pose).  One text, so
 // that both produce the same bits.  fp32, unfused (-ffp-contract=off).
 //
-// Replaces (reference file:line): core/geometry/depth.py:9-60 (sample_depth, project), core/geometry/wrappers.py:337-385
+// Replaces (reference file:line): core/geometry/depth.py:9-69 (sample_fmap, sample_depth, project), core/geometry/wrappers.py:337-385
 // (pinhole cam2image).
 #pragma once
 #include "einx_common.h"
@@ -11,7 +11,9 @@ namespace {
 
 // sample_depth (depth.py:9-25): bilinear with zero padding at ix = x - 0.5; a hole (<= 0 or NaN) under a tap of non-zero weight
 // sends the whole sample to the nearest pixel (half to even), NaN when that is a hole, 0 outside the map
-__device__ __forceinline__ float gt_sample_depth(const float* dm, int H, int W, float x, float y) {
+// NAN_HOLE: the same sampler for a feature map (depth.py:9-17, sample_fmap): a hole is a NaN and nothing else
+template <bool NAN_HOLE>
+__device__ __forceinline__ float gt_sample_map(const float* dm, int H, int W, float x, float y) {
   const float nan = einx_u2f(0x7fc00000u);
   const float ix = x - 0.5f, iy = y - 0.5f;
   const float fx0 = floorf(ix), fy0 = floorf(iy);
@@ -31,7 +33,7 @@ __device__ __forceinline__ float gt_sample_depth(const float* dm, int H, int W, 
       if (xx < 0 || xx >= W || yy < 0 || yy >= H) continue;
       const float w = wx[dx] * wy[dy];
       const float v = dm[(size_t)yy * W + xx];
-      if (!(v > 0.0f)) {
+      if (NAN_HOLE ? v != v : !(v > 0.0f)) {
         if (w != 0.0f) hole = true;
         continue;
       }
@@ -42,15 +44,16 @@ __device__ __forceinline__ float gt_sample_depth(const float* dm, int H, int W, 
   const float nx = nearbyintf(ix), ny = nearbyintf(iy);  // round half to even (the default rounding mode)
   if (!(nx >= 0.0f && nx < (float)W && ny >= 0.0f && ny < (float)H)) return 0.0f;
   const float v = dm[(size_t)(int)ny * W + (int)nx];
+  if (NAN_HOLE) return v;
   return v > 0.0f ? v : nan;
 }
 
-// depth.py:37-60 with ccth=None for one point (x, y) of depth d: image2cam, scale by the depth, transform by T (this view -> the
-// other; null: (R^T, -R^T t) of T_other), pinhole cam2image of the other camera Ko.  (u, v) is the projection, NaN where d is; the
-// return value is "in front of the other camera and inside its image"
-__device__ __forceinline__ bool gt_project_point(float x, float y, float d, const float* Ks, const float* Ko, const float* T,
-                                                 const float* T_other, float* u_out, float* v_out) {
-  float R[9], t[3];
+__device__ __forceinline__ float gt_sample_depth(const float* dm, int H, int W, float x, float y) {
+  return gt_sample_map<false>(dm, H, W, x, y);
+}
+
+// (R, t) of the motion this view -> the other: T's, or with T null (R^T, -R^T t) of T_other
+__device__ __forceinline__ void gt_pose_rt(const float* T, const float* T_other, float* R, float* t) {
   if (T) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -67,7 +70,11 @@ __device__ __forceinline__ bool gt_project_point(float x, float y, float d, cons
 #pragma unroll
     for (int q = 0; q < 3; ++q) t[q] = -((R[3 * q] * T[3] + R[3 * q + 1] * T[7]) + R[3 * q + 2] * T[11]);
   }
-  // image2cam, scale by the depth, transform, cam2image (pinhole)
+}
+
+// image2cam of camera Ks, scale by the depth, transform by (R, t), cam2image (pinhole) of camera Ko
+__device__ __forceinline__ bool gt_transform_project(float x, float y, float d, const float* Ks, const float* Ko, const float* R,
+                                                     const float* t, float* u_out, float* v_out) {
   const float px = ((x - Ks[2]) / Ks[0]) * d, py = ((y - Ks[5]) / Ks[4]) * d, pz = d;
   const float qx = ((px * R[0] + py * R[1]) + pz * R[2]) + t[0];
   const float qy = ((px * R[3] + py * R[4]) + pz * R[5]) + t[1];
@@ -81,6 +88,62 @@ __device__ __forceinline__ bool gt_project_point(float x, float y, float d, cons
   *u_out = u;
   *v_out = v;
   return front && u >= 0.0f && u <= wmax && v >= 0.0f && v <= hmax;
+}
+
+// depth.py:37-60 with ccth=None for one point (x, y) of depth d: image2cam, scale by the depth, transform by T (this view -> the
+// other; null: (R^T, -R^T t) of T_other), pinhole cam2image of the other camera Ko.  (u, v) is the projection, NaN where d is; the
+// return value is "in front of the other camera and inside its image"
+__device__ __forceinline__ bool gt_project_point(float x, float y, float d, const float* Ks, const float* Ko, const float* T,
+                                                 const float* T_other, float* u_out, float* v_out) {
+  float R[9], t[3];
+  gt_pose_rt(T, T_other, R, t);
+  return gt_transform_project(x, y, d, Ks, Ko, R, t, u_out, v_out);
+}
+
+// The other view's depth under a projection, for the cycle check of gt_project_cc: the map dm [H,W] is sampled at (u, v) with
+// gt_sample_depth, or (dm null) the caller sampled it already: dj with its validity
+struct GtOtherDepth {
+  const float* dm;
+  int H, W;
+  float dj;
+  bool validj;
+};
+
+// depth.py:37-69 for one point: gt_project_point, bit for bit, for (u, v) and -- without `cc` -- for the return value.  With
+// `cc` (ccth given) the point must also survive the way back: the other view's depth dj at (u, v) must be valid (not NaN, > 0),
+// (u, v) at depth dj taken through the INVERSE OF THE FORWARD MOTION (depth.py:65 T_itoj.inv(): (R^T, -R^T t) of the (R, t) used
+// above, whichever way that was obtained; not the caller's pose of the other direction) must land in front of and inside this
+// view's camera (2c - 1 bounds), and (x - x')^2 + (y - y')^2 < bound, strictly; a NaN fails.  The bound is compared with the
+// SQUARED distance as given (the reference compares squared pixels with its unsquared ccth).  *dj_out: the depth that was used.
+__device__ __forceinline__ bool gt_project_cc(float x, float y, float d, const float* Ks, const float* Ko, const float* T,
+                                              const float* T_other, bool cc, float bound, const GtOtherDepth& od, float* u_out,
+                                              float* v_out, float* dj_out) {
+  float R[9], t[3];
+  gt_pose_rt(T, T_other, R, t);
+  float u, v;
+  const bool seen = gt_transform_project(x, y, d, Ks, Ko, R, t, &u, &v);
+  *u_out = u;
+  *v_out = v;
+  if (!cc) return seen;
+  float dj = od.dj;
+  bool validj = od.validj;
+  if (od.dm) {
+    dj = gt_sample_depth(od.dm, od.H, od.W, u, v);
+    validj = dj == dj && dj > 0.0f;
+  }
+  *dj_out = dj;
+  float Ri[9], ti[3];  // Pose.inv of (R, t)
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Ri[3 * q + c] = R[3 * c + q];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) ti[q] = -((Ri[3 * q] * t[0] + Ri[3 * q + 1] * t[1]) + Ri[3 * q + 2] * t[2]);
+  float bx, by;
+  const bool back = gt_transform_project(u, v, dj, Ko, Ks, Ri, ti, &bx, &by);
+  const float ex = x - bx, ey = y - by;
+  const bool consistent = (ex * ex + ey * ey) < bound;
+  return seen && consistent && back && validj;
 }
 
 // q.z of gt_project_point alone: the same products in the same order, so `gt_point_qz(...) > 1e-4f` is that function's `front`

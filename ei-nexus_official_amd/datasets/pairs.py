@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from ..core.geometry.gt_generation import valid_ratio
-from ..core.metrics._native_metrics import gt_matches_dense, relative_pose
+from ..core.metrics._native_metrics import geom_dense_warp, gt_matches_dense, relative_pose
 
 
 def grid_keypoints(H, W, ordering="yx", device=None):
@@ -27,6 +27,16 @@ def covisibility(depth0, depth1, K0, K1, T_0to1, T_1to0=None, pos_th=3, neg_th=5
     #visible0, #visible1, "valid_ratio": [B] float32}.  Arguments as gt_matches_dense."""
     c = gt_matches_dense(depth0, depth1, K0, K1, T_0to1, T_1to0, pos_th=pos_th, neg_th=neg_th, idx0=idx0, idx1=idx1, labels=False)["counts"]
     return {"counts": c, "valid_ratio": valid_ratio(c)}
+
+
+def pair_overlap(depth0, depth1, K0, K1, T_0to1, T_1to0=None, cc_th=None):
+    """[B,2] float32 overlap of each pair, no host sync: column 0 the share of view 0's valid pixels (depth > 0) that view 1 sees,
+    column 1 the same for view 1, from the counts of one dense-warp launch over both directions (einx_geom_dense_warp, DESIGN.md
+    8t).  cc_th (None: off) bounds the SQUARED cycle distance in pixels^2, so that a pixel hidden behind a nearer surface of the
+    other view is not counted as seen.  A view without a valid pixel gives NaN (0 / 0).  depth [B,H,W], K [B,3,3], T [B,4,4]
+    (T_1to0 None: the inverse of T_0to1, taken in the kernel)."""
+    c = geom_dense_warp(depth0, depth1, K0, K1, T_0to1, T_1to0, cc_bound=cc_th, both=True)["counts"].to(torch.float32)
+    return c[:, :, 1] / c[:, :, 0]
 
 
 def rigid_inverse(T):

@@ -439,6 +439,12 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
       lines (no depth needed).  One call serves both; each key is the mean over the pairs where it is finite and appears once some
       pair gave a finite value.  `occlusion_th` (pixels) drops keypoints and matches the other view's depth map says are hidden;
       without `reproj_thr` it raises.  The returned rows are unchanged.
+    * `label_cc_th=` (pixels; None by default: nothing changes and nothing extra is launched).  The labels above call a keypoint
+      visible when it projects in front of and inside the other camera, whatever stands in between.  With `label_cc_th` a batch
+      with pose and depth is labelled through gt_matches_cc: the other view's depth map is sampled at the
+      projection, the point is taken back, and it stays visible only when it returns within `label_cc_th` pixels of where it
+      started (the reference's project(ccth=), here with label_cc_th^2 as the bound on the squared distance).  A hidden keypoint
+      can then neither become a positive nor block one; match_*, average_precision and matcher_loss follow from those labels.
     * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
       RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
       all-gathered before the AUC.  Once depth was given: the four matcher_metrics means over the pairs that have keypoints.
@@ -449,7 +455,10 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
                  ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None,
-                 matcher_loss=False, reproj_thr=None, epi_thr=None, occlusion_th=None):
+                 matcher_loss=False, reproj_thr=None, epi_thr=None, occlusion_th=None, label_cc_th=None):
+        if label_cc_th is not None and not float(label_cc_th) > 0:
+            raise ValueError("einx: label_cc_th is a distance in pixels (> 0), or None for labels without the occlusion check")
+        self.label_cc_th = None if label_cc_th is None else float(label_cc_th)
         if occlusion_th is not None and reproj_thr is None:
             raise ValueError("einx: occlusion_th needs reproj_thr: the occlusion check belongs to the depth form of the metrics")
         for name, thr in (("reproj_thr", reproj_thr), ("epi_thr", epi_thr)):
@@ -484,8 +493,9 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
         out = super()._account(ef, imf, matches, batch)
         if batch.depth is not None:
             K0, K1, T = batch.pose
+            cc = None if self.label_cc_th is None else self.label_cc_th ** 2  # pixels -> the bound on the squared cycle distance
             self._account_labels(batch_gt_matches(ef._batched, imf._batched, batch.depth[0], batch.depth[1], K0, K1, T, None, self.gt_pos_th,
-                                                  self.gt_neg_th), ef, imf)
+                                                  self.gt_neg_th, cc_th=cc), ef, imf)
         if batch.pose is not None:
             K0, K1, T = batch.pose
             self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,

@@ -1044,6 +1044,91 @@ int einx_gt_dense(const einx_gt_dense_params* p, const float* depth0, const floa
                   int64_t* matches1, float* scores0, float* scores1, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * core.geometry.depth and core.geometry.epipolar on the device (csrc/geometry.hip)
+ *   sample_fmap, sample_depth                                 core/geometry/depth.py:9-25
+ *   project (ccth None or given)                              core/geometry/depth.py:37-69
+ *   dense_warp_consistency                                    core/geometry/depth.py:72-89
+ *   sym_epipolar_distance_all                                 core/geometry/epipolar.py:59-72
+ *   Pose.transform, pinhole cam2image / image2cam             core/geometry/wrappers.py:186-193, :337-398
+ * The sampler and the projection are those of einx_gt_project (csrc/gt_project.h): the same bits on the same inputs.  All tensors
+ * float32 unless stated, K [B,9], T [B,16]; T is "this view -> the other" and may be NULL when T_other (the other view -> this one)
+ * is given: the kernel then uses (R^T, -R^T t) of it.  Nothing synchronises or allocates, no workspace; every call can be captured;
+ * two runs give the same bits.
+ *
+ * The cycle check (cc != 0; depth.py:62-69): the other view's depth map is sampled at the projection (or the caller supplies those
+ * samples: dj_in / validj_in), the projection is taken back through the inverse of the FORWARD motion (T_itoj.inv(), not the
+ * caller's pose of the other direction), and a point stays visible when that sample is valid, the way back ends in front of and
+ * inside this view's camera (0 <= . <= 2c - 1) and dx^2 + dy^2 < cc_bound, strictly (NaN fails).  cc_bound is compared with the
+ * SQUARED distance as given: the reference compares squared pixels with its unsquared ccth, so core.geometry.depth.project passes
+ * ccth through, and callers that think in pixels pass th^2.  cc == 0 is "ccth=None": no magic value of the bound means "off".
+ *
+ * einx_geom_project: p->sides = 1 (one direction) or 2 (both, one launch).  Per side: kp [B,cap,cols>=2] ((y,x,..) when p->kp_yx),
+ * count int32 [B] or NULL (= cap; rows at or beyond a count get zeros); the points' depths either given (d_in [B,cap] with valid_in
+ * uint8) or sampled from this view's map depth [B,H,W]; with cc the other view's map depth_other [B,Ho,Wo] or dj_in / validj_in
+ * [B,cap].  Outputs proj [B,cap,2] (x, y; NaN where the depth is) and visible [B,cap] uint8; d_out / valid_out [B,cap] (the depths
+ * and validity used) may be NULL.
+ * einx_geom_dense_warp: the keypoint of pixel i = y W + x of depth [B,H,W] is its centre (x + 0.5, y + 0.5), its depth the pixel's
+ * own value (not a bilinear sample), valid = d > 0.  Outputs warp [B,H,W,2] (8-byte aligned) and visible [B,H,W] uint8 per side, and
+ * counts int32 [B,sides,2] = #valid, #visible pixels: integer sums.
+ * einx_geom_sample: fmap [B,C,H,W] at pts [B,N,2] (x, y) -> out [B,N,C]: einx_gt_project's depth sampler per channel (bilinear with
+ * zero padding at x - 0.5; a hole under a tap of non-zero weight sends the sample to the nearest pixel, half to even; 0 outside the
+ * map).  A hole is a NaN, or with depth_rule a value <= 0 or NaN (sample_depth on its NaN-masked map; a hole at the nearest pixel
+ * then gives NaN); valid [B,N] uint8 = not NaN and > 0 may be given with depth_rule and C == 1, else NULL.
+ * einx_epipolar_all: p0 [B,N,cols0], p1 [B,M,cols1] with 2 or 3 columns (2: w = 1), E [B,9] -> out [B,N,M].  Row line l = E p0
+ * (l_i = (E[i,0] x + E[i,1] y) + E[i,2] w) and n0 = sqrt((l_0^2 + l_1^2) + eps), column c_k = (E[0,k] x' + E[1,k] y') + E[2,k] w' and
+ * n1 = sqrt((c_0^2 + c_1^2) + eps), each once per point; entry s = |(x' l_0 + y' l_1) + w' l_2|, out = (s / n0 + s / n1) * 0.5.
+ * N <= 2^21, M <= 2^24; N == 0 or M == 0 writes nothing.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_geom_side {
+  const float* kp;           /* [B,cap,cols] */
+  const int32_t* count;      /* [B] or NULL */
+  const float* depth;        /* [B,H,W] this view's depth map, or NULL with d_in / valid_in */
+  const float* d_in;         /* [B,cap] */
+  const uint8_t* valid_in;   /* [B,cap] */
+  const float* depth_other;  /* [B,Ho,Wo] the other view's depth map (cc), or NULL with dj_in / validj_in */
+  const float* dj_in;        /* [B,cap] the other view's depth under each projection */
+  const uint8_t* validj_in;  /* [B,cap] */
+  const float *K, *K_other;  /* [B,9] */
+  const float *T, *T_other;  /* [B,16]; one may be NULL */
+  float* d_out;              /* [B,cap] or NULL */
+  uint8_t* valid_out;        /* [B,cap] or NULL */
+  float* proj;               /* [B,cap,2] */
+  uint8_t* visible;          /* [B,cap] */
+  int32_t cap, cols, H, W, Ho, Wo;
+} einx_geom_side;
+typedef struct einx_geom_project_params {
+  size_t struct_size; /* sizeof(einx_geom_project_params) (checked) */
+  int32_t B, sides;   /* sides: 1 or 2 */
+  int32_t kp_yx;      /* 1: keypoints are (y,x,..) */
+  int32_t cc;         /* 0: no cycle check (ccth=None) */
+  float cc_bound;     /* compared with the squared cycle distance, strictly */
+  einx_geom_side side[2];
+} einx_geom_project_params;
+int einx_geom_project(const einx_geom_project_params* p, void* stream);
+typedef struct einx_geom_dense_side {
+  const float* depth;        /* [B,H,W] */
+  const float* depth_other;  /* [B,Ho,Wo] (cc) */
+  const float *K, *K_other;  /* [B,9] */
+  const float *T, *T_other;  /* [B,16]; one may be NULL */
+  float* warp;               /* [B,H,W,2] */
+  uint8_t* visible;          /* [B,H,W] */
+  int32_t H, W, Ho, Wo;      /* H W <= 2^24 */
+} einx_geom_dense_side;
+typedef struct einx_geom_dense_params {
+  size_t struct_size; /* sizeof(einx_geom_dense_params) (checked) */
+  int32_t B, sides;
+  int32_t cc;
+  float cc_bound;
+  int32_t* counts;    /* [B,sides,2] */
+  einx_geom_dense_side side[2];
+} einx_geom_dense_params;
+int einx_geom_dense_warp(const einx_geom_dense_params* p, void* stream);
+int einx_geom_sample(const float* fmap, int B, int C, int H, int W, const float* pts, int N, int depth_rule, float* out, uint8_t* valid,
+                     void* stream);
+int einx_epipolar_all(const float* p0, int cols0, const float* p1, int cols1, const float* E, int B, int N, int M, float eps, float* out,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Forward values of the extractor losses (csrc/loss.hip): validation under no_grad, no autograd.
  *   ScoreLoss, LogitsLoss, DescriptorsLoss (mse / mae / cosine_similarity), FeatureLoss      core/loss/extractor_loss.py:6-383
  * Every call writes out [B,2] float64 = one (sum, count) pair per image: the reference's (pooled) loss value is
