@@ -75,6 +75,11 @@ class HomographyParams(ctypes.Structure):
                [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("he_thr", c_float * 4), ("seed", ctypes.c_uint64)]
 
 
+class AbsPoseParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap", "cols", "kp_yx", "H", "W", "max_iters", "refine")] + \
+               [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("seed", ctypes.c_uint64)]
+
+
 class GtMatchesParams(ctypes.Structure):
     _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap0", "cap1", "cols0", "cols1", "kp_yx", "H0", "W0", "H1", "W1",
                                                                             "homography")] + [("pos_sq", c_float), ("neg_sq", c_float)]
@@ -242,6 +247,9 @@ SIGNATURES = {
     "einx_homography_ws_bytes": (c_size_t, [ctypes.POINTER(HomographyParams)]),
     "einx_homography": (c_int, [ctypes.POINTER(HomographyParams)] + [c_void_p] * 11),
     "einx_homography_dlt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_absolute_pose_ws_bytes": (c_size_t, [ctypes.POINTER(AbsPoseParams)]),
+    "einx_absolute_pose": (c_int, [ctypes.POINTER(AbsPoseParams)] + [c_void_p] * 16),
+    "einx_p3p": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "einx_gt_matches_ws_bytes": (c_size_t, [ctypes.POINTER(GtMatchesParams)]),
     "einx_gt_project": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 23),
     "einx_gt_warp": (c_int, [ctypes.POINTER(GtMatchesParams)] + [c_void_p] * 8),

@@ -1,0 +1,1 @@
+from .matching_metrics import AbsolutePoseEstimation  # noqa: F401

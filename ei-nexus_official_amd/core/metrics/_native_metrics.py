@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import GeomDenseParams, GeomProjectParams, GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, check
+from ..._lib import AbsPoseParams, GeomDenseParams, GeomProjectParams, GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -256,6 +256,66 @@ def homography_dlt(x1, x2):
     ok = torch.empty((n,), dtype=torch.int32, device=x1.device)
     check(N.lib().einx_homography_dlt(N._ptr(x1), N._ptr(x2), n, npts, N._ptr(H), N._ptr(ok), N._stream(x1)), "einx_homography_dlt")
     return H, ok
+
+
+ABS_POSE_STATUS = {-1: "few", -2: "none"}  # einx.h: >= 0: 4 * iteration + solution of the chosen model, negative: why there is no pose
+ABS_POSE_ROWS = ("R_errs", "t_errs", "t_angles", "inliers", "usable")
+
+
+@on_input_device
+def absolute_pose(mk0, mk1, nmatch, K0, K1, depth0=None, d0=None, valid0=None, T_0to1=None, thresh=8.0, conf=0.99, ordering="yx",
+                  max_iters=100, seed=POSE_SEED, refine=True):
+    """Metric pose of view 1 in view 0's frame from matches and view 0's depth for a batch (csrc/abs_pose.hip, DESIGN.md 8u: P3P
+    RANSAC, an LM refit on the inliers, the pose errors), no host sync.  mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the
+    device; the depth of view 0 as a map depth0 [B,H,W] (sampled at the keypoints like gt_project does) or per match as d0 [B,cap]
+    with valid0 [B,cap]: exactly one of the two; K0 / K1 [B,3,3]; T_0to1 [B,4,4] or None.  The defaults are solvePnPRansac's.
+    Returns device tensors (R [B,3,3] f64, t [B,3] f64, mask [B,cap] bool, status [B] int32 (ABS_POSE_STATUS), rows [B,5] f64 =
+    R_err (degrees), |t - t_gt|, angle of t against t_gt (degrees), inliers / usable, usable / matches)."""
+    if (depth0 is None) == (d0 is None) or (d0 is None) != (valid0 is None):
+        raise ValueError("einx: absolute_pose takes view 0's depth either as a map (depth0) or per match (d0 with valid0), not both and not neither")
+    B, cap, cols = mk0.shape
+    dev = mk0.device
+    if cols not in (2, 3):
+        raise ValueError("einx: absolute_pose: matched rows have 2 or 3 columns")
+    K0, K1 = _f32c(K0, dev, (B, 9)), _f32c(K1, dev, (B, 9))
+    T = None if T_0to1 is None else T_0to1.to(dev, torch.float64).reshape(B, 16).contiguous()
+    H = W = 0
+    dm = dk = vk = None
+    if depth0 is not None:
+        dm = depth0.to(dev, torch.float32).reshape(B, depth0.shape[-2], depth0.shape[-1]).contiguous()
+        H, W = dm.shape[1], dm.shape[2]
+    else:
+        dk = d0.to(dev, torch.float32).reshape(B, cap).contiguous()
+        vk = valid0.to(dev, torch.uint8).reshape(B, cap).contiguous()
+    L = N.lib()
+    p, ws, mask, status, rows = _ransac_call(AbsPoseParams, L.einx_absolute_pose_ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering, max_iters,
+                                             seed, 5, H=H, W=W, refine=int(bool(refine)))
+    R = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
+    t = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    P = N._ptr
+    check(L.einx_absolute_pose(ctypes.byref(p), P(mk0), P(mk1), P(nmatch), P(dm), P(dk), P(vk), P(K0), P(K1), P(T), P(ws), P(R), P(t), P(mask),
+                               P(status), P(rows), N._stream(mk0)), "einx_absolute_pose")
+    return R, t, mask.bool(), status, rows
+
+
+@on_input_device
+def batch_absolute_pose(mr, K0, K1, depth0=None, d0=None, valid0=None, T_0to1=None, thresh=8.0, conf=0.99, ordering="yx"):
+    """absolute_pose of an EIM match result (MatchResult: mk0 / mk1 / nmatch), no host sync"""
+    return absolute_pose(mr.mk0, mr.mk1, mr.nmatch, K0, K1, depth0, d0, valid0, T_0to1, thresh, conf, ordering)
+
+
+@on_input_device
+def p3p(X, f):
+    """the minimal solver alone (test aid): X [n,3,3] points, f [n,3,3] unit bearings, float64 -> (R [n,4,3,3], t [n,4,3],
+    n_solutions [n] int32)"""
+    n = X.shape[0]
+    X = X.to(torch.float64).contiguous()
+    f = f.to(X.device, torch.float64).contiguous()
+    R = torch.zeros((n, 4, 3, 3), dtype=torch.float64, device=X.device)
+    t = torch.zeros((n, 4, 3), dtype=torch.float64, device=X.device)
+    ns = torch.empty((n,), dtype=torch.int32, device=X.device)
+    check(N.lib().einx_p3p(N._ptr(X), N._ptr(f), n, N._ptr(R), N._ptr(t), N._ptr(ns), N._stream(X)), "einx_p3p")
+    return R, t, ns
 
 
 # ---- ground-truth matches and matcher precision / recall (csrc/gt_matches.hip, DESIGN.md 8e) ------------------------------------

@@ -2,11 +2,12 @@
 (core/metrics/matching_metrics.py:30-51, :84-156), computed by csrc/metrics.hip.  RelativePoseEstimation
 (:347-559) runs its RANSAC essential matrix and recoverPose on the device (csrc/pose.hip, DESIGN.md 8b: the
 written algorithm, not bit parity with cv2).  HomographyEstimation (:188-345) runs its RANSAC homography, the refit and
-the polish on the device as well (csrc/homography.hip, DESIGN.md 8c, on the same terms)."""
+the polish on the device as well (csrc/homography.hip, DESIGN.md 8c, on the same terms).  AbsolutePoseEstimation has no
+counterpart in the reference: the metric pose from matches and view 0's depth (csrc/abs_pose.hip)."""
 import numpy as np
 import torch
 
-from ._native_metrics import HOMOGRAPHY_STATUS, POSE_STATUS, homography, single_pair, relative_pose
+from ._native_metrics import ABS_POSE_ROWS, HOMOGRAPHY_STATUS, POSE_STATUS, absolute_pose, homography, single_pair, relative_pose
 
 
 class MatchingRatio:
@@ -255,3 +256,76 @@ class RelativePoseEstimation:
         for k in self.pose_thresh:
             out_dict[f"{self.metric_name}@{k}_auc"] = auc[f"{k}"]
         return out_dict
+
+
+class AbsolutePoseEstimation:
+    """The metric pose of view 1 in view 0's frame from the matches and view 0's depth map (csrc/abs_pose.hip, DESIGN.md 8u: P3P
+    RANSAC and an LM refit, a written algorithm and not OpenCV's solvePnPRansac), shaped like RelativePoseEstimation.  `thresholds`
+    is a sequence of (degrees, distance) pairs: a pair of views passes one when its rotation error is within the degrees AND
+    |t - t_gt| within the distance (the depth map's unit)."""
+
+    def __init__(self, name, thresholds, ransac_thresh=8.0, ransac_conf=0.99, ordering="yx") -> None:
+        assert ordering in {"xy", "yx"}
+        self.metric_name = name
+        self.to_device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+        self.thresholds = tuple((float(a), float(d)) for a, d in thresholds)
+        self.ransac_thresh = ransac_thresh
+        self.ransac_conf = ransac_conf
+        self.ordering = ordering
+        self.rows = []
+
+    @staticmethod
+    def threshold_key(name, deg, dist):
+        return f"{name}@{deg:g}deg_{dist:g}_ratio"
+
+    @staticmethod
+    def columns(rows, thresholds, name):
+        """per-pair rows [P,5] (R_err, |t - t_gt|, t angle, inlier ratio, usable ratio; inf errors for a pair without a pose) ->
+        {key: per-pair values}; a pair without a pose counts 0 under every threshold"""
+        r = np.asarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64).reshape(-1, 5)
+        cols = {f"{name}_{k}": r[:, i] for i, k in enumerate(ABS_POSE_ROWS)}
+        for deg, dist in thresholds:
+            with np.errstate(invalid="ignore"):
+                cols[AbsolutePoseEstimation.threshold_key(name, deg, dist)] = ((r[:, 0] <= deg) & (r[:, 1] <= dist)).astype(np.float64)
+        return cols
+
+    @staticmethod
+    def summary(rows, thresholds, name="APE"):
+        """the mean of every column over its finite values (NaN for a column without one)"""
+        out = {}
+        for k, v in AbsolutePoseEstimation.columns(rows, thresholds, name).items():
+            v = v[np.isfinite(v)]
+            out[k] = float(np.mean(v)) if len(v) else float("nan")
+        return out
+
+    @torch.no_grad()
+    def estimate_rows(self, matched_keypoints1, matched_keypoints2, K0, K1, depth0, T_0to1):
+        """the [5] float64 row of one pair (numpy)"""
+        assert len(matched_keypoints1) == len(matched_keypoints2)
+        assert matched_keypoints1.shape[1] in (2, 3)
+        if len(matched_keypoints1) == 0:
+            return np.array([np.inf, np.inf, np.inf, 0.0, np.nan])
+        mk0, mk1, nm = _batch_of_one(matched_keypoints1, matched_keypoints2, self.to_device)
+        dev = mk0.device
+        one = lambda v: torch.as_tensor(v).to(dev)[None]  # noqa: E731
+        rows = absolute_pose(mk0, mk1, nm, one(K0), one(K1), depth0=one(depth0), T_0to1=one(T_0to1), thresh=self.ransac_thresh,
+                             conf=self.ransac_conf, ordering=self.ordering)[4]
+        return rows[0].cpu().numpy()
+
+    @torch.no_grad()
+    def update_one(self, matched_keypoints1, matched_keypoints2, K0, K1, depth0, T_0to1):
+        row = self.estimate_rows(matched_keypoints1, matched_keypoints2, K0, K1, depth0, T_0to1)
+        self.rows.append(row)
+        return {k: v[0] for k, v in self.columns(row[None], self.thresholds, self.metric_name).items()}
+
+    @torch.no_grad()
+    def update_batch(self, matched_keypoints1, matched_keypoints2, K0, K1, depth0, T_0to1):
+        assert len(matched_keypoints1) == len(matched_keypoints2) == len(K0) == len(K1) == len(depth0) == len(T_0to1)
+        self.rows = []
+        for i in range(len(matched_keypoints1)):
+            self.update_one(matched_keypoints1[i], matched_keypoints2[i], K0[i], K1[i], depth0[i], T_0to1[i])
+        return self.compute()
+
+    def compute(self):
+        """the keys over every pair seen since construction (or the last update_batch)"""
+        return self.summary(np.stack(self.rows) if self.rows else np.zeros((0, 5)), self.thresholds, self.metric_name)

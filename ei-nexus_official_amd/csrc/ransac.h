@@ -1,5 +1,5 @@
-// The RANSAC skeleton shared by the estimators (pose.hip: DESIGN.md 8b, homography.hip: 8c): the counter-based generator and its
-// distinct-index draws, the selection scan with OpenCV's shrinking iteration bound and the state it keeps between rounds, the
+// The RANSAC skeleton shared by the estimators (pose.hip: DESIGN.md 8b, homography.hip: 8c, abs_pose.hip: 8u): the counter-based
+// generator and its distinct-index draws, the selection scan with OpenCV's shrinking iteration bound and the state it keeps between rounds, the
 // host's round schedule, and the cooperative Gauss-Jordan elimination.  An estimator adds its minimal solver, its error function,
 // its inlier count, its epilogue and the carve of its workspace (WsCarver: einx_common.h).
 #pragma once

@@ -31,8 +31,8 @@ import numpy as np
 import torch
 
 from . import _native as native
-from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_gt_matches, batch_homography, batch_metrics, batch_metrics_pose,
-                                            batch_relative_pose, gt_matches, match_pr, metric_names, pose_metric_names)
+from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_absolute_pose, batch_gt_matches, batch_homography, batch_metrics,
+                                            batch_metrics_pose, batch_relative_pose, gt_matches, match_pr, metric_names, pose_metric_names)
 from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
@@ -357,6 +357,13 @@ def rpe_summary(rows, pose_thresh=(5, 10, 20), name="RPE"):
     return _summary(cols, r[:, 2], pose_thresh, name)
 
 
+def ape_summary(rows, thresholds, name="APE"):
+    """the APE keys from per-pair rows of batch_absolute_pose (R_err, |t - t_gt|, t angle, inlier ratio, usable ratio; inf errors
+    for a pair without a pose, which counts 0 under every threshold): the mean of each key over its finite values"""
+    from .core.metrics.matching_metrics import AbsolutePoseEstimation
+    return AbsolutePoseEstimation.summary(rows, thresholds, name)
+
+
 MATCHER_LOSS_NAMES = ("matcher_loss", "matcher_nll_pos", "matcher_nll_neg", "matcher_row_norm")
 
 
@@ -445,6 +452,13 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
       projection, the point is taken back, and it stays visible only when it returns within `label_cc_th` pixels of where it
       started (the reference's project(ccth=), here with label_cc_th^2 as the bound on the squared distance).  A hidden keypoint
       can then neither become a positive nor block one; match_*, average_precision and matcher_loss follow from those labels.
+    * `abs_pose_thresh=((degrees, distance), ...)` (None by default: nothing is launched and result() is unchanged).  The relative
+      pose above is a rotation and a translation direction.  With `abs_pose_thresh`, a batch that carries pose and depth also
+      estimates the metric pose of the image camera in the event camera's frame from the matches and view 0's depth map
+      (batch_absolute_pose: P3P RANSAC and an LM refit; `abs_pose_ransac_thresh` pixels, `abs_pose_conf`), with no
+      host synchronisation; result() gains APE_R_errs (degrees), APE_t_errs (the depth map's unit), APE_t_angles, APE_inliers,
+      APE_usable and APE@{deg}deg_{dist}_ratio per threshold (both errors within it; a pair without a pose counts 0).  A batch
+      with pose but no depth contributes no row.
     * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
       RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
       all-gathered before the AUC.  Once depth was given: the four matcher_metrics means over the pairs that have keypoints.
@@ -455,7 +469,8 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
 
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
                  ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None,
-                 matcher_loss=False, reproj_thr=None, epi_thr=None, occlusion_th=None, label_cc_th=None):
+                 matcher_loss=False, reproj_thr=None, epi_thr=None, occlusion_th=None, label_cc_th=None, abs_pose_thresh=None,
+                 abs_pose_ransac_thresh=8.0, abs_pose_conf=0.99):
         if label_cc_th is not None and not float(label_cc_th) > 0:
             raise ValueError("einx: label_cc_th is a distance in pixels (> 0), or None for labels without the occlusion check")
         self.label_cc_th = None if label_cc_th is None else float(label_cc_th)
@@ -472,6 +487,9 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
         self.pose_thresh = tuple(pose_thresh)
         self.ransac_thresh, self.ransac_conf = float(ransac_thresh), float(ransac_conf)
         self._pose_rows = []
+        self.abs_pose_thresh = None if abs_pose_thresh is None else tuple((float(a), float(d)) for a, d in abs_pose_thresh)
+        self.abs_pose_ransac_thresh, self.abs_pose_conf = float(abs_pose_ransac_thresh), float(abs_pose_conf)
+        self._abs_pose_rows = []
         self._init_labels(model, matcher_loss, 3, 5)  # gt_matches_from_pose_depth's defaults, as val_matcher.py calls it
         # the depth / motion form of the metrics: one row layout for every batch, NaN where a batch had no depth
         self.reproj_thr = None if reproj_thr is None else tuple(reproj_thr)
@@ -500,6 +518,10 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
             K0, K1, T = batch.pose
             self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
                                                        ordering=ef._batched.ordering)[4])
+            if self.abs_pose_thresh is not None and batch.depth is not None:
+                self._abs_pose_rows.append(batch_absolute_pose(self.model._last_match, K0, K1, depth0=batch.depth[0], T_0to1=T,
+                                                               thresh=self.abs_pose_ransac_thresh, conf=self.abs_pose_conf,
+                                                               ordering=ef._batched.ordering)[4])
             depth = batch.depth if self.reproj_thr is not None else None
             if depth is not None or self.epi_thr is not None:  # one call for the depth form and the EPI columns
                 rows = batch_metrics_pose(ef._batched, imf._batched, self.model._last_match, K0, K1, T, depth, None, self.reproj_thr or (),
@@ -510,6 +532,8 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
     def result(self):
         out = super().result()
         out.update(_gathered_summary(self._pose_rows, 4, rpe_summary, self.pose_thresh))
+        if self.abs_pose_thresh is not None:
+            out.update(_gathered_summary(self._abs_pose_rows, 5, ape_summary, self.abs_pose_thresh))
         self._label_results(out)
         if self.reproj_thr is not None or self.epi_thr is not None:
             s, c = self._dt_mean.reduced(self.sums.device)

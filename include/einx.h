@@ -969,6 +969,42 @@ int einx_homography(const einx_homography_params* p, const float* mk0, const flo
 int einx_homography_dlt(const double* x1, const double* x2, int n_problems, int n_points, double* H_out, int32_t* ok, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Absolute (metric) pose from matches and the depth of view 0 (csrc/abs_pose.hip)
+ * The reference estimates no metric pose; this is a written algorithm (perspective-three-point RANSAC, a Levenberg-Marquardt
+ * refit on the inliers), not parity with OpenCV's solvePnPRansac.
+ * B pairs of matched keypoints mk0 / mk1 [B,cap,cols] float32 + nmatch int32 [B] (einx_gather_matches' layout).  The depth of a
+ * match of view 0 is sampled from depth0 [B,H,W] float32 with einx_gt_project's sampler, or given as d_in [B,cap] float32 +
+ * valid_in [B,cap] uint8: exactly one of the two forms.  K0 / K1 [B,9] float32, T_0to1 [B,16] float64 or NULL.  A match is usable
+ * when its depth is valid; everything runs over the nu usable matches of a pair.  Outputs:
+ *   R_out [B,9], t_out [B,3] float64: x1 = R x0 + t in the depth map's unit (zeros without a pose),
+ *   mask_out [B,cap] uint8: the RANSAC model's inliers at their match indices (not re-evaluated after the refit),
+ *   status [B] int32: >= 0: 4 * iteration + solution of the chosen model; -1 fewer than 4 usable matches, -2 no model,
+ *   rows_out [B,5] float64 or NULL: rotation error (degrees), |t - t_gt|, the angle between t and t_gt (degrees, folded to
+ *     [0, 90], NaN for a zero t_gt), inliers / nu, nu / min(nmatch, cap) (NaN without matches) -- inf, inf, inf, 0 without a pose;
+ *     the three errors are NaN when T_0to1 is NULL.
+ * Nothing synchronises or allocates; the call can be captured.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_abs_pose_params {
+  size_t struct_size; /* sizeof(einx_abs_pose_params) (checked) */
+  int32_t B, cap, cols;
+  int32_t kp_yx;      /* 1: keypoints are (y,x,..) */
+  int32_t H, W;       /* size of depth0 (unused with d_in / valid_in) */
+  int32_t max_iters;  /* RANSAC iterations (100: solvePnPRansac's iterationsCount) */
+  int32_t refine;     /* 1: the Levenberg-Marquardt refit on the inliers; 0: the RANSAC model itself */
+  double thresh;      /* reprojection threshold in pixels of view 1 (8.0) */
+  double conf;        /* RANSAC confidence (0.99) */
+  uint64_t seed;      /* counter-based generator key */
+} einx_abs_pose_params;
+size_t einx_absolute_pose_ws_bytes(const einx_abs_pose_params* p); /* 0 on a bad shape */
+int einx_absolute_pose(const einx_abs_pose_params* p, const float* mk0, const float* mk1, const int32_t* nmatch, const float* depth0,
+                       const float* d_in, const uint8_t* valid_in, const float* K0, const float* K1, const double* T_0to1, void* ws,
+                       double* R_out, double* t_out, uint8_t* mask_out, int32_t* status, double* rows_out, void* stream);
+/* The minimal solver alone (test aid, like einx_essential_5pt): X [n,3,3] float64 points, f [n,3,3] float64 unit bearings;
+ * R_out [n,4,9] / t_out [n,4,3] float64 get every pose with s_i f_i = R X_i + t, s_i > 0, ordered by ascending s3 / s1 (zeros past
+ * the count), n_solutions [n] int32 their count (0 for a degenerate sample). */
+int einx_p3p(const double* X, const double* f, int n, double* R_out, double* t_out, int32_t* n_solutions, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Ground-truth matches and the matcher's precision / recall (csrc/gt_matches.hip)
  *   gt_matches_from_pose_depth / gt_matches_from_homography   core/geometry/gt_generation.py:15-224
  *   sample_depth, project (ccth=None)                         core/geometry/depth.py:9-60

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Device time of a batched RANSAC estimator, the relative pose (csrc/pose.hip) or the homography (csrc/homography.hip): B pairs of
-cap matches with realistic ragged counts (pose: MVSEC-like scenes, homography: 346 x 260 frames; 0.5 px noise, 30 % outliers),
-timed with device events around the whole launch sequence.  Only the public relative_pose / homography functions are used, so
-EINX_LIB=ab_libs/libeinx_X.so times an A/B build.
+"""Device time of a batched RANSAC estimator, the relative pose (csrc/pose.hip), the homography (csrc/homography.hip) or the absolute
+pose (csrc/abs_pose.hip): B pairs of cap matches with realistic ragged counts (pose and abs_pose: MVSEC-like scenes, abs_pose with
+exact per-match depths; homography: 346 x 260 frames; 0.5 px noise, 30 % outliers), timed with device events around the whole
+launch sequence.  Only the public relative_pose / homography / absolute_pose functions are used, so EINX_LIB=ab_libs/libeinx_X.so
+times an A/B build.
 
-    python tools/ransac_bench.py {pose,homography} [--B 32] [--cap 1024] [--iters 20] [--outliers 0.3]
+    python tools/ransac_bench.py {pose,homography,abs_pose} [--B 32] [--cap 1024] [--iters 20] [--outliers 0.3]
 """
 import argparse
 import importlib
@@ -42,9 +43,29 @@ def homography_workload(nm, scenes):
     return nm.homography, (np.array([Hm.IMG_SHAPE] * len(Ht), np.int32), Ht), report
 
 
+def abs_pose_workload(nm, scenes, cap):
+    import abs_pose_f64 as A
+
+    def scene(rng, n, noise, outliers):
+        s = A.scene(rng, n, noise=noise, outliers=outliers)
+        d = np.zeros(cap, np.float32)
+        d[:n] = s["d0"]
+        return s["kp0"], s["kp1"], s["K0"], s["K1"], s["T"], d
+    K0, K1, T, d0 = (np.stack(v) for v in zip(*(s[2:] for s in scenes(scene))))
+
+    def run(mk0, mk1, n, K0, K1, d0, valid0, T):
+        return nm.absolute_pose(mk0, mk1, n, K0, K1, d0=d0, valid0=valid0, T_0to1=T)
+
+    def report(out):
+        status, rows = out[3].cpu().numpy(), out[4].cpu().numpy()
+        return {"posed": int((status >= 0).sum()), "max_chosen_iteration": int(status.max()) // 4, "median_R_err_deg": float(np.median(rows[:, 0])),
+                "median_t_err": float(np.median(rows[:, 1]))}
+    return run, (K0, K1, d0, np.ones_like(d0, dtype=np.uint8), T), report
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("estimator", choices=("pose", "homography"))
+    ap.add_argument("estimator", choices=("pose", "homography", "abs_pose"))
     ap.add_argument("--B", type=int, default=32)
     ap.add_argument("--cap", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=20)
@@ -65,7 +86,10 @@ def main():
             yield s
 
     t = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to("cuda:0")  # noqa: E731
-    run, extra, report = (pose_workload if a.estimator == "pose" else homography_workload)(nm, scenes)
+    if a.estimator == "abs_pose":
+        run, extra, report = abs_pose_workload(nm, scenes, a.cap)
+    else:
+        run, extra, report = (pose_workload if a.estimator == "pose" else homography_workload)(nm, scenes)
     args = tuple(t(x) for x in (mk0, mk1, cnt) + extra)
     for _ in range(3):
         run(*args)
