@@ -153,6 +153,7 @@ class BatchedFeats:
         self._prepared = None
         self._full_lists = None
         self._ns = None
+        self.subpixel = False  # the keypoints of this result are refined; a re-detection refines again
 
     # ------------------------------------------------------------------ device handles
     @property
@@ -348,7 +349,18 @@ class ExtractorEngine:
             self._shapes[(H, W)] = s
         return s
 
-    def _run_handle(self, h, sh, x, mask, pads, scale, dense, nms_iters, defer_dense=False):
+    def refine(self, bf):
+        """Sub-pixel keypoints (opt-in): ONE launch on the current stream that rewrites the positions of bf.det from
+        the score map the detection ran on and, for cell-8 networks, resamples the keypoints' descriptor rows at the refined
+        positions.  Cell-1 descriptors stay the gather at the integer peak (the reference floors the position)."""
+        det = bf.det
+        if self.cell == 8:
+            N.refine_keypoints(bf.score, det.indices, det.counts, det.positions, bf.pads, self.ordering, raw=bf.raw, raw_cl=bf.raw_cl,
+                               sparse_desc=bf.sparse_desc, scale=bf.scale)
+        else:
+            N.refine_keypoints(bf.score, det.indices, det.counts, det.positions, bf.pads, self.ordering)
+
+    def _run_handle(self, h, sh, x, mask, pads, scale, dense, nms_iters, defer_dense=False, subpixel=False):
         L = N.lib()
         dev = x.device
         B, _, H, W = x.shape
@@ -386,6 +398,9 @@ class ExtractorEngine:
             det.stale = wt.stale
         _lib.check(L.einx_extract_pad(h, P(x), P(m8), mpad, B, H, W, int(nms_iters), P(ws), nws, ctypes.byref(out), ww, N._stream(x)),
                    "einx_extract_pad")
+        if subpixel:
+            bf.subpixel = True
+            self.refine(bf)
         if dense and not defer_dense:
             bf.run_dense()
         return bf
@@ -404,11 +419,15 @@ class ExtractorEngine:
             det.positions = det.positions[:, :cmax].contiguous()
             det.indices = det.indices[:, :cmax].contiguous()
             det.cap = cmax
+        bf.det = det
+        if bf.subpixel and self.cell != 8:  # positions only, in the map's own frame: before mapping_positions shifts them
+            self.refine(bf)
         if self.valid_crop:  # mapping_positions: both coordinates + 9 (the third column is the score); indices stay map-relative
             det.positions[:, :, :2] += float(self.valid_crop)
-        bf.det = det
         bf.sparse_desc = N.desc_sample(bf.raw, det.indices, det.counts, bf.padded, bilinear=(self.cell == 8), scale=bf.scale,
                                        raw_cl=bf.raw_cl)
+        if bf.subpixel and self.cell == 8:
+            self.refine(bf)
         return bf
 
     def grow_nms_iters(self):
@@ -427,9 +446,11 @@ class ExtractorEngine:
                 self.nms_iters = max(self.nms_base, self.nms_iters // 2)
                 self._calm = 0
 
-    def run(self, x, mask, *, scale, dilate_mask, dense=False, nms_iters=None, input_div=0.0, defer_dense=False, half=False):
+    def run(self, x, mask, *, scale, dilate_mask, dense=False, nms_iters=None, input_div=0.0, defer_dense=False, half=False, subpixel=False):
         """One einx_extract call (handle-level ABI) enqueues the whole network; the op-by-op path below it serves the
-        unbounded-capacity configurations (no top-k: the descriptor buffer is sized from the real counts)."""
+        unbounded-capacity configurations (no top-k: the descriptor buffer is sized from the real counts).
+        subpixel: one refine_keypoints launch on the same stream directly after the detection (and after every re-detection of
+        the returned result); False enqueues nothing new."""
         if x.dim() != 4:
             raise ValueError(f"Expected 4D tensor, got {x.dim()}D tensor instead.")
         if x.dtype != torch.float32:
@@ -460,7 +481,7 @@ class ExtractorEngine:
             h = self.handle(scale, dilate_mask, input_div, half)
             sh = self.shapes(h, H, W)
             if sh.cap <= 8192 and self.use_handle:
-                return self._run_handle(h, sh, x, mask, pads, scale, dense, nms_iters or self.nms_iters, defer_dense=defer_dense)
+                return self._run_handle(h, sh, x, mask, pads, scale, dense, nms_iters or self.nms_iters, defer_dense=defer_dense, subpixel=subpixel)
         if input_div:
             N.div_inplace(x, input_div)
         t = x
@@ -494,6 +515,7 @@ class ExtractorEngine:
             bf.coarse, bf.raw_cl = N.normalize_map(raw, scale, want_cl=True)  # + channels-last raw copy for the sparse sampler
         prob, score = N.score_map(logits, mask, pads, dilate=dilate_mask, border=self.border)
         bf.feats, bf.logits, bf.raw, bf.prob, bf.score = feats, logits, raw, prob, score
+        bf.subpixel = bool(subpixel)
         self.redetect(bf, nms_iters)
         wt = getattr(self, "watch", None)
         if wt is not None and wt.n:  # op-level path (rare configurations): the weight watch as its own launch, same word

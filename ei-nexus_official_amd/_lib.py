@@ -190,6 +190,10 @@ SIGNATURES = {
                             c_void_p, c_void_p]),
     "einx_desc_sample": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float,
                                  c_void_p, c_void_p]),
+    "einx_desc_sample_pos": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float,
+                                     c_void_p, c_void_p]),
+    "einx_refine_keypoints": (c_int, [c_void_p] + [c_int] * 8 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                      c_float, c_void_p, c_void_p]),
     "einx_normalize_map": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "einx_upsample_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "einx_upsample_normalize": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,

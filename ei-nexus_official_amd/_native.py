@@ -326,6 +326,57 @@ def desc_sample(raw, indices, counts, padded_size, bilinear, scale, raw_cl=None)
     return out
 
 
+SUBPIXEL_DMAX = 0.5 - 2.0 ** -10  # largest sub-pixel offset per axis (csrc/subpixel.hip)
+
+
+def desc_sample_pos(raw, positions, counts, padded_size, scale, ordering="yx", raw_cl=None):
+    """raw [B,D,hc,wc] sampled bilinearly (zero padding, align_corners=False) at the float positions [B,cap,>=2] of the padded
+    frame, then normalised: the reference's sparsify_low_resolution_descriptors for ANY position -> [B,cap,D].  raw_cl: see
+    desc_sample."""
+    _dev_check(raw, raw_cl, positions)
+    _dev_check(counts, dt=I32)
+    B, D, hc, wc = raw.shape
+    if positions.dim() != 3 or positions.shape[0] != B or positions.shape[2] < 2 or counts.numel() != B:
+        raise ValueError(f"einx: positions must be [B, cap, >= 2] and counts [B] for B = {B}, got {tuple(positions.shape)} and {tuple(counts.shape)}")
+    cap = positions.shape[1]
+    out = torch.empty((B, cap, D), dtype=F32, device=raw.device)
+    use_cl = raw_cl is not None
+    check(lib().einx_desc_sample_pos(_ptr(raw_cl if use_cl else raw), B, D, hc, wc, int(padded_size[0]), int(padded_size[1]), int(use_cl),
+                                     _ptr(positions), int(positions.shape[2]), int(ordering == "xy"), _ptr(counts), cap, float(scale), _ptr(out),
+                                     _stream(raw)), "einx_desc_sample_pos")
+    return out
+
+
+def refine_keypoints(score, indices, counts, positions, pads=(0, 0, 0, 0), ordering="yx", raw=None, raw_cl=None, sparse_desc=None, scale=1.0):
+    """Sub-pixel refinement of detected keypoints IN PLACE (einx.h: einx_refine_keypoints): columns 0 and 1 of positions
+    [B,cap,3] from the parabola through each peak of score [B,1,Hp,Wp] / [B,Hp,Wp] and its neighbours; with sparse_desc [B,cap,D]
+    (cell-8 networks) the keypoints' descriptor rows are resampled from raw [B,D,hc,wc] (raw_cl: its channels-last copy) at
+    the refined positions.  Without sparse_desc: positions only.  -> positions"""
+    _dev_check(score, positions, raw, raw_cl, sparse_desc)
+    _dev_check(indices, counts, dt=I32)
+    B = score.shape[0]
+    Hp, Wp = score.shape[-2:]
+    w0, w1, h0, h1 = pads
+    cap = indices.shape[1]
+    if tuple(positions.shape) != (B, cap, 3) or tuple(indices.shape) != (B, cap) or counts.numel() != B or score.numel() != B * Hp * Wp:
+        raise ValueError(f"einx: refine_keypoints wants score [B,Hp,Wp], indices [B,cap], counts [B] and positions [B,cap,3]; got "
+                         f"{tuple(score.shape)}, {tuple(indices.shape)}, {tuple(counts.shape)}, {tuple(positions.shape)}")
+    bilinear = sparse_desc is not None
+    D = hc = wc = 0
+    src = None
+    if bilinear:
+        if raw is None:
+            raise ValueError("einx: resampling the descriptors needs the raw map")
+        _, D, hc, wc = raw.shape
+        if tuple(sparse_desc.shape) != (B, cap, D) or raw.shape[0] != B:
+            raise ValueError(f"einx: sparse_desc must be [B,cap,D] = {(B, cap, D)}, got {tuple(sparse_desc.shape)}")
+        src = raw_cl if raw_cl is not None else raw
+    check(lib().einx_refine_keypoints(_ptr(score), B, Hp, Wp, Hp - h0 - h1, Wp - w0 - w1, h0, w0, int(ordering == "xy"), _ptr(indices), _ptr(counts),
+                                      cap, _ptr(positions), _ptr(src), D, hc, wc, int(bilinear), int(bilinear and raw_cl is not None), float(scale),
+                                      _ptr(sparse_desc), _stream(score)), "einx_refine_keypoints")
+    return positions
+
+
 def normalize_map(raw, scale, want_cl=False):
     """-> normalised map like `raw`; with want_cl also the channels-last copy [B,P,D] of the raw values."""
     _dev_check(raw)

@@ -329,7 +329,7 @@ class EIM(nn.Module):
         """every attribute that changes what `_enqueue` puts on the stream (part of the graph cache key)"""
         def ext(e):
             return tuple(getattr(e, k, None) for k in ("dense_outputs", "detection_top_k", "detection_threshold", "nms_radius", "remove_borders",
-                                                       "ordering", "dilate_mask", "conv_mode"))
+                                                       "ordering", "dilate_mask", "conv_mode", "keypoint_mode"))
         m = self.matcher.matcher
         mk = None if m is None else (type(m).__name__,) + tuple(repr(getattr(m, k, None)) for k in ("want_log_assignment", "ratio_thresh", "distance_thresh")) \
             + (repr(getattr(getattr(m, "conf", None), "filter_threshold", None)),) \

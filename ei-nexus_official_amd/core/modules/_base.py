@@ -23,6 +23,19 @@ class NativeExtractor(nn.Module):
     # to binary16, fp32 accumulation and epilogue.  Results then follow that contract, not the fp32 forward.  Read at every call.
     half_precision = False
 
+    # opt-in: keypoints refined to sub-pixel positions by a parabola through each peak of the score map (one extra
+    # launch after the detection; cell-8 descriptors are resampled at the refined positions).  Scores, `indices`, `nms` and the
+    # dense outputs stay pixel-quantised.  Results then depart from the reference's pixel centres.  Read at every call.
+    subpixel = False
+
+    @property
+    def keypoint_mode(self):
+        """"subpixel" when `subpixel` is set, the module is in eval mode and its parameters are on a GPU; "pixel" otherwise"""
+        if not self.subpixel or self.training:
+            return "pixel"
+        p = next(self.parameters(), None)
+        return "subpixel" if p is not None and p.device.type == "cuda" else "pixel"
+
     @property
     def conv_mode(self):
         """"fp16" when `half_precision` is set, the module is in eval mode and its parameters are on a GPU; "fp32" otherwise"""
@@ -187,7 +200,8 @@ class NativeExtractor(nn.Module):
         scale = self._scale_host
         # (the engine's weight watch rides on the call and reports through its own device word, bf.det.stale)
         return eng.run(x, score_mask, scale=scale, dilate_mask=self.dilate_mask, dense=self.dense_outputs if dense is None else dense,
-                       nms_iters=nms_iters, input_div=input_div, defer_dense=defer_dense, half=self.conv_mode == "fp16")
+                       nms_iters=nms_iters, input_div=input_div, defer_dense=defer_dense, half=self.conv_mode == "fp16",
+                       subpixel=self.keypoint_mode == "subpixel")
 
     @on_input_device
     def forward(self, x, score_mask=None, **kwargs):

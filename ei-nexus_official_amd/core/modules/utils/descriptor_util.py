@@ -2,7 +2,7 @@
 (core/modules/utils/descriptor_util.py), backed by csrc/desc.hip (kernels K6/K10)."""
 import torch
 
-from ...._native import desc_sample, normalize_map, upsample_normalize
+from ...._native import desc_sample, desc_sample_pos, normalize_map, upsample_normalize
 
 
 def _f32(t):
@@ -56,7 +56,8 @@ def _pack_positions(positions, size, bilinear):
     if bad and bool(torch.stack(bad).any()):
         if bilinear:
             raise NotImplementedError(f"einx: sparsify_low_resolution_descriptors samples at pixel centres (y + 0.5, x + 0.5) inside the "
-                                      f"padded image {(H, W)}; a position with another fractional part or outside it is not supported")
+                                      f"padded image {(H, W)}; a position with another fractional part or outside it is not supported "
+                                      f"(sample_descriptors_at samples at any position)")
         raise IndexError(f"position out of bounds for the descriptor map of size {(H, W)}")
     return idx, cnt
 
@@ -82,6 +83,34 @@ def sparsify_low_resolution_descriptors(raw_descriptors, positions, image_size, 
     idx, cnt = _pack_positions(positions, (Hp, Wp), bilinear=True)
     out = desc_sample(raw, idx, cnt, (Hp, Wp), bilinear=True, scale=_scale(scale_factor))
     return [out[b, :int(positions[b].shape[0])] for b in range(len(positions))]
+
+
+def sample_descriptors_at(raw_descriptors, positions, image_size, scale_factor=1.0, ordering="yx"):
+    """What the reference's sparsify_low_resolution_descriptors (descriptor_util.py:74-128) returns for ANY finite positions --
+    projected, warped or sub-pixel points, inside or outside the image: bilinear grid_sample (align_corners=False, zero padding)
+    of raw_descriptors [B,C,hc,wc] at the float positions (list of [n_i,>=2] rows, (y, x, ..) or with ordering="xy" (x, y, ..), in
+    the frame of `image_size` = (H, W) with pixel centres at .5), then normalise * scale.  -> list of [n_i,C].
+    A non-finite coordinate is a ValueError (one small reduction and one read-back per call, as in _pack_positions)."""
+    if ordering not in ("yx", "xy"):
+        raise ValueError(f"ordering must be 'yx' or 'xy', got {ordering!r}")
+    raw = _f32(raw_descriptors).contiguous()
+    B = len(positions)
+    if B != raw.shape[0]:
+        raise ValueError(f"{B} position lists for a batch of {raw.shape[0]} descriptor maps")
+    ns = [int(p.shape[0]) for p in positions]
+    if any(p.dim() != 2 or p.shape[1] < 2 for p in positions):
+        raise ValueError("positions must be [n, >= 2] per image")
+    nonempty = [_f32(p[:, :2]) for p in positions if p.shape[0]]
+    if nonempty and not bool(torch.stack([torch.isfinite(p).all() for p in nonempty]).all()):
+        raise ValueError("einx: sample_descriptors_at needs finite positions (a NaN or infinite coordinate was given)")
+    cap = max(ns + [1])
+    pos = torch.zeros((B, cap, 2), dtype=torch.float32, device=raw.device)
+    for b, p in enumerate(positions):
+        if ns[b]:
+            pos[b, :ns[b]] = p[:, :2]
+    cnt = torch.tensor(ns, dtype=torch.int32, device=raw.device)
+    out = desc_sample_pos(raw, pos, cnt, (int(image_size[0]), int(image_size[1])), _scale(scale_factor), ordering=ordering)
+    return [out[b, :ns[b]] for b in range(B)]
 
 
 def upsample_descriptors(raw_descriptors, image_size, scale_factor=1.0):

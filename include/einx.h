@@ -256,6 +256,31 @@ int einx_detect(const float* score, const einx_detect_params* p, void* ws, float
 int einx_desc_sample(const float* raw, int B, int D, int hc, int wc, int Hp, int Wp, int bilinear, int channels_last,
                      const int32_t* indices, const int32_t* counts, int cap, float scale, float* out, void* stream);
 
+/* sparsify_low_resolution_descriptors at GIVEN float positions (descriptor_util.py:74-128: grid_sample bilinear,
+ * align_corners=False, zero padding outside the map, then F.normalize * scale) -- for projected, warped or refined points.
+ * positions [B,cap,pos_stride >= 2] in the padded frame (pixel centres at .5), rows (y, x, ...) or with ordering_xy (x, y, ...);
+ * counts [B] rows are read per image (clamped to cap); out [B,cap,D].  Any coordinate is accepted: the map coordinate is tested
+ * as a float before it is converted, a position whose four taps lie outside the map (or a non-finite one) gives a zero row.  A
+ * position (y + 0.5, x + 0.5) gives einx_desc_sample's row of index y * Wp + x bit for bit.  No workspace. */
+int einx_desc_sample_pos(const float* raw, int B, int D, int hc, int wc, int Hp, int Wp, int channels_last, const float* positions,
+                         int pos_stride, int ordering_xy, const int32_t* counts, int cap, float scale, float* out, void* stream);
+
+/* Opt-in sub-pixel keypoints (a departure from the reference, whose keypoints are pixel centres).  For each of
+ * the first counts[b] keypoints of einx_detect / einx_extract: (y, x) from indices; per axis, with c the score at the peak and
+ * (l, r) its two neighbours along the axis on the padded score map [B,Hp,Wp], the offset is 0 when a neighbour is outside the map
+ * or !(l < c && r < c), otherwise, in fp32 and in this order,
+ *   a = l - c; b = r - c; den = a + b; num = l - r; delta = (0.5f * num) / den      (IEEE division)
+ * clamped to +-(0.5 - 2^-10), which keeps floor() of the refined position on the detected pixel for map sides <= 8192 (larger
+ * maps are refused).  positions [B,cap,3]: columns 0 and 1 become ((y + 0.5f + dy) - h0, (x + 0.5f + dx) - w0) in the ordering;
+ * column 2 (the score at the integer peak) and indices are not touched.
+ * bilinear = 1 (cell-8 networks): the keypoint's row of sparse_desc [B,cap,D] is resampled at the refined position, from raw
+ * [B,D,hc,wc] or with channels_last = 1 its [B,hc*wc,D] copy, like einx_desc_sample_pos; with both offsets 0 the row equals
+ * einx_desc_sample's bit for bit.  bilinear = 0 (cell-1 networks): positions only; raw, D, hc, wc, scale are ignored and
+ * sparse_desc may be NULL.  One launch, no workspace, no host synchronisation: capturable. */
+int einx_refine_keypoints(const float* score, int B, int Hp, int Wp, int H, int W, int h0, int w0, int ordering_xy,
+                          const int32_t* indices, const int32_t* counts, int cap, float* positions, const float* raw, int D, int hc,
+                          int wc, int bilinear, int channels_last, float scale, float* sparse_desc, void* stream);
+
 /* normalize_descriptors over channels of a dense map (descriptor_util.py:21-28). raw/out [B,D,P].
  * raw_cl: optional [B,P,D] channels-last copy of `raw` (un-normalised) for einx_desc_sample, or NULL. */
 int einx_normalize_map(const float* raw, int B, int D, int P, float scale, float* out, float* raw_cl, void* stream);
