@@ -70,6 +70,11 @@ class PoseParams(ctypes.Structure):
                [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
+class PoseRefineParams(ctypes.Structure):
+    _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap", "cols", "kp_yx", "k_f64", "rounds", "lm_iters")] + \
+               [("thresh", ctypes.c_double)]
+
+
 class HomographyParams(ctypes.Structure):
     _fields_ = [("struct_size", c_size_t)] + [(n, ctypes.c_int32) for n in ("B", "cap", "cols", "kp_yx", "max_iters", "n_thr")] + \
                [("thresh", ctypes.c_double), ("conf", ctypes.c_double), ("he_thr", c_float * 4), ("seed", ctypes.c_uint64)]
@@ -248,6 +253,8 @@ SIGNATURES = {
     "einx_relative_pose_ws_bytes": (c_size_t, [ctypes.POINTER(PoseParams)]),
     "einx_relative_pose": (c_int, [ctypes.POINTER(PoseParams)] + [c_void_p] * 13),
     "einx_essential_5pt": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "einx_relative_pose_refine_ws_bytes": (c_size_t, [ctypes.POINTER(PoseRefineParams)]),
+    "einx_relative_pose_refine": (c_int, [ctypes.POINTER(PoseRefineParams)] + [c_void_p] * 18),
     "einx_homography_ws_bytes": (c_size_t, [ctypes.POINTER(HomographyParams)]),
     "einx_homography": (c_int, [ctypes.POINTER(HomographyParams)] + [c_void_p] * 11),
     "einx_homography_dlt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

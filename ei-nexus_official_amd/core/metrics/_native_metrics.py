@@ -5,7 +5,7 @@ import torch
 
 from ..._native import on_input_device
 from ... import _native as N
-from ..._lib import AbsPoseParams, GeomDenseParams, GeomProjectParams, GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, check
+from ..._lib import AbsPoseParams, GeomDenseParams, GeomProjectParams, GtDenseParams, GtMatchesParams, HomographyParams, MetricParams, PoseMetricParams, PoseParams, PoseRefineParams, check
 
 
 def metric_names(mma_thr=(1, 3), vdd_thr=(1, 3), prefix_vdd="VDD"):
@@ -171,18 +171,36 @@ def _ransac_call(params, ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering, max
     return p, ws, mask, status, rows
 
 
-@on_input_device
-def relative_pose(mk0, mk1, nmatch, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx", max_iters=1000, seed=POSE_SEED):
-    """RANSAC essential matrix + recoverPose + update_one's errors for a batch (csrc/pose.hip, DESIGN.md 8b), no host sync.
-    mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the device, K0 / K1 [B,3,3] float32 or float64 (numpy's dtype rules
-    follow K's), T_0to1 [B,4,4] or None.  Returns device tensors (R [B,3,3] f64, t [B,3] f64, mask [B,cap] bool,
-    status [B] int32, rows [B,4] f64 = R_err, t_err, pose_err, inlier ratio)."""
+def _check_refine(who, refine, rounds, iters, rounds_name="refine_rounds", iters_name="refine_iters"):
+    """the refinement's options: rounds 1..4, iterations 1..50, and neither given without the refinement"""
+    for name, v, lo, hi in ((rounds_name, rounds, 1, 4), (iters_name, iters, 1, 50)):
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"einx: {who}: {name} is an integer of {lo}..{hi}, not {v!r}")
+    if not refine and (int(rounds), int(iters)) != (2, 10):
+        raise ValueError(f"einx: {who}: {rounds_name} / {iters_name} are options of the refinement: pass refine=True with them")
+
+
+def _pose_inputs_k(mk0, K0, K1, T_0to1):
     B, dev = mk0.shape[0], mk0.device
     k_f64 = K0.dtype == torch.float64 or K1.dtype == torch.float64
     kdt = torch.float64 if k_f64 else torch.float32
     K0 = K0.to(dev, kdt).reshape(B, 9).contiguous()
     K1 = K1.to(dev, kdt).reshape(B, 9).contiguous()
     T = None if T_0to1 is None else T_0to1.to(dev, torch.float64).reshape(B, 16).contiguous()
+    return k_f64, K0, K1, T
+
+
+@on_input_device
+def relative_pose(mk0, mk1, nmatch, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx", max_iters=1000, seed=POSE_SEED, refine=False,
+                  refine_rounds=2, refine_iters=10):
+    """RANSAC essential matrix + recoverPose + update_one's errors for a batch (csrc/pose.hip, DESIGN.md 8b), no host sync.
+    mk0 / mk1 [B,cap,2|3] float32 and nmatch int32 [B] on the device, K0 / K1 [B,3,3] float32 or float64 (numpy's dtype rules
+    follow K's), T_0to1 [B,4,4] or None.  Returns device tensors (R [B,3,3] f64, t [B,3] f64, mask [B,cap] bool,
+    status [B] int32, rows [B,4] f64 = R_err, t_err, pose_err, inlier ratio).  refine=True: the pose is then fitted to its inliers
+    (refine_relative_pose) and R, t, mask and rows are those of the refinement; status is unchanged."""
+    _check_refine("relative_pose", refine, refine_rounds, refine_iters)
+    B, dev = mk0.shape[0], mk0.device
+    k_f64, K0, K1, T = _pose_inputs_k(mk0, K0, K1, T_0to1)
     L = N.lib()
     p, ws, mask, status, rows = _ransac_call(PoseParams, L.einx_relative_pose_ws_bytes, mk0, mk1, nmatch, thresh, conf, ordering, max_iters,
                                              seed, 4, k_f64=int(k_f64))
@@ -190,13 +208,61 @@ def relative_pose(mk0, mk1, nmatch, K0, K1, T_0to1=None, thresh=1.0, conf=0.999,
     t = torch.empty((B, 3), dtype=torch.float64, device=dev)
     check(L.einx_relative_pose(ctypes.byref(p), N._ptr(mk0), N._ptr(mk1), N._ptr(nmatch), N._ptr(K0), N._ptr(K1), N._ptr(T), N._ptr(ws),
                                N._ptr(R), N._ptr(t), N._ptr(mask), N._ptr(status), N._ptr(rows), N._stream(mk0)), "einx_relative_pose")
+    if refine:
+        R, t, mask, _, rows, _ = refine_relative_pose(mk0, mk1, nmatch, K0, K1, R, t, mask, status, T, thresh, ordering, refine_rounds,
+                                                      refine_iters)
+        return R, t, mask, status, rows
     return R, t, mask.bool(), status, rows
 
 
+REFINE_INFO = ("kept", "rounds", "accepted", "last_set")  # the columns of refine_relative_pose's info
+
+
 @on_input_device
-def batch_relative_pose(mr, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx"):
+def refine_relative_pose(mk0, mk1, nmatch, K0, K1, R, t, mask, status, T_0to1=None, thresh=1.0, ordering="yx", rounds=2, lm_iters=10):
+    """Fits the poses relative_pose returned to their inliers (csrc/pose.hip: pose_refine_kernel), no host sync:
+    Levenberg-Marquardt on the Sampson distances over E = [t]x R, `rounds` rounds of inlier selection with at most `lm_iters`
+    iterations each.  mk0 ... K1 and thresh / ordering as relative_pose took them; R [B,3,3], t [B,3], mask [B,cap], status [B] as it
+    returned them.  Returns device tensors (R, t, mask [B,cap] bool, info [B,4] int32 = REFINE_INFO: kept (1 refined, 0 the input
+    pose came back, -1 no pose), rounds run, steps accepted, size of the last round's set; rows [B,4] f64 as relative_pose's, of the
+    returned pose; cost [B,2] f64: the mean squared residual over the last round's set before and after it, NaN without a round).
+    The refined pose is kept only when its inlier count is not below the input's."""
+    _check_refine("refine_relative_pose", True, rounds, lm_iters, "rounds", "lm_iters")
+    B, cap, cols = mk0.shape
+    dev = mk0.device
+    k_f64, K0, K1, T = _pose_inputs_k(mk0, K0, K1, T_0to1)
+    N._dev_check(mk0, mk1)
+    N._dev_check(nmatch, status, dt=torch.int32)
+    R_in = R.to(dev, torch.float64).reshape(B, 9).contiguous()
+    t_in = t.to(dev, torch.float64).reshape(B, 3).contiguous()
+    mask_in = mask.to(dev, torch.uint8).reshape(B, cap).contiguous()
+    p = PoseRefineParams()
+    p.struct_size = ctypes.sizeof(PoseRefineParams)
+    p.B, p.cap, p.cols, p.kp_yx, p.k_f64, p.rounds, p.lm_iters = B, cap, cols, int(ordering == "yx"), int(k_f64), int(rounds), int(lm_iters)
+    p.thresh = float(thresh)
+    L = N.lib()
+    ws = N._workspace(L.einx_relative_pose_refine_ws_bytes(ctypes.byref(p)), dev)
+    R_out = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
+    t_out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    mask_out = torch.empty((B, cap), dtype=torch.uint8, device=dev)
+    rows = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    cost = torch.empty((B, 2), dtype=torch.float64, device=dev)
+    P = N._ptr
+    check(L.einx_relative_pose_refine(ctypes.byref(p), P(mk0), P(mk1), P(nmatch), P(K0), P(K1), P(R_in), P(t_in), P(mask_in), P(status), P(T),
+                                      P(ws), P(R_out), P(t_out), P(mask_out), P(rows), P(info), P(cost), N._stream(mk0)),
+          "einx_relative_pose_refine")
+    return R_out, t_out, mask_out.bool(), info, rows, cost
+
+
+@on_input_device
+def batch_relative_pose(mr, K0, K1, T_0to1=None, thresh=1.0, conf=0.999, ordering="yx", refine=False, refine_rounds=2, refine_iters=10):
     """relative_pose of an EIM match result (MatchResult: mk0 / mk1 / nmatch), no host sync"""
-    return relative_pose(mr.mk0, mr.mk1, mr.nmatch, K0, K1, T_0to1, thresh, conf, ordering)
+    if not refine:
+        _check_refine("batch_relative_pose", refine, refine_rounds, refine_iters)
+        return relative_pose(mr.mk0, mr.mk1, mr.nmatch, K0, K1, T_0to1, thresh, conf, ordering)
+    return relative_pose(mr.mk0, mr.mk1, mr.nmatch, K0, K1, T_0to1, thresh, conf, ordering, refine=True, refine_rounds=refine_rounds,
+                         refine_iters=refine_iters)
 
 
 @on_input_device

@@ -163,15 +163,18 @@ class HomographyEstimation:
 
 class RelativePoseEstimation:
     """matching_metrics.py:347-559 with the reference's constructor, attributes and methods; estimate_pose runs csrc/pose.hip
-    for the one pair (RANSAC essential matrix, recoverPose's cheirality vote) and hands back numpy like cv2 does."""
+    for the one pair (RANSAC essential matrix, recoverPose's cheirality vote) and hands back numpy like cv2 does.  refine=True
+    (not the reference's; off by default): the pose is then fitted to its inliers on the device and estimate_pose
+    returns the refined pose and its mask."""
 
-    def __init__(self, name, pose_thresh, ransac_thresh=1.0, ransac_conf=0.999, ordering="yx") -> None:
+    def __init__(self, name, pose_thresh, ransac_thresh=1.0, ransac_conf=0.999, ordering="yx", refine=False) -> None:
         self.metric_name = name
         self.to_device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
         self.pose_thresh = pose_thresh
         self.ransac_thresh = ransac_thresh
         self.ransac_conf = ransac_conf
         self.ordering = ordering
+        self.refine = bool(refine)
         self.error_list = []
         assert ordering in {"xy", "yx"}
 
@@ -184,7 +187,7 @@ class RelativePoseEstimation:
             return None
         mk0, mk1, nm = _batch_of_one(matched_keypoints1, matched_keypoints2, self.to_device)
         R, t, mask, status, _ = relative_pose(mk0, mk1, nm, torch.as_tensor(K0).to(mk0.device)[None], torch.as_tensor(K1).to(mk0.device)[None],
-                                              None, thresh, conf, ordering)
+                                              None, thresh, conf, ordering, refine=self.refine)
         st = int(status[0])
         if POSE_STATUS.get(st) == "noE":
             print("\nE is None while trying to recover pose.\n")

@@ -12,6 +12,10 @@
 //   pose_score_kernel    one workgroup per (iteration, pair): Sampson inlier counts of the sample's models
 //   ransac_select_kernel one lane per pair: OpenCV's sequential scan with its shrinking iteration bound, resumed per round
 //   pose_recover_kernel  one workgroup per pair: decomposition, cheirality vote, mask, errors
+//
+// einx_relative_pose_refine (tests/pose_refine_f64.py) then fits such a pose to its Sampson inliers, opt-in:
+//   pose_refine_norm_kernel  the same normalisation into the refinement's own workspace
+//   pose_refine_kernel       one workgroup per pair: rounds of inlier selection + Levenberg-Marquardt, keep rule, mask, errors
 #include "einx_common.h"
 #include "ransac.h"
 
@@ -662,6 +666,31 @@ __device__ void decompose(const double* e0, double* R1, double* R2, double* t) {
     }
 }
 
+// relative_pose_error + update_one (matching_metrics.py:452-518): R_err, t_err, pose_err of (R, t) against T [4,4] into rows[0..2]
+__device__ void pose_error_rows(const double* R, const double* t, const double* T, double* rows) {
+  const double tg0 = T[3], tg1 = T[7], tg2 = T[11];
+  const double ngt = sqrt(tg0 * tg0 + tg1 * tg1 + tg2 * tg2);
+  const double nrm = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]) * ngt;
+  const double rad2deg = 57.29577951308232;
+  double c = (t[0] * tg0 + t[1] * tg1 + t[2] * tg2) / nrm;
+  if (!isnan(c)) c = fmin(fmax(c, -1.0), 1.0);
+  double t_err = acos(c) * rad2deg;
+  t_err = isnan(t_err) ? t_err : fmin(t_err, 180.0 - t_err);
+  if (!isfinite(ngt)) t_err = 0.0;
+  double tr = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    double d = 0.0;
+    for (int k = 0; k < 3; ++k) d += R[3 * k + i] * T[4 * k + i];
+    tr += d;
+  }
+  double cs = (tr - 1.0) / 2.0;
+  if (!isnan(cs)) cs = fmin(fmax(cs, -1.0), 1.0);
+  const double R_err = fabs(acos(cs)) * rad2deg;
+  rows[0] = R_err;
+  rows[1] = t_err;
+  rows[2] = isfinite(t_err) ? fmax(R_err, t_err) : R_err;
+}
+
 __global__ __launch_bounds__(256) void pose_recover_kernel(const PoseArgs a) {
   __shared__ double cand[4][12];  // (R, t) of (R1,t), (R2,t), (R1,-t), (R2,-t)
   __shared__ int red[4][4];
@@ -765,31 +794,378 @@ __global__ __launch_bounds__(256) void pose_recover_kernel(const PoseArgs a) {
     rows[0] = rows[1] = rows[2] = __longlong_as_double(0x7ff8000000000000LL);
     return;
   }
-  // relative_pose_error + update_one (matching_metrics.py:452-518)
-  const double* T = (const double*)a.T + (size_t)b * 16;
-  const double* R = keepR;
-  const double* t = keepR + 9;
-  const double tg0 = T[3], tg1 = T[7], tg2 = T[11];
-  const double ngt = sqrt(tg0 * tg0 + tg1 * tg1 + tg2 * tg2);
-  const double nrm = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]) * ngt;
-  const double rad2deg = 57.29577951308232;
-  double c = (t[0] * tg0 + t[1] * tg1 + t[2] * tg2) / nrm;
-  if (!isnan(c)) c = fmin(fmax(c, -1.0), 1.0);
-  double t_err = acos(c) * rad2deg;
-  t_err = isnan(t_err) ? t_err : fmin(t_err, 180.0 - t_err);
-  if (!isfinite(ngt)) t_err = 0.0;
-  double tr = 0.0;
-  for (int i = 0; i < 3; ++i) {
-    double d = 0.0;
-    for (int k = 0; k < 3; ++k) d += R[3 * k + i] * T[4 * k + i];
-    tr += d;
+  pose_error_rows(keepR, keepR + 9, (const double*)a.T + (size_t)b * 16, rows);
+}
+
+// ---------------------------------------------------------------------------------------------- refinement on the inliers (8w)
+// Levenberg-Marquardt on the signed Sampson distances of the current Sampson inliers over the five parameters of E = [t]x R
+// (R <- exp([w]x) R, t moved in its tangent plane and renormalised), in rounds that re-select the inliers; the refined pose is
+// kept when a step was accepted and its inlier count is not below the input pose's.  tests/pose_refine_f64.py restates it.
+constexpr double FLT_EPS = 1.1920928955078125e-07;
+constexpr int RF_MIN_SET = 6;  // a round needs this many Sampson inliers: five parameters and one to spare
+constexpr int RF_SUMS = 21;    // J^T J (packed upper 5x5: 15), J^T r (5), |r|^2
+
+struct RefineWs {
+  double4* xn;   // [B,cap] (u1, v1, u2, v2) normalised
+  float* thr2;   // [B] (float)(thr * thr)
+  uint8_t* inl;  // [B,cap] the current round's set; in the end the Sampson inliers of the refined pose
+};
+
+// the workspace's regions; ws == nullptr: only their total size in *bytes
+RefineWs carve(const einx_pose_refine_params* p, void* ws, size_t* bytes = nullptr) {
+  const size_t B = p->B, cap = p->cap;
+  WsCarver c{(char*)ws};
+  RefineWs w;
+  w.xn = c.take<double4>(B * cap);
+  w.thr2 = c.take<float>(B);
+  w.inl = c.take<uint8_t>(B * cap);
+  if (bytes) *bytes = c.bytes;
+  return w;
+}
+
+bool refine_params_ok(const einx_pose_refine_params* p) {
+  return p && p->struct_size == sizeof(einx_pose_refine_params) && p->B > 0 && p->cap > 0 && (p->cols == 2 || p->cols == 3) &&
+         (p->kp_yx == 0 || p->kp_yx == 1) && (p->k_f64 == 0 || p->k_f64 == 1) && p->rounds >= 1 && p->rounds <= 4 && p->lm_iters >= 1 &&
+         p->lm_iters <= 50 && p->thresh > 0.0 && p->thresh <= 1.7976931348623157e308;
+}
+
+struct RefineArgs {
+  const int32_t* nmatch;
+  const double *R_in, *t_in;
+  const uint8_t* mask_in;
+  const int32_t* status_in;
+  const double* T;
+  double *R_out, *t_out, *rows_out, *cost_out;
+  uint8_t* mask_out;
+  int32_t* info_out;
+  RefineWs w;
+  int cap, rounds, lm_iters;
+};
+
+// the normalisation of pose_norm_kernel into the refinement's workspace (no scan state to start)
+__global__ void pose_refine_norm_kernel(const PoseArgs a) {
+  const int b = blockIdx.y;
+  const int n = min(a.nmatch[b], a.p.cap);
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  if (a.p.k_f64)
+    norm_pair<double>(a, b, t);
+  else
+    norm_pair<float>(a, b, t);
+}
+
+struct PoseRefineLds {
+  double red[4][RF_SUMS];
+  double tot[RF_SUMS];
+  double cur[RF_SUMS];  // the sums at the accepted pose
+  double M[5][6];       // the damped system [A + lambda diag(A) | J^T r]
+  double fac[5];
+  double m[12];         // the accepted pose: R row-major, t
+  double mn[12];        // the trial pose
+  double EG[6][9];      // E = [t]x R of the pose last linearised and its five directions
+  int cnt[4];
+};
+
+__device__ __forceinline__ int tri5(int j, int k) { return j * 5 - j * (j - 1) / 2 + (k - j); }  // packed upper triangle, j <= k
+
+// [v]x M
+__device__ __forceinline__ void skew_mul(const double* v, const double* M, double* out) {
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    out[j] = v[1] * M[6 + j] - v[2] * M[3 + j];
+    out[3 + j] = v[2] * M[j] - v[0] * M[6 + j];
+    out[6 + j] = v[0] * M[3 + j] - v[1] * M[j];
   }
-  double cs = (tr - 1.0) / 2.0;
-  if (!isnan(cs)) cs = fmin(fmax(cs, -1.0), 1.0);
-  const double R_err = fabs(acos(cs)) * rad2deg;
-  rows[0] = R_err;
-  rows[1] = t_err;
-  rows[2] = isfinite(t_err) ? fmax(R_err, t_err) : R_err;
+}
+
+// the tangent plane of the unit sphere at t: k = the smallest |t_i| (the first on ties), b1 = e_k x t normalised, b2 = t x b1
+__device__ __forceinline__ void tangent_basis(const double* t, double* b1, double* b2) {
+  const double a0 = fabs(t[0]), a1 = fabs(t[1]), a2 = fabs(t[2]);
+  int k = 0;
+  double am = a0;
+  if (a1 < am) {
+    k = 1;
+    am = a1;
+  }
+  if (a2 < am) k = 2;
+  double c0 = 0.0, c1 = -t[2], c2 = t[1];
+  if (k == 1) {
+    c0 = t[2];
+    c1 = 0.0;
+    c2 = -t[0];
+  } else if (k == 2) {
+    c0 = -t[1];
+    c1 = t[0];
+    c2 = 0.0;
+  }
+  const double nn = sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+  b1[0] = c0 / nn;
+  b1[1] = c1 / nn;
+  b1[2] = c2 / nn;
+  b2[0] = t[1] * b1[2] - t[2] * b1[1];
+  b2[1] = t[2] * b1[0] - t[0] * b1[2];
+  b2[2] = t[0] * b1[1] - t[1] * b1[0];
+}
+
+// E and the five directions of E at the pose m into EG, matrix k by thread k < 6: E = [t]x R, then [t]x [e_k]x R for the
+// rotation, then [b1]x R and [b2]x R.  Every matrix is [v]x N with v of (t, b1, b2) and N of (R, [e_k]x R).
+__device__ __forceinline__ void refine_linearise(const double* m, double (*EG)[9], int k) {
+  double R[9], t[3], b1[3], b2[3], N[9], v[3], out[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) R[e] = m[e];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) t[e] = m[9 + e];
+  const double ek[3] = {k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0, k == 3 ? 1.0 : 0.0};
+  skew_mul(ek, R, N);
+  tangent_basis(t, b1, b2);
+#pragma unroll
+  for (int e = 0; e < 9; ++e) N[e] = (k >= 1 && k <= 3) ? N[e] : R[e];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) v[e] = k == 4 ? b1[e] : k == 5 ? b2[e] : t[e];
+  skew_mul(v, N, out);
+#pragma unroll
+  for (int e = 0; e < 9; ++e) EG[k][e] = out[e];
+}
+
+// the trial pose of the step d from m into mn (one thread): abs_pose.hip::apply_step's closed form of exp([w]x) for the rotation,
+// t + d[3] b1 + d[4] b2 renormalised for the translation
+__device__ __forceinline__ void refine_step(const double* m, const double* d, double* mn) {
+  const double th = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  double A = 1.0, Bc = 0.5;
+  if (th > 0.0) {
+    A = sin(th) / th;
+    const double h = sin(0.5 * th) / th;
+    Bc = 2.0 * h * h;
+  }
+  const double W[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
+  double X[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double w2 = (W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j]) + W[3 * i + 2] * W[6 + j];
+      X[3 * i + j] = ((i == j ? 1.0 : 0.0) + A * W[3 * i + j]) + Bc * w2;
+    }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) mn[3 * i + j] = (X[3 * i] * m[j] + X[3 * i + 1] * m[3 + j]) + X[3 * i + 2] * m[6 + j];
+  double t[3], b1[3], b2[3], tn[3];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) t[e] = m[9 + e];
+  tangent_basis(t, b1, b2);
+#pragma unroll
+  for (int e = 0; e < 3; ++e) tn[e] = (t[e] + d[3] * b1[e]) + d[4] * b2[e];
+  const double nn = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
+#pragma unroll
+  for (int e = 0; e < 3; ++e) mn[9 + e] = tn[e] / nn;
+}
+
+// the Sampson inliers of E among the n matches (pose_score_kernel's compare): their count, uniform across the workgroup; with
+// flags, each thread records its matches tid, tid + 256, ...
+__device__ int refine_count(PoseRefineLds& L, const double* E, const double4* xn, int n, float thr2, uint8_t* flags) {
+  const int tid = threadIdx.x;
+  int c = 0;
+  for (int j0 = 0; j0 < n; j0 += 256) {
+    const int j = j0 + tid;
+    const bool in = j < n && sampson(E, xn[j < n ? j : 0]) <= thr2;  // a NaN error is never an inlier
+    if (flags && j < n) flags[j] = in;
+    c += __popcll(__ballot(in));
+  }
+  __syncthreads();
+  if ((tid & 63) == 0) L.cnt[tid >> 6] = c;
+  __syncthreads();
+  return L.cnt[0] + L.cnt[1] + L.cnt[2] + L.cnt[3];
+}
+
+// J^T J (packed upper), J^T r and |r|^2 of r = d / sqrt(s) over the flagged matches at the pose linearised in L.EG, into L.tot:
+// per thread over its matches, a butterfly inside each wave, then the waves in order (a fixed order)
+__device__ void refine_pass(PoseRefineLds& L, const double4* xn, const uint8_t* flags, int n) {
+  const int tid = threadIdx.x, wv = tid >> 6;
+  double acc[RF_SUMS];
+#pragma unroll
+  for (int e = 0; e < RF_SUMS; ++e) acc[e] = 0.0;
+  for (int j = tid; j < n; j += 256) {
+    if (!flags[j]) continue;
+    const double4 pt = xn[j];
+    const double x1 = pt.x, y1 = pt.y, x2 = pt.z, y2 = pt.w;
+    // E and the directions are read from LDS per match: hoisted out of the loop, the 54 loop-invariant doubles take 108 VGPRs
+    // and the kernel 220 bytes of scratch (as in polish above)
+    __asm__ volatile("" ::: "memory");
+    const double* E = L.EG[0];
+    const double a = E[0] * x1 + E[1] * y1 + E[2];
+    const double b = E[3] * x1 + E[4] * y1 + E[5];
+    const double c = E[6] * x1 + E[7] * y1 + E[8];
+    const double p = E[0] * x2 + E[3] * y2 + E[6];
+    const double q = E[1] * x2 + E[4] * y2 + E[7];
+    const double d = x2 * a + y2 * b + c;
+    const double s = a * a + b * b + p * p + q * q;
+    const double rs = sqrt(s);
+    const double r = d / rs;
+    double J[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const double* G = L.EG[1 + k];
+      const double da = G[0] * x1 + G[1] * y1 + G[2];
+      const double db = G[3] * x1 + G[4] * y1 + G[5];
+      const double dc = G[6] * x1 + G[7] * y1 + G[8];
+      const double dp = G[0] * x2 + G[3] * y2 + G[6];
+      const double dq = G[1] * x2 + G[4] * y2 + G[7];
+      const double dd = x2 * da + y2 * db + dc;
+      const double ds = 2.0 * (a * da + b * db + p * dp + q * dq);
+      J[k] = dd / rs - d * ds / (2.0 * s * rs);
+    }
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+      for (int k = i; k < 5; ++k, ++e) acc[e] += J[i] * J[k];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) acc[15 + i] += J[i] * r;
+    acc[20] += r * r;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < RF_SUMS; ++k) {
+    double x = acc[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
+    if ((tid & 63) == 0) L.red[wv][k] = x;
+  }
+  __syncthreads();
+  if (tid < RF_SUMS) L.tot[tid] = ((L.red[0][tid] + L.red[1][tid]) + L.red[2][tid]) + L.red[3][tid];
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void pose_refine_kernel(const RefineArgs a) {
+  __shared__ PoseRefineLds L;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = min(a.nmatch[b], a.cap);
+  const size_t cap = a.cap;
+  uint8_t* mout = a.mask_out + b * cap;
+  const uint8_t* min_ = a.mask_in + b * cap;
+  uint8_t* inl = a.w.inl + b * cap;
+  const double4* xn = a.w.xn + b * cap;
+  double* Ro = a.R_out + (size_t)b * 9;
+  double* to = a.t_out + (size_t)b * 3;
+  double* rows = a.rows_out ? a.rows_out + (size_t)b * 4 : nullptr;
+  double* cost = a.cost_out ? a.cost_out + (size_t)b * 2 : nullptr;
+  int32_t* info = a.info_out + (size_t)b * 4;
+  const double inf = __longlong_as_double(0x7ff0000000000000LL), nan = __longlong_as_double(0x7ff8000000000000LL);
+  if (a.status_in[b] < 0) {  // no pose to refine (uniform across the workgroup)
+    for (size_t j = tid; j < cap; j += 256) mout[j] = 0;
+    if (tid != 0) return;
+    for (int i = 0; i < 9; ++i) Ro[i] = 0.0;
+    for (int i = 0; i < 3; ++i) to[i] = 0.0;
+    if (rows) {
+      rows[0] = rows[1] = rows[2] = inf;
+      rows[3] = 0.0;
+    }
+    info[0] = -1;
+    info[1] = info[2] = info[3] = 0;
+    if (cost) cost[0] = cost[1] = nan;
+    return;
+  }
+  if (tid < 9)
+    L.m[tid] = a.R_in[(size_t)b * 9 + tid];
+  else if (tid < 12)
+    L.m[tid] = a.t_in[(size_t)b * 3 + (tid - 9)];
+  __syncthreads();
+  if (tid < 6) refine_linearise(L.m, L.EG, tid);
+  __syncthreads();
+  const float thr2 = n > 0 ? a.w.thr2[b] : 0.0f;
+  const int c_in = refine_count(L, L.EG[0], xn, n, thr2, nullptr);
+  int accepted = 0, ran = 0, last = 0;
+  double cost0 = nan, cost1 = nan;
+  for (int round = 0; round < a.rounds; ++round) {
+    // L.EG is linearised at L.m here
+    const int cs = refine_count(L, L.EG[0], xn, n, thr2, inl);
+    if (cs < RF_MIN_SET) break;
+    refine_pass(L, xn, inl, n);
+    if (tid < RF_SUMS) L.cur[tid] = L.tot[tid];
+    __syncthreads();
+    ++ran;
+    last = cs;
+    cost0 = L.cur[20] / (double)cs;
+    double lambda = 1e-3;
+    for (int iter = 0; iter < a.lm_iters; ++iter) {
+      if (tid < 30) {
+        const int r = tid / 6, k = tid % 6;
+        L.M[r][k] = k == 5 ? L.cur[15 + r] : L.cur[r <= k ? tri5(r, k) : tri5(k, r)] + (r == k ? lambda * L.cur[tri5(r, r)] : 0.0);
+      }
+      __syncthreads();
+      if (!gauss_jordan<5, 6>(L.M, L.fac, 0.0)) break;
+      double d[5], dmax = 0.0;
+      bool fin = true;
+#pragma unroll
+      for (int e = 0; e < 5; ++e) {
+        d[e] = -L.M[e][5];
+        fin &= isfinite(d[e]);
+        dmax = fmax(dmax, fabs(d[e]));
+      }
+      if (!fin) break;
+      if (tid == 0) refine_step(L.m, d, L.mn);
+      __syncthreads();
+      if (tid < 6) refine_linearise(L.mn, L.EG, tid);
+      __syncthreads();
+      refine_pass(L, xn, inl, n);
+      const double S = L.cur[20], Sd = L.tot[20];
+      __syncthreads();
+      if (Sd < S) {  // a non-finite trial cost is a rejection
+        if (tid < 12) L.m[tid] = L.mn[tid];
+        if (tid < RF_SUMS) L.cur[tid] = L.tot[tid];
+        lambda = lambda / 10.0;
+        ++accepted;
+      } else {
+        lambda = lambda * 10.0;
+      }
+      __syncthreads();
+      if (dmax < FLT_EPS) break;
+    }
+    __syncthreads();
+    if (tid < 6) refine_linearise(L.m, L.EG, tid);  // the last trial may have been rejected
+    __syncthreads();
+    cost1 = L.cur[20] / (double)cs;
+  }
+  const int c_ref = refine_count(L, L.EG[0], xn, n, thr2, inl);
+  const bool kept = accepted > 0 && c_ref >= c_in;
+  int nmask = 0;
+  for (size_t j0 = 0; j0 < cap; j0 += 256) {
+    const size_t j = j0 + tid;
+    bool in = false;
+    if (j < cap) {
+      if (kept)
+        in = j < (size_t)n && inl[j] && cheiral(L.m, L.m + 9, xn[j]);
+      else
+        in = min_[j] != 0;
+      mout[j] = kept ? (uint8_t)in : min_[j];
+    }
+    nmask += __popcll(__ballot(in && j < (size_t)n));
+  }
+  __syncthreads();
+  if ((tid & 63) == 0) L.cnt[tid >> 6] = nmask;
+  __syncthreads();
+  if (tid != 0) return;
+  nmask = L.cnt[0] + L.cnt[1] + L.cnt[2] + L.cnt[3];
+  const double* Rk = kept ? L.m : a.R_in + (size_t)b * 9;
+  const double* tk = kept ? L.m + 9 : a.t_in + (size_t)b * 3;
+  for (int i = 0; i < 9; ++i) Ro[i] = Rk[i];
+  for (int i = 0; i < 3; ++i) to[i] = tk[i];
+  info[0] = kept ? 1 : 0;
+  info[1] = ran;
+  info[2] = accepted;
+  info[3] = last;
+  if (cost) {
+    cost[0] = cost0;
+    cost[1] = cost1;
+  }
+  if (!rows) return;
+  rows[3] = (double)nmask / (double)n;  // mask.mean()
+  if (!a.T) {
+    rows[0] = rows[1] = rows[2] = nan;
+    return;
+  }
+  pose_error_rows(Rk, tk, a.T + (size_t)b * 16, rows);
 }
 
 }  // namespace
@@ -847,6 +1223,68 @@ EINX_EXPORT int einx_essential_5pt(const double* x1, const double* x2, int n_pro
   EINX_CHECK_ARG(x1 && x2 && E_out && n_solutions, "null pointer");
   EINX_CHECK_ARG(n_problems > 0, "n_problems > 0");
   hipLaunchKernelGGL(essential_5pt_kernel, dim3((unsigned)n_problems), dim3(64), 0, (hipStream_t)stream, x1, x2, E_out, n_solutions);
+  EINX_CHECK_LAUNCH();
+  return EINX_OK;
+}
+
+EINX_EXPORT size_t einx_relative_pose_refine_ws_bytes(const einx_pose_refine_params* p) {
+  if (!refine_params_ok(p)) return 0;
+  size_t bytes = 0;
+  carve(p, nullptr, &bytes);
+  return bytes;
+}
+
+EINX_EXPORT int einx_relative_pose_refine(const einx_pose_refine_params* p, const float* mk0, const float* mk1, const int32_t* nmatch,
+                                          const void* K0, const void* K1, const double* R_in, const double* t_in, const uint8_t* mask_in,
+                                          const int32_t* status_in, const double* T_0to1, void* ws, double* R_out, double* t_out,
+                                          uint8_t* mask_out, double* rows_out, int32_t* info_out, double* cost_out, void* stream) {
+  EINX_CHECK_ARG(p && p->struct_size == sizeof(einx_pose_refine_params), "einx_pose_refine_params.struct_size mismatch");
+  EINX_CHECK_ARG(mk0 && mk1 && nmatch && K0 && K1, "null pointer among the matches and intrinsics");
+  EINX_CHECK_ARG(R_in && t_in && mask_in && status_in, "null pointer among the input pose (R_in, t_in, mask_in, status_in)");
+  EINX_CHECK_ARG(ws && R_out && t_out && mask_out && info_out, "null pointer among ws, R_out, t_out, mask_out, info_out");
+  EINX_CHECK_ARG(p->B > 0 && p->cap > 0 && (p->cols == 2 || p->cols == 3), "bad shape");
+  EINX_CHECK_ARG(p->kp_yx == 0 || p->kp_yx == 1, "kp_yx is 0 or 1");
+  EINX_CHECK_ARG(p->k_f64 == 0 || p->k_f64 == 1, "k_f64 is 0 or 1");
+  EINX_CHECK_ARG(p->rounds >= 1 && p->rounds <= 4, "rounds is 1..4");
+  EINX_CHECK_ARG(p->lm_iters >= 1 && p->lm_iters <= 50, "lm_iters is 1..50");
+  EINX_CHECK_ARG(refine_params_ok(p), "thresh is a positive number of pixels");
+  hipStream_t s = (hipStream_t)stream;
+  const RefineWs w = carve(p, ws);
+  PoseArgs na = {};  // what norm_pair reads: the matches, the intrinsics, the layout, the threshold, where xn and thr2 go
+  na.mk0 = mk0;
+  na.mk1 = mk1;
+  na.nmatch = nmatch;
+  na.K0 = K0;
+  na.K1 = K1;
+  na.w.xn = w.xn;
+  na.w.thr2 = w.thr2;
+  na.p.B = p->B;
+  na.p.cap = p->cap;
+  na.p.cols = p->cols;
+  na.p.kp_yx = p->kp_yx;
+  na.p.k_f64 = p->k_f64;
+  na.p.thresh = p->thresh;
+  const unsigned B = (unsigned)p->B;
+  hipLaunchKernelGGL(pose_refine_norm_kernel, dim3((unsigned)einx_cdiv(p->cap, 256), B), dim3(256), 0, s, na);
+  EINX_CHECK_LAUNCH();
+  RefineArgs a;
+  a.nmatch = nmatch;
+  a.R_in = R_in;
+  a.t_in = t_in;
+  a.mask_in = mask_in;
+  a.status_in = status_in;
+  a.T = T_0to1;
+  a.R_out = R_out;
+  a.t_out = t_out;
+  a.rows_out = rows_out;
+  a.cost_out = cost_out;
+  a.mask_out = mask_out;
+  a.info_out = info_out;
+  a.w = w;
+  a.cap = p->cap;
+  a.rounds = p->rounds;
+  a.lm_iters = p->lm_iters;
+  hipLaunchKernelGGL(pose_refine_kernel, dim3(B), dim3(256), 0, s, a);
   EINX_CHECK_LAUNCH();
   return EINX_OK;
 }

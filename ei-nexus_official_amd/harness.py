@@ -32,7 +32,8 @@ import torch
 
 from . import _native as native
 from .core.metrics._native_metrics import (MATCH_PR_NAMES, batch_absolute_pose, batch_gt_matches, batch_homography, batch_metrics,
-                                            batch_metrics_pose, batch_relative_pose, gt_matches, match_pr, metric_names, pose_metric_names)
+                                            batch_metrics_pose, batch_relative_pose, gt_matches, match_pr, metric_names, pose_metric_names,
+                                            refine_relative_pose)
 from .datasets.representations import EventStage, build_representation, events_representation_batch
 
 
@@ -357,6 +358,14 @@ def rpe_summary(rows, pose_thresh=(5, 10, 20), name="RPE"):
     return _summary(cols, r[:, 2], pose_thresh, name)
 
 
+def refined_summary(kept, _=None, name="RPE"):
+    """RPE_refined_ratio from the per-pair kept column of refine_relative_pose (1 the refined pose, 0 the input pose came back, -1
+    no pose): the share of the pairs with a pose whose refined pose was kept; NaN when no pair has a pose"""
+    k = _rows_f64(kept, 1)[:, 0]
+    posed = int(np.count_nonzero(k >= 0))
+    return {f"{name}_refined_ratio": float(np.count_nonzero(k == 1)) / posed if posed else float("nan")}
+
+
 def ape_summary(rows, thresholds, name="APE"):
     """the APE keys from per-pair rows of batch_absolute_pose (R_err, |t - t_gt|, t angle, inlier ratio, usable ratio; inf errors
     for a pair without a pose, which counts 0 under every threshold): the mean of each key over its finite values"""
@@ -459,6 +468,11 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
       host synchronisation; result() gains APE_R_errs (degrees), APE_t_errs (the depth map's unit), APE_t_angles, APE_inliers,
       APE_usable and APE@{deg}deg_{dist}_ratio per threshold (both errors within it; a pair without a pose counts 0).  A batch
       with pose but no depth contributes no row.
+    * `pose_refine=True` (False by default: nothing extra is launched and result() is unchanged).  The relative pose above is that
+      of one five-point sample, as OpenCV returns it.  With `pose_refine` it is then fitted to its inliers on the device
+      (refine_relative_pose, DESIGN.md 8w: Levenberg-Marquardt on the Sampson distances, kept only when no inlier is lost), with no
+      host synchronisation: the RPE_* keys are those of the refined poses, and result() gains RPE_refined_ratio, the share of the
+      pairs with a pose whose refined pose was kept.
     * `result()`: the metric means, plus -- once poses were given -- the reference's rpe_dict keys (RPE_R_errs, RPE_t_errs,
       RPE_pose_errs, RPE_inliers, RPE@t_ratio, RPE@t_auc; :326-334).  Under a process group the per-pair pose rows are
       all-gathered before the AUC.  Once depth was given: the four matcher_metrics means over the pairs that have keypoints.
@@ -470,7 +484,11 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
     def __init__(self, model, bins, resolution=(346, 260), mma_thr=(1, 3), vdd_thr=(1, 3), pose_thresh=(5, 10, 20), ransac_thresh=1.0,
                  ransac_conf=0.999, he_thresh=None, he_ransac_thresh=3.0, he_conf=0.995, representation_type="VoxelGrid", losses=None,
                  matcher_loss=False, reproj_thr=None, epi_thr=None, occlusion_th=None, label_cc_th=None, abs_pose_thresh=None,
-                 abs_pose_ransac_thresh=8.0, abs_pose_conf=0.99):
+                 abs_pose_ransac_thresh=8.0, abs_pose_conf=0.99, pose_refine=False):
+        if not isinstance(pose_refine, (bool, np.bool_)):
+            raise ValueError(f"einx: pose_refine is True or False, not {pose_refine!r}")
+        self.pose_refine = bool(pose_refine)
+        self._pose_kept = []  # per batch [P,1] float64: refine_relative_pose's kept column (1 refined, 0 the input pose, -1 no pose)
         if label_cc_th is not None and not float(label_cc_th) > 0:
             raise ValueError("einx: label_cc_th is a distance in pixels (> 0), or None for labels without the occlusion check")
         self.label_cc_th = None if label_cc_th is None else float(label_cc_th)
@@ -516,8 +534,15 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
                                                   self.gt_neg_th, cc_th=cc), ef, imf)
         if batch.pose is not None:
             K0, K1, T = batch.pose
-            self._pose_rows.append(batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf,
-                                                       ordering=ef._batched.ordering)[4])
+            pose = batch_relative_pose(self.model._last_match, K0, K1, T, self.ransac_thresh, self.ransac_conf, ordering=ef._batched.ordering)
+            if self.pose_refine:
+                mr = self.model._last_match
+                _, _, _, info, rows, _ = refine_relative_pose(mr.mk0, mr.mk1, mr.nmatch, K0, K1, pose[0], pose[1], pose[2], pose[3], T,
+                                                              self.ransac_thresh, ef._batched.ordering)
+                self._pose_rows.append(rows)
+                self._pose_kept.append(info[:, :1].to(torch.float64))
+            else:
+                self._pose_rows.append(pose[4])
             if self.abs_pose_thresh is not None and batch.depth is not None:
                 self._abs_pose_rows.append(batch_absolute_pose(self.model._last_match, K0, K1, depth0=batch.depth[0], T_0to1=T,
                                                                thresh=self.abs_pose_ransac_thresh, conf=self.abs_pose_conf,
@@ -532,6 +557,8 @@ class DifferentTimeEvaluator(_MatcherLabels, SameTimeEvaluator):
     def result(self):
         out = super().result()
         out.update(_gathered_summary(self._pose_rows, 4, rpe_summary, self.pose_thresh))
+        if self.pose_refine:
+            out.update(_gathered_summary(self._pose_kept, 1, refined_summary, None))
         if self.abs_pose_thresh is not None:
             out.update(_gathered_summary(self._abs_pose_rows, 5, ape_summary, self.abs_pose_thresh))
         self._label_results(out)

@@ -961,6 +961,44 @@ int einx_relative_pose(const einx_pose_params* p, const float* mk0, const float*
 int einx_essential_5pt(const double* x1, const double* x2, int n_problems, double* E_out, int32_t* n_solutions, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Refinement of the relative pose on its inliers (csrc/pose.hip)
+ * einx_relative_pose returns the pose of one five-point sample, as cv2.findEssentialMat + cv2.recoverPose do.  This entry fits
+ * that pose to the matches that agree with it: Levenberg-Marquardt on the signed Sampson distances over the five parameters of
+ * E = [t]x R with |t| = 1, in `rounds` rounds that each re-select the Sampson inliers of the current E (8b's points, threshold and
+ * float-rounded compare) and run at most `lm_iters` iterations on them; a round needs 6 inliers.  A written algorithm (DESIGN.md
+ * 8w), not parity with a library: the reference uses recoverPose's result as it is.
+ * Inputs: mk0 / mk1 / nmatch / K0 / K1 / T_0to1 as einx_relative_pose takes them, and its outputs for the same pairs: R_in [B,9],
+ * t_in [B,3] float64, mask_in [B,cap] uint8, status_in [B] int32.  Outputs:
+ *   R_out [B,9] / t_out [B,3] float64, mask_out [B,cap] uint8, rows_out [B,4] float64 or NULL (einx_relative_pose's four values of
+ *     the returned pose).  The refined pose is returned iff a step was accepted and its Sampson inlier count is not below the
+ *     input pose's; its mask is its Sampson inliers that pass recoverPose's cheirality test.  Otherwise the input pose and mask_in
+ *     come back unchanged, so the option never lowers a pair's inlier count.  status_in < 0: zeros and the no-pose rows.
+ *   info_out [B,4] int32: kept (1 the refined pose, 0 the input pose, -1 no pose), rounds run, steps accepted over all rounds,
+ *     the size of the last round's set (0 when no round ran),
+ *   cost_out [B,2] float64 or NULL: the mean squared residual over the last round's set before and after that round's iterations
+ *     (NaN where no round ran).
+ * Every sum runs in a fixed order: two runs give the same bits, and a pair's result depends neither on its slot nor on B.
+ * Nothing allocates, synchronises or uses atomics; the call can be captured.
+ * EINX_ERR_ARG (and a workspace query of 0): wrong struct_size, a non-positive size, cols outside {2, 3}, kp_yx / k_f64 outside
+ * {0, 1}, rounds outside 1..4, lm_iters outside 1..50, a thresh that is not a positive number; the call also refuses a null
+ * pointer other than T_0to1, rows_out and cost_out.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct einx_pose_refine_params {
+  size_t struct_size; /* sizeof(einx_pose_refine_params) (checked) */
+  int32_t B, cap, cols;
+  int32_t kp_yx;      /* 1: keypoints are (y,x,..) */
+  int32_t k_f64;      /* 0: K0 / K1 float32, 1: float64 (as einx_pose_params) */
+  int32_t rounds;     /* rounds of inlier selection + LM (1..4; 2) */
+  int32_t lm_iters;   /* LM iterations of a round at the most (1..50; 10) */
+  double thresh;      /* pixels; the value einx_relative_pose ran with */
+} einx_pose_refine_params;
+size_t einx_relative_pose_refine_ws_bytes(const einx_pose_refine_params* p); /* 0 on refused parameters */
+int einx_relative_pose_refine(const einx_pose_refine_params* p, const float* mk0, const float* mk1, const int32_t* nmatch, const void* K0,
+                              const void* K1, const double* R_in, const double* t_in, const uint8_t* mask_in, const int32_t* status_in,
+                              const double* T_0to1, void* ws, double* R_out, double* t_out, uint8_t* mask_out, double* rows_out,
+                              int32_t* info_out, double* cost_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Homography of the same-time evaluation (csrc/homography.hip)
  *   HomographyEstimation   core/metrics/matching_metrics.py:188-345 (cv2.findHomography(RANSAC) with its defaults + the corner
  *                          distances of update_one, :232-297)

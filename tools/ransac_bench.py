@@ -3,9 +3,10 @@
 pose (csrc/abs_pose.hip): B pairs of cap matches with realistic ragged counts (pose and abs_pose: MVSEC-like scenes, abs_pose with
 exact per-match depths; homography: 346 x 260 frames; 0.5 px noise, 30 % outliers), timed with device events around the whole
 launch sequence.  Only the public relative_pose / homography / absolute_pose functions are used, so EINX_LIB=ab_libs/libeinx_X.so
-times an A/B build.
+times an A/B build.  `refine` times the refinement of the relative pose on its inliers on the pose workload: the
+refinement alone on the poses relative_pose returned, and relative_pose(refine=True) against refine=False in alternating runs.
 
-    python tools/ransac_bench.py {pose,homography,abs_pose} [--B 32] [--cap 1024] [--iters 20] [--outliers 0.3]
+    python tools/ransac_bench.py {pose,homography,abs_pose,refine} [--B 32] [--cap 1024] [--iters 20] [--outliers 0.3]
 """
 import argparse
 import importlib
@@ -63,9 +64,48 @@ def abs_pose_workload(nm, scenes, cap):
     return run, (K0, K1, d0, np.ones_like(d0, dtype=np.uint8), T), report
 
 
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def refine_report(nm, a, cnt, args):
+    """the result line of the `refine` mode: the refinement alone, then the estimator with and without it in alternating runs"""
+    mk0, mk1, n, K0, K1, T = args
+    first = nm.relative_pose(mk0, mk1, n, K0, K1, T)
+    alone = lambda: nm.refine_relative_pose(mk0, mk1, n, K0, K1, *first[:4], T)  # noqa: E731
+    plain = lambda: nm.relative_pose(mk0, mk1, n, K0, K1, T)  # noqa: E731
+    both = lambda: nm.relative_pose(mk0, mk1, n, K0, K1, T, refine=True)  # noqa: E731
+    for f in (alone, plain, both) * 3:
+        f()
+    torch.cuda.synchronize()
+    t = {"refine": [], "plain": [], "with_refine": []}
+    for _ in range(a.iters):
+        for key, f in (("refine", alone), ("plain", plain), ("with_refine", both)):
+            ms, out = timed(f)
+            t[key].append(ms)
+            if key == "refine":
+                fine = out
+    info, status = fine[3].cpu().numpy(), first[3].cpu().numpy()
+    posed = status >= 0
+    before, after = first[4][:, 2].cpu().numpy()[posed], fine[4][:, 2].cpu().numpy()[posed]
+    line = {"B": a.B, "cap": a.cap, "outliers": a.outliers, "mean_nmatch": float(cnt.mean())}
+    for key, v in t.items():
+        line.update({f"{key}_ms_median": float(np.median(v)), f"{key}_ms_min": float(np.min(v)), f"{key}_ms_max": float(np.max(v))})
+    line.update({"posed": int(posed.sum()), "kept": int((info[:, 0] == 1).sum()), "mean_accepted_steps": float(info[posed, 2].mean()),
+                 "mean_last_set": float(info[posed, 3].mean()), "median_pose_err_deg_before": float(np.median(before)),
+                 "median_pose_err_deg_after": float(np.median(after)), "mean_pose_err_deg_before": float(before.mean()),
+                 "mean_pose_err_deg_after": float(after.mean())})
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("estimator", choices=("pose", "homography", "abs_pose"))
+    ap.add_argument("estimator", choices=("pose", "homography", "abs_pose", "refine"))
     ap.add_argument("--B", type=int, default=32)
     ap.add_argument("--cap", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=20)
@@ -89,19 +129,17 @@ def main():
     if a.estimator == "abs_pose":
         run, extra, report = abs_pose_workload(nm, scenes, a.cap)
     else:
-        run, extra, report = (pose_workload if a.estimator == "pose" else homography_workload)(nm, scenes)
+        run, extra, report = (homography_workload if a.estimator == "homography" else pose_workload)(nm, scenes)
     args = tuple(t(x) for x in (mk0, mk1, cnt) + extra)
+    if a.estimator == "refine":
+        return refine_report(nm, a, cnt, args)
     for _ in range(3):
         run(*args)
     torch.cuda.synchronize()
     times = []
     for _ in range(a.iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = run(*args)
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1))
+        ms, out = timed(lambda: run(*args))
+        times.append(ms)
     print(json.dumps({"B": a.B, "cap": a.cap, "outliers": a.outliers, "mean_nmatch": float(cnt.mean()), "ms_median": float(np.median(times)),
                       "ms_min": float(np.min(times)), "ms_max": float(np.max(times)), **report(out)}))
 
